@@ -12,9 +12,16 @@ Workload at N > 1 GPUs (BASELINE configs[3]): the same law over a global batch o
   of all shards are all-gathered over RCCL (xGMI), timed separately ("gather_ms").
 A step is one batched solve of all lanes; inputs are resident in HBM before the timed region,
 which brackets exactly --steps solves.  Rank 0 prints one JSON line.
+A plain run (`python bench.py --gpus 1 --steps K --warmup W`) sets up, warms up, times the K solves and
+prints the line: the headline figure and what the timed solves themselves yield (their per-kernel HIP
+event times, the roofline of qp_step from them, iteration counts, the device facts).  Everything that
+takes runs of its own -- the host-boundary rate, the QP cap 50, configs[1] and configs[4], the side
+rows and the closed loop, the CPU baselines and every parity leg -- is measured with `--full` only
+(the --no-* switches then leave single legs out).
+`--dump-outputs DIR` writes what the last timed solve returned as DIR/<name>.npy (dump_outputs).
 `python bench.py --gpus N` (N > 1, no WORLD_SIZE in the environment) starts the N ranks itself, one
 process per GPU through torch.distributed.run, before anything touches a GPU.
-Parity: every lane's u0 (and status, iteration counts) against the oracle's kernel-order twin
+Parity (--full): every lane's u0 (and status, iteration counts) against the oracle's kernel-order twin
 (oracle/qsp_twin.c, bit for bit), and against the literal restatement (oracle/qsp_oracle.c) with
 its own rounding sensitivity as the yardstick.
 `python bench.py --closed-loop` measures SURVEY §8(f) row 1 instead: main.m's closed loop, batched
@@ -164,6 +171,39 @@ def device_facts(dev):
 
 def flops_per_solve(N, K, qp_iter_total):
     return K * N * FLOP_LIN_STAGE + qp_iter_total * N * FLOP_IPM_STAGE
+
+
+DUMP_BUDGET = 48 << 20      # bytes of FP64 that --dump-outputs spends on the per-stage arrays (X, U, PI)
+DUMP_LANE_BUDGET = 16 << 20  # and on the per-lane ones (u0, status, cost): 64 MB in all
+DUMP_SEED = 20250303
+
+
+def dump_lanes(B, bytes_per_lane, budget):
+    """The lanes --dump-outputs keeps of a B-lane array: all of them when they fit the budget, otherwise
+    a fixed sample (the sorted head of a permutation seeded with DUMP_SEED: the same lanes in every run
+    and every build)."""
+    n = min(B, budget // bytes_per_lane)
+    return np.arange(B) if n == B else np.sort(np.random.default_rng(DUMP_SEED).permutation(B)[:n])
+
+
+def dump_outputs(path, per_lane, per_stage):
+    """--dump-outputs: what the timed path handed back in its last step, one FP64 .npy per output
+    (status too), first axis = lanes.  per_lane / per_stage: name -> device tensor or host array; the
+    per-stage arrays of the 65 536-lane workload are 107 MB, so they are written for dump_lanes()'s
+    sample, each group within its budget."""
+    os.makedirs(path, exist_ok=True)
+    for group, budget in ((per_lane, DUMP_LANE_BUDGET), (per_stage, DUMP_BUDGET)):
+        if not group:
+            continue
+        B = len(next(iter(group.values())))
+        lanes = dump_lanes(B, sum(8 * int(np.prod(a.shape[1:])) for a in group.values()), budget)
+        for name, a in group.items():
+            if not isinstance(a, np.ndarray):   # a device tensor: only the kept lanes cross to the host
+                import torch
+                a = a[torch.as_tensor(lanes, device=a.device)].cpu().numpy() if len(lanes) < B else a.cpu().numpy()
+            elif len(lanes) < B:
+                a = a[lanes]
+            np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def cpu_baseline(x0, traj, shape_id, N, K, target_s, threads, nlp_mode=0, twin=True, qp_iters=20, idx=1,
@@ -524,8 +564,16 @@ def launch_ranks(n):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed solves (at least 1)")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed solves also measure what takes runs of its own: the host-boundary rate, "
+                         "QP cap 50, configs[1], configs[4], the side rows, the closed loop, the CPU baselines and "
+                         "the parity legs (one GPU; the --no-* switches leave single legs out)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the outputs of the last timed solve as DIR/<name>.npy (FP64): u0, status and cost "
+                         "of every lane, X, U and PI of a fixed lane sample (dump_outputs; on several GPUs rank 0 "
+                         "writes the gathered u0 and status)")
     ap.add_argument("--global-batch", type=int, default=0,
                     help="lanes over all GPUs (0: the configuration's batch: 65 536 = configs[2] on one GPU, "
                          "262 144 = configs[3] on several, 16 384 for configs[4])")
@@ -560,6 +608,8 @@ def main():
                     help="measure the batched closed loop of main.m instead (SURVEY §8(f) row 1; one GPU; "
                          "--global-batch lanes, --steps timed runs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.closed_loop:
         if args.gpus != 1:
@@ -619,12 +669,13 @@ def main():
     d_sid = t(sid, torch.int32)
     d_Xin = torch.zeros((Bl, N + 1, 4), dtype=torch.float64, device=dev)
     d_Uin = torch.zeros((Bl, N, 2), dtype=torch.float64, device=dev)
-    d_u0 = torch.empty((Bl, 2), dtype=torch.float64, device=dev)
-    d_X = torch.empty((Bl, N + 1, 4), dtype=torch.float64, device=dev)
-    d_U = torch.empty((Bl, N, 2), dtype=torch.float64, device=dev)
-    d_PI = torch.empty((Bl, N, 4), dtype=torch.float64, device=dev)
-    d_st = torch.empty((Bl,), dtype=torch.int32, device=dev)
-    d_cost = torch.empty((Bl,), dtype=torch.float64, device=dev)
+    # zeroed, so that --dump-outputs is the same from run to run wherever a solve leaves an element alone
+    d_u0 = torch.zeros((Bl, 2), dtype=torch.float64, device=dev)
+    d_X = torch.zeros((Bl, N + 1, 4), dtype=torch.float64, device=dev)
+    d_U = torch.zeros((Bl, N, 2), dtype=torch.float64, device=dev)
+    d_PI = torch.zeros((Bl, N, 4), dtype=torch.float64, device=dev)
+    d_st = torch.zeros((Bl,), dtype=torch.int32, device=dev)
+    d_cost = torch.zeros((Bl,), dtype=torch.float64, device=dev)
     io = DeviceIO()
     for name, ten in (("x0", d_x0), ("yref", d_yref), ("yref_e", d_yref_e), ("X_in", d_Xin), ("U_in", d_Uin),
                       ("shape_id", d_sid), ("u0", d_u0), ("X_out", d_X), ("U_out", d_U), ("PI_out", d_PI),
@@ -688,6 +739,13 @@ def main():
     nbad = int(np.count_nonzero(status_all))
     if rank == 0 and args.dump_u0:
         np.savez(args.dump_u0, u0=u0_all, status=status_all)
+    if rank == 0 and args.dump_outputs:
+        # here, before --full's legs solve into the same device arrays
+        if dist:
+            dump_outputs(args.dump_outputs, {"u0": u0_all, "status": status_all}, {})
+        else:
+            dump_outputs(args.dump_outputs, {"u0": d_u0, "status": d_st, "cost": d_cost},
+                         {"X": d_X, "U": d_U, "PI": d_PI})
 
     flops_solve = float(flops_per_solve(N, K, qp_iter.astype(np.float64)).sum())   # this shard, one solve
     # dominant kernel: qp_step (one launch = one SQP iteration's QP for every lane of the shard).
@@ -771,7 +829,8 @@ def main():
         except Exception:
             pass
 
-    if world == 1:
+    full = args.full and rank == 0 and world == 1   # the legs below: runs of their own, --full only
+    if full:
         # host-boundary rate (not `value`): NMPC_controller.solve through the C ABI with x0 in
         # host memory and u0 copied back, y_ref staged on the device from the shared table
         solver.set_shape_ids(sid)
@@ -786,7 +845,7 @@ def main():
             u_host = solver.controller_solve(x0, idx_h)
         result["host_boundary_solves_per_s"] = Bl * nrep / (time.perf_counter() - th)
         gpu_dev = None
-        if rank == 0 and not args.no_cpu and not cfg4:
+        if not args.no_cpu and not cfg4:
             # the GPU's own sensitivity to the parity leg's 1e-13 x0 probes (three solves, untimed)
             gpu_dev = np.zeros(Bl)
             for sgn, f in ((1, 1.0), (-1, 1.0), (1, 3.0)):
@@ -796,8 +855,7 @@ def main():
             result["host_boundary_u0_equals_device_u0"] = bool(np.array_equal(u_host, u0))
     solver.close()
 
-    if (rank == 0 and world == 1 and not cfg4 and args.nlp == "SQP_RTI" and not args.no_qp50
-            and args.qp_iters != 50):
+    if full and not cfg4 and args.nlp == "SQP_RTI" and not args.no_qp50 and args.qp_iters != 50:
         # the same workload at acados' default QP cap, qp_solver_iter_max = 50, which the reference leaves
         # in place (NMPC_controller.m:275): the same device-resident inputs and timing as the headline
         s50 = OcpSolver(N=N, batch=Bl, sqp_iters=K, qp_iters=50, stages_per_lane=args.stages_per_lane,
@@ -825,7 +883,7 @@ def main():
             "steps": n50, "factor_walk": s50.factor_walk()}
         s50.close()
 
-    if rank == 0 and world == 1 and not args.no_configs1 and not cfg4:
+    if full and not args.no_configs1 and not cfg4:
         # BASELINE configs[1] beside the headline (its own GPU timing; CPU in full below)
         x1, traj1, sid1 = config1_inputs(N)
         s1 = OcpSolver(N=N, batch=len(x1), sqp_iters=K, qp_iters=args.qp_iters, device=gpu, nlp_solver_type=args.nlp)
@@ -844,7 +902,7 @@ def main():
         u1_gpu = s1.get_u0()
         s1.close()
 
-    if rank == 0 and world == 1 and not args.no_configs4 and not cfg4 and args.nlp == "SQP_RTI":
+    if full and not args.no_configs4 and not cfg4 and args.nlp == "SQP_RTI":
         # BASELINE configs[4] beside the headline: N = 50, B = 16 384, curved x_finals reference with a
         # random start index per lane (bench.py --config 4 measures it as the main line)
         x4, _, _, sid4, traj4, idx4b = config4_inputs(16384, 50, args.seed)
@@ -893,14 +951,14 @@ def main():
             gpu_dev4 = np.maximum(gpu_dev4, np.abs(s4.controller_solve(x4 * (1 + sgn * f * 1e-13), idx4b) - u4_gpu).max(1))
         s4.close()
 
-    if rank == 0 and world == 1 and not args.no_closed_loop and not cfg4 and args.nlp == "SQP_RTI":
+    if full and not args.no_closed_loop and not cfg4 and args.nlp == "SQP_RTI":
         result["side_rows"] = side_rows_measure(gpu, args.no_cpu)
         # SURVEY §8(f) row 1 beside the headline: main.m's closed loop, batched (bench.py --closed-loop
         # measures it alone, over 65 536 lanes by default)
         result["closed_loop"] = closed_loop_measure(16384, args.seed, 1, max(3.0, args.cpu_seconds / 3), args.no_cpu,
                                                     device=gpu)
 
-    if rank == 0 and world == 1 and not args.no_cpu and not cfg4:
+    if full and not args.no_cpu and not cfg4:
         hc = host_cpu()
         threads = hc["threads"]
         nlp_mode = 1 if args.nlp == "SQP" else 0

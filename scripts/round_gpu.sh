@@ -27,5 +27,5 @@ echo "configs[4]"
 timeout -k 10 600 python bench.py --config 4 --no-cpu --steps 5 --warmup 1 > $R/bench_cfg4.json 2> $R/bench_cfg4.err || { tail -20 $R/bench_cfg4.err; exit 1; }
 cat $R/bench_cfg4.json
 echo "bench"
-timeout -k 10 900 python bench.py > $R/bench.json 2> $R/bench.err || { tail -20 $R/bench.err; exit 1; }
+timeout -k 10 900 python bench.py --full > $R/bench.json 2> $R/bench.err || { tail -20 $R/bench.err; exit 1; }
 cat $R/bench.json

@@ -22,6 +22,33 @@ def test_host_facts_and_thread_scaling():
     np.testing.assert_allclose(ts["full_host_estimate"]["solves_per_s"], n / dt / 2 * 256)
 
 
+def test_dump_outputs_sample_is_fixed_and_within_budget(tmp_path, monkeypatch):
+    """--dump-outputs: FP64 files, whole arrays while they fit their budget, otherwise the same sorted
+    lane sample in every call; the headline workload's arrays stay under 64 MB."""
+    import bench
+    B, N = 65536, 20
+    per_stage = 8 * ((N + 1) * 4 + N * 2 + N * 4)
+    lanes = bench.dump_lanes(B, per_stage, bench.DUMP_BUDGET)
+    assert len(lanes) == bench.DUMP_BUDGET // per_stage < B and np.all(np.diff(lanes) > 0)
+    np.testing.assert_array_equal(lanes, bench.dump_lanes(B, per_stage, bench.DUMP_BUDGET))
+    assert len(lanes) * per_stage + B * 32 <= 64 << 20
+    assert bench.DUMP_BUDGET + bench.DUMP_LANE_BUDGET <= 64 << 20
+    np.testing.assert_array_equal(bench.dump_lanes(100, per_stage, bench.DUMP_BUDGET), np.arange(100))
+    rng = np.random.default_rng(0)
+    st = rng.integers(0, 3, 50).astype(np.int32)
+    X = rng.standard_normal((50, 3, 4))
+    bench.dump_outputs(str(tmp_path / "d"), {"status": st}, {"X": X})
+    got = np.load(tmp_path / "d" / "status.npy")
+    assert got.dtype == np.float64
+    np.testing.assert_array_equal(got, st)
+    np.testing.assert_array_equal(np.load(tmp_path / "d" / "X.npy"), X)
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 96 * 7)      # room for 7 of the 50 lanes
+    keep = bench.dump_lanes(50, 96, 96 * 7)
+    assert len(keep) == 7
+    bench.dump_outputs(str(tmp_path / "s"), {}, {"X": X})
+    np.testing.assert_array_equal(np.load(tmp_path / "s" / "X.npy"), X[keep])
+
+
 def test_extended_adjudication_sides_with_the_gpu_on_the_stable_lane():
     """Lane 4 891 of the bench sample: stable under every probe in both implementations, 0.1 apart in
     u0; the __float128 literal restatement sides with the device's formulation."""

@@ -39,8 +39,9 @@ extern "C" {
 #define QSP_NY_E 4
 #define QSP_NH 3          /* h = [s; u_n; u_t]      (NMPC_controller.m:237) */
 #define QSP_MAX_CTRL 64   /* spline control points per shape */
-#define QSP_ABI_VERSION 4 /* 2: struct_size fields, qp_mu_max, qsp_get_qp_stalled, QP-failure exits;
-                             3: qsp_options.factor_scan; 4: qsp_get_factor_walk */
+#define QSP_ABI_VERSION 5 /* 2: struct_size fields, qp_mu_max, qsp_get_qp_stalled, QP-failure exits;
+                             3: qsp_options.factor_scan; 4: qsp_get_factor_walk;
+                             5: qsp_rollout_cost, qsp_rollout_cost_device, qsp_cost_landscape */
 
 #define QSP_OK 0
 #define QSP_ERR_ARG (-1)
@@ -325,6 +326,83 @@ int qsp_eval_vbound(qsp_solver* s, int32_t n, const int32_t* shape_id, const dou
 int qsp_qp_solve(qsp_solver* s, int32_t nb, const double* A, const double* B, const double* b, const double* H,
                  const double* g, const double* lo, const double* hi, const double* dx0, double* dx, double* du,
                  double* pi, double* lam, int32_t* iters, int32_t* qp_status);
+
+/* ------------------------------------- rollout costs and the u0 cost landscape */
+/* The reference's optimality probe on the device (helper.m:356-431): control trajectories are rolled out
+ * from x0 with the model, the tracking cost against the references is summed
+ *     cost = sum_{k<N} 0.5 tau |[x_k; u_k] - yref_k|^2_W + 0.5 |x_N - yref_e|^2_We     (helper.m:416-423)
+ * with the handle's W, W_e (qsp_set_cost_W), and the largest violation of lh <= [s_k; u_n; u_t] <= uh
+ * over k = 0..N-1 is tracked (qsp_set_constr_h; the s bound at stage 0 only with stage0_s_bound).
+ * Two deviations from the reference, both deliberate:
+ *   model      : the probe calls the fixed-shape plant.eval_model (helper.m:362,419); the library rolls out
+ *                with the OCP's own f (PusherSliderModel.m:503-603), which is what evalModelVariableShape
+ *                evaluates (helper.m:294) and what the solver optimises over;
+ *   references : the probe reads get_y_ref(time_index + n), n = 1..Hp (helper.m:360,417), one column
+ *                later than solve stages them (index_time + k, k = 0..Hp-1, NMPC_controller.m:343-346).
+ *                These entry points evaluate against the references they are given (or the handle's
+ *                staged ones); which columns those are is the caller's choice (helper.py stages the
+ *                probe's).
+ * x0 is used as given: the s pre-wrap of NMPC_controller.m:332 is the controller's, not the probe's. */
+#define QSP_ROLLOUT_EULER 0   /* x+ = x + Ts f(x, u): the probe's and the plant's step (helper.m:419-420, :307) */
+#define QSP_ROLLOUT_RK4 1     /* the OCP's integrator: one RK4 step of Ts (NMPC_controller.m:272), qsp_eval_rk4's xn */
+typedef struct {
+    int32_t struct_size;      /* sizeof(qsp_rollout_opts) (qsp_default_rollout_opts sets it; checked as qsp_options') */
+    int32_t integrator;       /* QSP_ROLLOUT_* */
+    int32_t cost_scale;       /* 1: the handle's objective, stage terms x tau (Ts with cost_scale_Ts), as
+                                 qsp_get_cost; 0: unscaled stage terms, as helper.m:418 */
+    int32_t pad_;
+} qsp_rollout_opts;
+void qsp_default_rollout_opts(qsp_rollout_opts* opts);   /* Euler, cost_scale 1 */
+/* evaluate_cost_function (helper.m:356-367), batched: M control trajectories per lane.
+ * x0: B x 4; U: B x M x N x 2; yref: B x N x 6 and yref_e: B x 4, or NULL for the references the handle
+ * has staged (qsp_set_yref*, or the last qsp_controller_solve's); shapes per lane as qsp_set_shape_ids.
+ * cost: B x M; viol: B x M or NULL (0 when feasible); x_end: B x M x 4 or NULL (x_N). */
+int qsp_rollout_cost(qsp_solver* s, const qsp_rollout_opts* opts, int32_t M, const double* x0, const double* U,
+                     const double* yref, const double* yref_e, double* cost, double* viol, double* x_end);
+/* The same on caller-owned device memory, asynchronous on hip_stream (NULL: the handle's), as
+ * qsp_solve_device: yref, yref_e, shape_id NULL = the handle's; viol, x_end optional. */
+typedef struct {
+    const double* x0;        /* B x 4 */
+    const double* U;         /* B x M x N x 2 */
+    const double* yref;      /* B x N x 6 or NULL */
+    const double* yref_e;    /* B x 4 or NULL */
+    const int32_t* shape_id; /* B or NULL */
+    double* cost;            /* B x M */
+    double* viol;            /* B x M or NULL */
+    double* x_end;           /* B x M x 4 or NULL */
+} qsp_rollout_io;
+int qsp_rollout_cost_device(qsp_solver* s, const qsp_rollout_opts* opts, int32_t M, const qsp_rollout_io* io,
+                            void* hip_stream);
+/* debug_cost_function (helper.m:369-431): the cost of every first move u_0 = (un_grid[i], ut_grid[j]) with
+ * u_k = U_tail[k], k >= 1 (u_vect(:,1) replaced, helper.m:413), and the grid minimiser (helper.m:430-431).
+ * U_tail: B x N x 2, row 0 ignored; NULL: the last solve's solution before the controller's shift, what
+ * ocp_solver.get('u') returns at helper.m:376 (QSP_ERR_STATE before any solve; after qsp_solve_device on
+ * a caller's stream, synchronise that stream first).
+ * cost: B x n_un x n_ut row-major (cost_values(j, i) of the meshgrid, helper.m:382) or NULL: then only
+ * the B x 4 numbers below leave the device.  u_min: B x 2; cost_min: B; idx_min: B or NULL, the 0-based
+ * linear index i n_ut + j = MATLAB's ind_raw - 1.  min as MATLAB's: the first minimum in that order,
+ * NaN never wins, an all-NaN lane gives cost_min = NaN, idx_min = 0. */
+int qsp_cost_landscape(qsp_solver* s, const qsp_rollout_opts* opts, const double* x0, const double* U_tail,
+                       int32_t n_un, const double* un_grid, int32_t n_ut, const double* ut_grid, const double* yref,
+                       const double* yref_e, double* cost, double* u_min, double* cost_min, int32_t* idx_min);
+/* The same on caller-owned device memory, asynchronous on hip_stream (NULL: the handle's); NULL
+ * U_tail, yref, yref_e, shape_id, cost, idx_min as above. */
+typedef struct {
+    const double* x0;        /* B x 4 */
+    const double* U_tail;    /* B x N x 2 or NULL */
+    const double* un_grid;   /* n_un */
+    const double* ut_grid;   /* n_ut */
+    const double* yref;      /* B x N x 6 or NULL */
+    const double* yref_e;    /* B x 4 or NULL */
+    const int32_t* shape_id; /* B or NULL */
+    double* cost;            /* B x n_un x n_ut or NULL */
+    double* u_min;           /* B x 2 */
+    double* cost_min;        /* B */
+    int32_t* idx_min;        /* B or NULL */
+    int32_t n_un, n_ut;
+} qsp_landscape_io;
+int qsp_cost_landscape_device(qsp_solver* s, const qsp_rollout_opts* opts, const qsp_landscape_io* io,
+                              void* hip_stream);
 
 #ifdef __cplusplus
 }

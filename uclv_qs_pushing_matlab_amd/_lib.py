@@ -12,7 +12,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 # QSP_LIB_PATH: developer override (A/B runs of differently compiled libraries)
 LIB_PATH = os.environ.get("QSP_LIB_PATH") or os.path.join(_PKG, "libqsp_nmpc.so")
 MAX_CTRL = 64
-ABI_VERSION = 4   # include/qsp_nmpc.h QSP_ABI_VERSION
+ABI_VERSION = 5   # include/qsp_nmpc.h QSP_ABI_VERSION
 
 _lib = None
 
@@ -59,6 +59,20 @@ class DeviceIO(C.Structure):
                 ("x0", "yref", "yref_e", "X_in", "U_in", "shape_id", "u0", "X_out", "U_out", "PI_out", "status",
                  "cost")] + [("controller", C.c_int32), ("pad_", C.c_int32), ("warm_valid", C.c_void_p),
                              ("PI_in", C.c_void_p)]
+
+
+class RolloutOpts(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("integrator", C.c_int32), ("cost_scale", C.c_int32), ("pad_", C.c_int32)]
+
+
+class RolloutIO(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("x0", "U", "yref", "yref_e", "shape_id", "cost", "viol", "x_end")]
+
+
+class LandscapeIO(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in
+                ("x0", "U_tail", "un_grid", "ut_grid", "yref", "yref_e", "shape_id", "cost", "u_min", "cost_min",
+                 "idx_min")] + [("n_un", C.c_int32), ("n_ut", C.c_int32)]
 
 
 _P = C.c_void_p
@@ -127,9 +141,14 @@ _SIGS = {
     "qsp_eval_rk4": [_P, _I, _P, _D, _P, _P, _P, _P, _P],
     "qsp_eval_vbound": [_P, _I, _P, _P, _P],
     "qsp_qp_solve": [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "qsp_default_rollout_opts": [C.POINTER(RolloutOpts)],
+    "qsp_rollout_cost": [_P, C.POINTER(RolloutOpts), _I, _P, _P, _P, _P, _P, _P, _P],
+    "qsp_rollout_cost_device": [_P, C.POINTER(RolloutOpts), _I, C.POINTER(RolloutIO), _P],
+    "qsp_cost_landscape": [_P, C.POINTER(RolloutOpts), _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P],
+    "qsp_cost_landscape_device": [_P, C.POINTER(RolloutOpts), C.POINTER(LandscapeIO), _P],
     "qsp_last_error": [],
 }
-_VOID = {"qsp_default_options"}
+_VOID = {"qsp_default_options", "qsp_default_rollout_opts"}
 EXPORTED = tuple(_SIGS)
 
 

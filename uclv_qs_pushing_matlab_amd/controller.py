@@ -60,7 +60,9 @@ class NMPCController:
         """acados_ocp(create_ocp_model(), create_ocp_opts()) (:302-305).  `shapes` defaults to
         the plant's contour; pass several shapes + shape_id to mix sliders per lane."""
         s = OcpSolver(N=self.Hp, batch=self.batch, Ts=self.sample_time, **self._opts)
-        s.set_shapes(shapes if shapes is not None else [self.plant.shape])
+        shapes = list(shapes) if shapes is not None else [self.plant.shape]
+        s.set_shapes(shapes)
+        self._shape_b = np.array([sh.b for sh in shapes])                  # contour lengths (the s pre-wrap, :332)
         if shape_id is not None:
             self._shape_id = np.broadcast_to(np.asarray(shape_id, np.int32), (self.batch,)).copy()
         s.set_shape_ids(self._shape_id)

@@ -62,6 +62,8 @@ struct qsp_solver {
     DevBuf ubc, ubp, cl_x, cl_xsim, cl_amp;
     DevBuf wX, wU, wx0, wlin, wnlp, wdone, wres, wqp, wperm, wnit, whist;
     DevBuf scratch[12];
+    DevBuf ro[12];                  // staging of the rollout entry points' host arrays
+    bool solved = false;            // wU holds a solve's iterate (qsp_cost_landscape with U_tail = NULL)
     int32_t T = 0;
     bool have_traj = false;
     bool traj_per_lane = false;     // reference table per lane (B x T x 6) instead of shared (T x 6)
@@ -241,6 +243,7 @@ static int run_timed(qsp_solver* s, const SolveArgs& a) {
     HIPCHK(hipEventRecord(s->ev1, s->stream));
     HIPCHK(hipEventSynchronize(s->ev1));
     HIPCHK(hipEventElapsedTime(&s->last_ms, s->ev0, s->ev1));
+    s->solved = true;
     return QSP_OK;
 }
 
@@ -482,6 +485,7 @@ int qsp_destroy(qsp_solver* s) {
                       &s->whist};
     for (DevBuf* b : bufs) b->release();
     for (auto& b : s->scratch) b.release();
+    for (auto& b : s->ro) b.release();
     for (hipEvent_t e : s->kev) (void)hipEventDestroy(e);
     if (s->ev0) (void)hipEventDestroy(s->ev0);
     if (s->ev1) (void)hipEventDestroy(s->ev1);
@@ -1004,6 +1008,7 @@ int qsp_closed_loop_ex(qsp_solver* s, const qsp_closed_loop_opts* o, const doubl
     if (status_traj) HIPCHK(hipMemcpyAsync(status_traj, dS.p, B * T * 4, hipMemcpyDeviceToHost, s->stream));
     HIPCHK(hipStreamSynchronize(s->stream));
     HIPCHK(hipEventElapsedTime(&s->last_ms, s->ev0, s->ev1));
+    s->solved = true;
     return QSP_OK;
 }
 
@@ -1058,6 +1063,7 @@ int qsp_solve_device(qsp_solver* s, const qsp_device_io* io, void* stream) {
     }
     hipStream_t st = stream ? (hipStream_t)stream : s->stream;
     HIPCHK(launch_sqp(a, s->S, st, take_kernel_events(s), sqp_split(s)));
+    s->solved = true;
     return QSP_OK;
 }
 
@@ -1295,6 +1301,169 @@ int qsp_qp_solve(qsp_solver* s, int32_t nb, const double* A, const double* B, co
             qp_status[l] = !fin ? 1 : (infeas ? 3 : qst[l]);
         }
     }
+    return QSP_OK;
+}
+
+// ------------------------------------- rollout costs and the u0 cost landscape
+void qsp_default_rollout_opts(qsp_rollout_opts* o) {
+    std::memset(o, 0, sizeof(*o));
+    o->struct_size = (int32_t)sizeof(qsp_rollout_opts);
+    o->integrator = QSP_ROLLOUT_EULER;
+    o->cost_scale = 1;
+}
+
+// the options' checks and the handle's cost, bounds and shapes into a kernel argument block
+static int rollout_args(qsp_solver* s, const qsp_rollout_opts* o, const char* who, RolloutArgs& a) {
+    const std::string w(who);
+    if (!s || !o) return fail(QSP_ERR_ARG, w + ": null argument");
+    if (o->struct_size != (int32_t)sizeof(qsp_rollout_opts))
+        return fail(QSP_ERR_ARG, w + ": qsp_rollout_opts.struct_size != sizeof(qsp_rollout_opts) (stale layout?)");
+    if (o->integrator != QSP_ROLLOUT_EULER && o->integrator != QSP_ROLLOUT_RK4)
+        return fail(QSP_ERR_ARG, w + ": unknown integrator");
+    if (o->cost_scale != 0 && o->cost_scale != 1) return fail(QSP_ERR_ARG, w + ": cost_scale must be 0 or 1");
+    if (s->n_shapes < 1) return fail(QSP_ERR_STATE, w + ": no shapes set");
+    std::memset(&a, 0, sizeof a);
+    a.N = s->o.N;
+    a.B = s->o.batch;
+    a.integrator = o->integrator;
+    a.s0_bound = s->p.s0_bound;
+    a.Ts = s->p.Ts;
+    a.tau = o->cost_scale ? s->p.tau : 1.0;
+    std::memcpy(a.W, s->p.W, sizeof a.W);
+    std::memcpy(a.We, s->p.We, sizeof a.We);
+    std::memcpy(a.lh, s->p.lh, sizeof a.lh);
+    std::memcpy(a.uh, s->p.uh, sizeof a.uh);
+    a.shapes = s->shapes.as<ShapeDev>();
+    a.n_shapes = s->n_shapes;
+    a.shape_id = s->shape_id.as<int32_t>();
+    a.yref = s->yref.as<double>();
+    a.yref_e = s->yref_e.as<double>();
+    return QSP_OK;
+}
+
+int qsp_rollout_cost(qsp_solver* s, const qsp_rollout_opts* opts, int32_t M, const double* x0, const double* U,
+                     const double* yref, const double* yref_e, double* cost, double* viol, double* x_end) {
+    RolloutArgs a;
+    int r = rollout_args(s, opts, "qsp_rollout_cost", a);
+    if (r) return r;
+    if (!x0 || !U || !cost) return fail(QSP_ERR_ARG, "qsp_rollout_cost: null argument");
+    if (M < 1) return fail(QSP_ERR_ARG, "qsp_rollout_cost: M must be >= 1");
+    const size_t B = s->o.batch, N = s->o.N, BM = B * (size_t)M;
+    HIPCHK(hipSetDevice(s->o.device));
+    auto& b = s->ro;
+    if ((r = stage_in(s, b[0], x0, B * 4)) || (r = stage_in(s, b[1], U, BM * N * 2))) return r;
+    if (yref && (r = stage_in(s, b[2], yref, B * N * 6))) return r;
+    if (yref_e && (r = stage_in(s, b[3], yref_e, B * 4))) return r;
+    HIPCHK(b[4].ensure(BM * 8));
+    if (viol) HIPCHK(b[5].ensure(BM * 8));
+    if (x_end) HIPCHK(b[6].ensure(BM * 4 * 8));
+    a.M = M;
+    a.x0 = b[0].as<double>();
+    a.U = b[1].as<double>();
+    if (yref) a.yref = b[2].as<double>();
+    if (yref_e) a.yref_e = b[3].as<double>();
+    a.cost = b[4].as<double>();
+    a.viol = viol ? b[5].as<double>() : nullptr;
+    a.x_end = x_end ? b[6].as<double>() : nullptr;
+    HIPCHK(launch_rollout_cost(a, s->stream));
+    if ((r = stage_out(s, cost, b[4], BM))) return r;
+    if (viol && (r = stage_out(s, viol, b[5], BM))) return r;
+    if (x_end && (r = stage_out(s, x_end, b[6], BM * 4))) return r;
+    HIPCHK(hipStreamSynchronize(s->stream));
+    return QSP_OK;
+}
+
+int qsp_rollout_cost_device(qsp_solver* s, const qsp_rollout_opts* opts, int32_t M, const qsp_rollout_io* io,
+                            void* stream) {
+    RolloutArgs a;
+    int r = rollout_args(s, opts, "qsp_rollout_cost_device", a);
+    if (r) return r;
+    if (!io || !io->x0 || !io->U || !io->cost) return fail(QSP_ERR_ARG, "qsp_rollout_cost_device: missing device pointer");
+    if (M < 1) return fail(QSP_ERR_ARG, "qsp_rollout_cost_device: M must be >= 1");
+    HIPCHK(hipSetDevice(s->o.device));
+    a.M = M;
+    a.x0 = io->x0;
+    a.U = io->U;
+    if (io->yref) a.yref = io->yref;
+    if (io->yref_e) a.yref_e = io->yref_e;
+    if (io->shape_id) a.shape_id = io->shape_id;
+    a.cost = io->cost;
+    a.viol = io->viol;
+    a.x_end = io->x_end;
+    HIPCHK(launch_rollout_cost(a, stream ? (hipStream_t)stream : s->stream));
+    return QSP_OK;
+}
+
+int qsp_cost_landscape(qsp_solver* s, const qsp_rollout_opts* opts, const double* x0, const double* U_tail,
+                       int32_t n_un, const double* un_grid, int32_t n_ut, const double* ut_grid, const double* yref,
+                       const double* yref_e, double* cost, double* u_min, double* cost_min, int32_t* idx_min) {
+    RolloutArgs a;
+    int r = rollout_args(s, opts, "qsp_cost_landscape", a);
+    if (r) return r;
+    if (!x0 || !un_grid || !ut_grid || !u_min || !cost_min) return fail(QSP_ERR_ARG, "qsp_cost_landscape: null argument");
+    if (n_un < 1 || n_ut < 1) return fail(QSP_ERR_ARG, "qsp_cost_landscape: empty grid");
+    if ((long long)n_un * n_ut > (1ll << 30)) return fail(QSP_ERR_ARG, "qsp_cost_landscape: more than 2^30 grid points");
+    if (!U_tail && !s->solved)
+        return fail(QSP_ERR_STATE, "qsp_cost_landscape: U_tail = NULL needs a solve (the last solution's tail)");
+    const size_t B = s->o.batch, N = s->o.N, G = (size_t)n_un * n_ut;
+    HIPCHK(hipSetDevice(s->o.device));
+    auto& b = s->ro;
+    if ((r = stage_in(s, b[0], x0, B * 4)) || (r = stage_in(s, b[7], un_grid, (size_t)n_un)) ||
+        (r = stage_in(s, b[8], ut_grid, (size_t)n_ut)))
+        return r;
+    if (U_tail && (r = stage_in(s, b[1], U_tail, B * N * 2))) return r;
+    if (yref && (r = stage_in(s, b[2], yref, B * N * 6))) return r;
+    if (yref_e && (r = stage_in(s, b[3], yref_e, B * 4))) return r;
+    if (cost) HIPCHK(b[4].ensure(B * G * 8));
+    HIPCHK(b[9].ensure(B * 2 * 8));
+    HIPCHK(b[10].ensure(B * 8));
+    HIPCHK(b[11].ensure(B * 4));
+    a.x0 = b[0].as<double>();
+    a.U_tail = U_tail ? b[1].as<double>() : s->wU.as<double>();   // the iterate epilogue_kernel reads
+    if (yref) a.yref = b[2].as<double>();
+    if (yref_e) a.yref_e = b[3].as<double>();
+    a.n_un = n_un;
+    a.n_ut = n_ut;
+    a.un_grid = b[7].as<double>();
+    a.ut_grid = b[8].as<double>();
+    a.cost = cost ? b[4].as<double>() : nullptr;
+    a.u_min = b[9].as<double>();
+    a.cost_min = b[10].as<double>();
+    a.idx_min = b[11].as<int32_t>();
+    HIPCHK(launch_cost_landscape(a, s->stream));
+    if (cost && (r = stage_out(s, cost, b[4], B * G))) return r;
+    if ((r = stage_out(s, u_min, b[9], B * 2)) || (r = stage_out(s, cost_min, b[10], B))) return r;
+    if (idx_min && (r = stage_out(s, idx_min, b[11], B))) return r;
+    HIPCHK(hipStreamSynchronize(s->stream));
+    return QSP_OK;
+}
+
+int qsp_cost_landscape_device(qsp_solver* s, const qsp_rollout_opts* opts, const qsp_landscape_io* io, void* stream) {
+    RolloutArgs a;
+    int r = rollout_args(s, opts, "qsp_cost_landscape_device", a);
+    if (r) return r;
+    if (!io || !io->x0 || !io->un_grid || !io->ut_grid || !io->u_min || !io->cost_min)
+        return fail(QSP_ERR_ARG, "qsp_cost_landscape_device: missing device pointer");
+    if (io->n_un < 1 || io->n_ut < 1) return fail(QSP_ERR_ARG, "qsp_cost_landscape_device: empty grid");
+    if ((long long)io->n_un * io->n_ut > (1ll << 30))
+        return fail(QSP_ERR_ARG, "qsp_cost_landscape_device: more than 2^30 grid points");
+    if (!io->U_tail && !s->solved)
+        return fail(QSP_ERR_STATE, "qsp_cost_landscape_device: U_tail = NULL needs a solve (the last solution's tail)");
+    HIPCHK(hipSetDevice(s->o.device));
+    a.x0 = io->x0;
+    a.U_tail = io->U_tail ? io->U_tail : s->wU.as<double>();
+    if (io->yref) a.yref = io->yref;
+    if (io->yref_e) a.yref_e = io->yref_e;
+    if (io->shape_id) a.shape_id = io->shape_id;
+    a.n_un = io->n_un;
+    a.n_ut = io->n_ut;
+    a.un_grid = io->un_grid;
+    a.ut_grid = io->ut_grid;
+    a.cost = io->cost;
+    a.u_min = io->u_min;
+    a.cost_min = io->cost_min;
+    a.idx_min = io->idx_min;
+    HIPCHK(launch_cost_landscape(a, stream ? (hipStream_t)stream : s->stream));
     return QSP_OK;
 }
 

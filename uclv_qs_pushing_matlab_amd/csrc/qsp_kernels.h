@@ -131,4 +131,36 @@ hipError_t launch_rk4(const ShapeDev* shapes, const int32_t* sid, int n, double 
 hipError_t launch_vbound(const ShapeDev* shapes, const int32_t* sid, int n, CtrlParams cp, const double* s, double* vb,
                          hipStream_t stream);
 
+// Rollout costs and the u0 cost landscape (qsp_rollout.hip; helper.m:356-431): candidate control
+// trajectories rolled out from x0 with the OCP's f, one thread per (lane, candidate).
+struct RolloutArgs {
+    int32_t N, B;
+    int32_t integrator;        // QSP_ROLLOUT_EULER / QSP_ROLLOUT_RK4
+    int32_t s0_bound;          // 1: the s bound of h also counts at stage 0 (viol)
+    double Ts, tau;            // step; stage-cost scaling (the handle's tau, or 1 with cost_scale = 0)
+    double W[6], We[4], lh[3], uh[3];
+    const ShapeDev* shapes;
+    int32_t n_shapes;
+    const int32_t* shape_id;   // B (nullptr: shape 0); clamped into [0, n_shapes)
+    const double* x0;          // B x 4
+    const double* yref;        // B x N x 6
+    const double* yref_e;      // B x 4
+    // rollout_cost_kernel
+    int32_t M;                 // candidates per lane
+    const double* U;           // B x M x N x 2
+    double* cost;              // B x M; landscape: B x n_un x n_ut or nullptr
+    double* viol;              // B x M or nullptr
+    double* x_end;             // B x M x 4 or nullptr
+    // cost_landscape_kernel
+    const double* U_tail;      // B x N x 2, row 0 ignored
+    int32_t n_un, n_ut;
+    const double* un_grid;     // n_un
+    const double* ut_grid;     // n_ut
+    double* u_min;             // B x 2
+    double* cost_min;          // B
+    int32_t* idx_min;          // B or nullptr
+};
+hipError_t launch_rollout_cost(const RolloutArgs& a, hipStream_t stream);
+hipError_t launch_cost_landscape(const RolloutArgs& a, hipStream_t stream);
+
 }  // namespace qsp

@@ -5,9 +5,81 @@ the disturbance branch (:221-236: y offset, contact re-projected onto the contou
 fminunc restated as a damped Newton iteration), sim_noise (:240-242), the controller's delay
 prediction delay_buffer_sim and its input buffer (NMPC_controller.m:112-120, helper.m:255),
 NMPC_controller.solve, and the plant step with evalModelVariableShape and the plant's own delay
-buffer (:289-307).  Not reproduced: print/debug_cost (MATLAB figures and console output).
+buffer (:289-307).  Not reproduced: print_ (console output).
+
+helper.evaluate_cost_function and helper.debug_cost_function (helper.m:356-431), the reference's
+optimality probe, run on the device too (OcpSolver.rollout_cost / cost_landscape): the cost of a control
+trajectory rolled out with Euler steps, and the cost surface over a grid of first moves u_0 with the rest
+of the solver's trajectory held, with its grid minimiser.  The figures (helper.m:433-451) are not drawn,
+and closed_loop_matlab's debug_cost argument stays ignored: call debug_cost_function after a
+controller.solve.  Two deliberate deviations (include/qsp_nmpc.h): the model is the OCP's f instead of the
+fixed-shape plant.eval_model, and x0 is rolled out as given.
 """
 import numpy as np
+
+
+def _probe_refs(controller, t):
+    """The probe's references: columns time_index + 1 .. time_index + Hp of the controller's table, clamped
+    at its end as get_y_ref (NMPC_controller.m:307-313), time_index = round(t / Ts) (helper.m:358,409); the
+    terminal term reads column time_index + Hp (helper.m:365,422).  One column later than solve stages them
+    (index_time + k, k = 0..Hp-1, :343-346).  -> yref (Hp, 6), yref_e (4,)."""
+    if controller.y_ref is None:
+        raise RuntimeError("set_reference_trajectory must be called before the cost probe")
+    y = np.asarray(controller.y_ref, np.float64)                       # 6 x T
+    D = int(controller.delay_buff_comp)
+    if D > 0:                                                           # set_reference_trajectory (:428-429)
+        pre = np.zeros((6, D))
+        pre[5] = y[5, 0]
+        y = np.concatenate([pre, y], 1)
+    time_index = int(np.round(t / controller.sample_time))              # MATLAB round: t >= 0 here
+    idx = np.minimum(time_index + np.arange(1, controller.Hp + 1), y.shape[1])   # 1-based columns
+    yref = y[:, idx - 1].T.copy()
+    return yref, yref[-1, :4].copy()
+
+
+def _lanes_x(controller, x):
+    return np.broadcast_to(np.asarray(x, np.float64).reshape(-1, 4), (controller.batch, 4))
+
+
+def evaluate_cost_function(xn, controller, plant, t, u_vect):
+    """cost_fcn_ = evaluate_cost_function(xn, controller, plant, t, u_vect) (helper.m:356-367), batched:
+    xn (B, 4) or (4,); u_vect (B, Hp, 2), (Hp, 2) or MATLAB's 2 x Hp.  Euler rollout, stage terms unscaled
+    and without the 1/2 (:361,366): exactly twice the library's cost_scale = 0 value.  Returns (B,).
+    `plant` is kept for the signature: the model is the OCP's f (module docstring)."""
+    B, Hp = controller.batch, controller.Hp
+    u = np.asarray(u_vect, np.float64)
+    if u.ndim == 2 and u.shape == (2, Hp) and Hp != 2:
+        u = u.T
+    u = np.broadcast_to(u, (B, Hp, 2))
+    yref, yref_e = _probe_refs(controller, t)
+    c = controller.ocp_solver.rollout_cost(_lanes_x(controller, xn), u[:, None], integrator="euler", cost_scale=False,
+                                           yref=yref, yref_e=yref_e)
+    return 2.0 * c[:, 0]
+
+
+def colon(lb, ub, step):
+    """MATLAB's lb:step:ub as lb + k step, k = 0..floor((ub - lb) / step + 1e-10)."""
+    return lb + np.arange(int(np.floor((ub - lb) / step + 1e-10)) + 1) * step
+
+
+def debug_cost_function(x0, u_n_lb, u_t_lb, u_n_ub, u_t_ub, controller, plant, index, t, prewrap=False):
+    """u_min = debug_cost_function(...) (helper.m:369-431), batched and without the figure: the cost of
+    every u_0 on UN = u_n_lb:0.005:u_n_ub x UT = u_t_lb:0.005:u_t_ub (7 x 21 for the default bounds) with
+    columns 2..Hp of ocp_solver.get('u') held (:376,413) -- the last solve's solution before the controller's
+    shift -- Euler steps and the 1/2 (:418,423).
+    Returns (u_min (B, 2), cost_values (B, len(UT), len(UN)): MATLAB's meshgrid layout cost_values(j, i),
+    UN, UT).  u_min is the first minimum of cost_values(:) (:430-431).  `index` (the subplot slot) and
+    `plant` are kept for the signature.  prewrap=True applies the controller's s pre-wrap
+    (NMPC_controller.m:332) to x0 first, so the probe starts from the state the solver saw."""
+    UN, UT = colon(u_n_lb, u_n_ub, 0.005), colon(u_t_lb, u_t_ub, 0.005)     # :380-381
+    x = _lanes_x(controller, x0).copy()
+    if prewrap:
+        b = controller._shape_b[controller._shape_id]
+        x[:, 3] = np.mod(x[:, 3], b) - b * (x[:, 3] < 0)
+    yref, yref_e = _probe_refs(controller, t)
+    r = controller.ocp_solver.cost_landscape(x, UN, UT, U_tail=None, integrator="euler", cost_scale=False,
+                                             yref=yref, yref_e=yref_e)
+    return r["u_min"], np.ascontiguousarray(r["cost"].transpose(0, 2, 1)), UN, UT
 
 
 def closed_loop_matlab(plant, controller, x0, time_sim, print_=False, sim_noise=False, debug_cost=False,

@@ -71,6 +71,7 @@ class OcpSolver:
         self._lh = np.array([-0.06, 0.0, -0.05])
         self._uh = np.array([0.011, 0.03, 0.05])
         self._dirty = set(["x0", "yref", "init"])
+        self._refs_staged = False   # the device references are a controller step's, newer than set('cost_y_ref*')
         self.n_shapes = 0
         # timings=True: per-kernel HIP events around every solve, for get('time_lin'/'time_qp_sol')
         self._timings = bool(timings)
@@ -142,11 +143,13 @@ class OcpSolver:
                     raise ValueError(f"cost_y_ref stage {stage} out of range 0..{N - 1}")
                 self._yref[:, stage] = self._lanes(value, 6)
             self._dirty.add("yref")
+            self._refs_staged = False
         elif field == "cost_y_ref_e":
             if stage is not None and stage != N:
                 raise ValueError("cost_y_ref_e is only defined at stage N")
             self._yref_e[:] = self._lanes(value, 4)
             self._dirty.add("yref")
+            self._refs_staged = False
         elif field == "cost_W":
             W = np.asarray(value, np.float64)
             if W.ndim == 2:
@@ -190,6 +193,7 @@ class OcpSolver:
             check(self._L.qsp_set_x0(self._h, ptr(f64(self._x0))), "qsp_set_x0")
         if "yref" in self._dirty:
             check(self._L.qsp_set_yref(self._h, ptr(f64(self._yref)), ptr(f64(self._yref_e))), "qsp_set_yref")
+            self._refs_staged = False
         if "init" in self._dirty:
             check(self._L.qsp_set_init(self._h, ptr(f64(self._X)), ptr(f64(self._U)), ptr(f64(self._PI))),
                   "qsp_set_init")
@@ -247,6 +251,82 @@ class OcpSolver:
         check(self._L.qsp_get_cost(self._h, ptr(out)), "qsp_get_cost")
         return out
 
+    # ------------------------------- rollout costs / u0 cost landscape
+    INTEGRATORS = {"euler": 0, "rk4": 1}   # QSP_ROLLOUT_EULER / QSP_ROLLOUT_RK4
+
+    def _rollout_opts(self, integrator, cost_scale):
+        if integrator not in self.INTEGRATORS:
+            raise ValueError(f"integrator must be one of {tuple(self.INTEGRATORS)}")
+        o = _lib.RolloutOpts()
+        self._L.qsp_default_rollout_opts(C.byref(o))
+        o.integrator = self.INTEGRATORS[integrator]
+        o.cost_scale = 1 if cost_scale else 0
+        return o
+
+    def _rollout_refs(self, yref, yref_e):
+        """References of a rollout call: given arrays, or (None) the handle's staged ones -- the last controller
+        step's, or what set('cost_y_ref*') holds when that is newer (flushed here, as solve() would)."""
+        if (yref is None or yref_e is None) and "yref" in self._dirty and not self._refs_staged:
+            check(self._L.qsp_set_yref(self._h, ptr(f64(self._yref)), ptr(f64(self._yref_e))), "qsp_set_yref")
+            self._dirty.discard("yref")
+        yr = None if yref is None else f64(np.broadcast_to(np.asarray(yref, np.float64), (self.B, self.N, 6)))
+        ye = None if yref_e is None else f64(self._lanes(yref_e, 4))
+        return yr, ye
+
+    def rollout_cost(self, x0, U, integrator="euler", cost_scale=True, yref=None, yref_e=None, want_viol=False,
+                     want_x_end=False):
+        """Cost of M control trajectories per lane rolled out from x0 (helper.evaluate_cost_function,
+        helper.m:356-367, with the OCP's f): U (B, M, N, 2) -> cost (B, M); with want_viol / want_x_end a
+        tuple (cost[, viol (B, M)][, x_end (B, M, 4)]).  cost_scale: stage terms x tau as get_cost (True) or
+        unscaled as helper.m:418 (False); yref / yref_e None: the handle's references."""
+        x0 = f64(self._lanes(x0, 4))
+        U = f64(U)
+        if U.ndim != 4 or U.shape[0] != self.B or U.shape[1] < 1 or U.shape[2:] != (self.N, 2):
+            raise ValueError(f"U must be (B={self.B}, M >= 1, N={self.N}, 2), got {U.shape}")
+        M = U.shape[1]
+        o = self._rollout_opts(integrator, cost_scale)
+        yr, ye = self._rollout_refs(yref, yref_e)
+        cost = np.zeros((self.B, M))
+        viol = np.zeros((self.B, M)) if want_viol else None
+        xe = np.zeros((self.B, M, 4)) if want_x_end else None
+        check(self._L.qsp_rollout_cost(self._h, C.byref(o), M, ptr(x0), ptr(U), ptr(yr), ptr(ye), ptr(cost), ptr(viol),
+                                       ptr(xe)), "qsp_rollout_cost")
+        out = (cost,) + ((viol,) if want_viol else ()) + ((xe,) if want_x_end else ())
+        return out[0] if len(out) == 1 else out
+
+    def cost_landscape(self, x0, un, ut, U_tail=None, integrator="euler", cost_scale=True, yref=None, yref_e=None,
+                       want_surface=True):
+        """Cost of every first move u_0 = (un[i], ut[j]) with u_k = U_tail[k] for k >= 1, and the grid
+        minimiser (helper.debug_cost_function, helper.m:369-431).  U_tail (B, N, 2), row 0 ignored; None: the
+        last solve's solution before the controller's shift (ocp_solver.get('u') at helper.m:376).
+        Returns dict(cost (B, n_un, n_ut) or None, u_min (B, 2), cost_min (B,), idx_min (B,): 0-based i n_ut + j);
+        the first minimum in that order wins, NaN never does (MATLAB's min)."""
+        x0 = f64(self._lanes(x0, 4))
+        un, ut = f64(un).ravel(), f64(ut).ravel()
+        tail = None
+        if U_tail is not None:
+            tail = f64(np.broadcast_to(np.asarray(U_tail, np.float64), (self.B, self.N, 2)))
+        o = self._rollout_opts(integrator, cost_scale)
+        yr, ye = self._rollout_refs(yref, yref_e)
+        cost = np.zeros((self.B, len(un), len(ut))) if want_surface else None
+        u_min, cost_min, idx_min = np.zeros((self.B, 2)), np.zeros(self.B), np.zeros(self.B, np.int32)
+        check(self._L.qsp_cost_landscape(self._h, C.byref(o), ptr(x0), ptr(tail), len(un), ptr(un), len(ut), ptr(ut),
+                                         ptr(yr), ptr(ye), ptr(cost), ptr(u_min), ptr(cost_min), ptr(idx_min)),
+              "qsp_cost_landscape")
+        return dict(cost=cost, u_min=u_min, cost_min=cost_min, idx_min=idx_min)
+
+    def rollout_cost_device(self, io, M, integrator="euler", cost_scale=True, stream=None):
+        """rollout_cost on caller-owned device memory (io: _lib.RolloutIO of device pointers), asynchronous."""
+        o = self._rollout_opts(integrator, cost_scale)
+        check(self._L.qsp_rollout_cost_device(self._h, C.byref(o), int(M), C.byref(io),
+                                              C.c_void_p(stream) if stream else None), "qsp_rollout_cost_device")
+
+    def cost_landscape_device(self, io, integrator="euler", cost_scale=True, stream=None):
+        """cost_landscape on caller-owned device memory (io: _lib.LandscapeIO of device pointers), asynchronous."""
+        o = self._rollout_opts(integrator, cost_scale)
+        check(self._L.qsp_cost_landscape_device(self._h, C.byref(o), C.byref(io),
+                                                C.c_void_p(stream) if stream else None), "qsp_cost_landscape_device")
+
     # --------------------------------------------------- controller level
     def set_reference_trajectory(self, traj):
         """traj: 6 x T (MATLAB layout) or T x 6."""
@@ -286,6 +366,7 @@ class OcpSolver:
         x0 = f64(self._lanes(x0, 4))
         idx = i32(np.broadcast_to(np.asarray(index_time, np.int32), (self.B,)))
         self._timed(lambda: check(self._L.qsp_controller_solve(self._h, ptr(x0), ptr(idx)), "qsp_controller_solve"))
+        self._refs_staged = True
         return self.get_u0()
 
     def closed_loop(self, x0, n_steps, index0=1, noise=None, plant_delay=0.0, disturbance=False, t_dist=0,
@@ -308,6 +389,7 @@ class OcpSolver:
         st = np.zeros((self.B, n), np.int32)
         check(self._L.qsp_closed_loop_ex(self._h, C.byref(o), ptr(x0), ptr(idx), n, ptr(nz), ptr(X), ptr(Xs), ptr(U),
                                          ptr(st)), "qsp_closed_loop_ex")
+        self._refs_staged = True
         return dict(X=X, Xsim=Xs, U=U, status=st)
 
     # ------------------------------------------------ delay compensation

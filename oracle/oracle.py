@@ -107,6 +107,12 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def tw_factor_walk(opts):
+    """The factorisation the twin emulates for these options, in the library's QSP_WALK_* coding
+    (0 lane walk, 1 matrix cores, 2 associative scan): what qsp_get_factor_walk reports on the device."""
+    return int(lib().tw_factor_walk(C.byref(opts)))
+
+
 class Oracle:
     def __init__(self, names=("santal", "balea", "montana", "pulirapid"), max_ctrl=64, tab=None, twin=False):
         # tab: optional explicit shape table (n_ctrl, ctrl, knots, params) instead of named PLY objects

@@ -31,6 +31,8 @@
 #endif
 
 #include "or_opts.h"
+#include "qsp_nmpc.h"     /* QSP_WALK_* (tw_factor_walk) */
+#include "qsp_layout.h"   /* the library's own layout rules: stages per lane, lanes per instance, mfw_fits */
 
 #define TW_MAX_N 128
 #define TW_MAX_SLOTS (TW_MAX_N + 2)
@@ -363,19 +365,12 @@ typedef struct {
     double v_alpha, d_v, t_angle0, u_n_lb, u_t_ub;
 } tw_par;
 
-static int auto_S(const or_opts *o)
-{
-    if (o->stages_per_lane > 0) return o->stages_per_lane;
-    if (o->nlp_mode == 1) return 1;
-    return o->N + 1 <= 32 ? 1 : 2;
-}
-
 static void make_par(tw_par *p, const or_opts *o)
 {
     memset(p, 0, sizeof *p);
     p->N = o->N;
-    p->S = auto_S(o);
-    p->L = (p->N + p->S) / p->S;
+    p->S = stages_per_lane(o->N, o->nlp_mode, o->stages_per_lane);
+    p->L = lanes_per_instance(p->N, p->S);
     p->nlp_mode = o->nlp_mode;
     p->sqp_iters = o->sqp_iters;
     p->qp_iters = o->qp_iters;
@@ -383,16 +378,10 @@ static void make_par(tw_par *p, const or_opts *o)
     p->s0_bound = o->stage0_s_bound ? 1 : 0;
     p->factor_scan = o->factor_scan ? 1 : 0;
     /* the kernels factorise on the matrix cores where one instance per 16-lane block and a phase's
-     * stage records fit (mfw_fits: one stage per lane at 12 <= N <= 31, two stages per lane from four
-     * instances per wave down), unless the library's developer switch QSP_MFMA_WALK=0 selects the lane
-     * walk there too */
+     * stage records fit (mfw_fits, the library's own rule), unless the library's developer switch
+     * QSP_MFMA_WALK=0 selects the lane walk there too */
     const char *mw = getenv("QSP_MFMA_WALK");
-    {
-        const int G = 64 / p->L, H = (p->N + 1) / 2, CM = p->N + 1 - H;
-        const int cap = (p->S == 1 ? 12 + 2 : 24 + 4) * 64;   /* F_VA .. F_HG per slot + mfw_extra, x 64 lanes */
-        const int fits = G <= 4 && G * CM * 27 + 5 <= cap && (p->S == 2 || p->N <= 31);   /* + 5 constants */
-        p->mfma_walk = fits && !(mw && mw[0] == '0') && !o->lane_walk;
-    }
+    p->mfma_walk = mfw_fits(p->N, p->S) && !(mw && mw[0] == '0') && !o->lane_walk;
     p->Ts = o->Ts;
     p->tau = o->tau;
     memcpy(p->W, o->W, sizeof p->W);
@@ -405,6 +394,16 @@ static void make_par(tw_par *p, const or_opts *o)
     p->tol_stat = o->tol_stat; p->tol_eq = o->tol_eq; p->tol_ineq = o->tol_ineq; p->tol_comp = o->tol_comp;
     p->ls_alpha_min = o->ls_alpha_min; p->ls_alpha_red = o->ls_alpha_red; p->ls_eps = o->ls_eps;
     p->v_alpha = o->v_alpha; p->d_v = o->d_v; p->t_angle0 = o->t_angle0; p->u_n_lb = o->u_n_lb; p->u_t_ub = o->u_t_ub;
+}
+
+/* The factorisation the twin emulates for these options, in the library's QSP_WALK_* coding
+ * (qsp_get_factor_walk reports the library's side of the same choice). */
+int tw_factor_walk(const or_opts *o)
+{
+    tw_par p;
+    make_par(&p, o);
+    if (p.S == 2 && p.factor_scan) return QSP_WALK_SCAN;
+    return p.mfma_walk ? QSP_WALK_MFMA : QSP_WALK_LANE;
 }
 
 /* group_sum: the kernel's log-step shuffle tree towards the group's first lane */

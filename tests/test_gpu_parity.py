@@ -281,6 +281,9 @@ def test_horizon_and_layout_edges(oracle, N, S):
     np.testing.assert_allclose(u[~ok], r["u0"][~ok], rtol=0, atol=1e-5)
 
 
+MFMA = "matrix cores (v_mfma_f64_4x4x4_4b_f64)"
+
+
 @pytest.mark.parametrize("N, kw, want", [
     (11, {}, "lane walk"),                                        # five instances per wave: no block each
     (12, {}, "matrix cores (v_mfma_f64_4x4x4_4b_f64)"),          # four instances per wave
@@ -291,14 +294,32 @@ def test_horizon_and_layout_edges(oracle, N, S):
     (50, {}, "matrix cores (v_mfma_f64_4x4x4_4b_f64)"),          # configs[4]: two stages per lane
     (50, {"factor_scan": True}, "associative scan"),
     (20, {"stages_per_lane": 2}, "lane walk"),                   # 11 lanes: five instances per wave
+    # the edges of the rule (qsp_layout.h mfw_fits), one stage per lane ...
+    (32, {"stages_per_lane": 1}, "lane walk"),                   # one instance per wave, N > 31
+    (63, {"stages_per_lane": 1}, "lane walk"),
+    # ... and two: four instances per wave from N = 24, the fullest regions at N = 30, 31, the last horizons
+    (22, {"stages_per_lane": 2}, "lane walk"),
+    (23, {"stages_per_lane": 2}, "lane walk"),
+    (24, {"stages_per_lane": 2}, MFMA),
+    (29, {"stages_per_lane": 2}, MFMA),
+    (30, {"stages_per_lane": 2}, MFMA),
+    (31, {"stages_per_lane": 2}, MFMA),
+    (32, {"stages_per_lane": 2}, MFMA),
+    (63, {"stages_per_lane": 2}, MFMA),
+    (126, {"stages_per_lane": 2}, MFMA),
+    (127, {"stages_per_lane": 2}, MFMA),
 ])
 def test_library_reports_its_factor_walk(N, kw, want):
     """qsp_get_factor_walk (ABI 4) reports the walk the launchers take, so bench lines label runs by what
-    ran (qsp_solver.hip factor_walk_kind = mfw_use / factor_scan)."""
+    ran (qsp_solver.hip factor_walk_kind), and the twin emulates that same walk for the same options
+    (both read the rule from qsp_layout.h)."""
+    from oracle.oracle import make_opts, tw_factor_walk
     from uclv_qs_pushing_matlab_amd.solver import OcpSolver
     s = OcpSolver(N=N, batch=8, **kw)
     try:
         assert s.factor_walk() == want
+        op = make_opts(N=N, stages_per_lane=kw.get("stages_per_lane", 0), factor_scan=int(kw.get("factor_scan", False)))
+        assert OcpSolver.FACTOR_WALKS[tw_factor_walk(op)] == s.factor_walk()
     finally:
         s.close()
 
@@ -306,9 +327,11 @@ def test_library_reports_its_factor_walk(N, kw, want):
 def test_lane_walk_switch_is_reported(monkeypatch):
     from uclv_qs_pushing_matlab_amd.solver import OcpSolver
     monkeypatch.setenv("QSP_MFMA_WALK", "0")
+    from oracle.oracle import make_opts, tw_factor_walk
     for N in (20, 50):
         s = OcpSolver(N=N, batch=8)
         try:
             assert s.factor_walk() == "lane walk"
+            assert OcpSolver.FACTOR_WALKS[tw_factor_walk(make_opts(N=N))] == s.factor_walk()
         finally:
             s.close()

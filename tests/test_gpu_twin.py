@@ -172,6 +172,10 @@ def test_merit_sqp_bit_identical(twin):
     NMPC_controller.m:271-276) on 4 096 configs[2] lanes: statuses, iteration counts, u0, the
     NLP multipliers; two controller steps (the second warm-started from the shifted solution)."""
     from bench import SEED, make_inputs
+    # N = 12, 64 lanes: the shortest horizon at which the merit kernel, too, factorises on the matrix
+    # cores (N = 12 .. 14 since the range was widened; four instances per wave)
+    x12, _, _, sid12, traj12 = make_inputs(64, 12, SEED + 7)
+    controller_pair(twin, 12, 64, x12, traj12, sid12, 1, K=30, steps=2, nlp_mode=1)
     x0, _, _, sid, traj = make_inputs(4096, 20, SEED + 7)
     r = controller_pair(twin, 20, 4096, x0, traj, sid, 1, K=30, steps=2, nlp_mode=1)
     # Measured on the twin (= the device, bit for bit): 1 010 of 4 096 lanes meet tol 1e-6 within 30

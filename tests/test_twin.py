@@ -300,3 +300,23 @@ def test_factor_scan_s2_matches_walk_at_one_iteration(twin):
         u = [twin.controller_solve(make_opts(N=N, sqp_iters=1, stages_per_lane=2, factor_scan=fs), x0, traj, 1,
                                    twin.new_warm(nb, N), shape_id=sid)["u0"] for fs in (0, 1)]
         np.testing.assert_allclose(u[1], u[0], rtol=0, atol=1e-15, err_msg=f"N={N}")
+
+
+def test_factor_walk_table(monkeypatch):
+    """The walk the twin emulates (tw_factor_walk, from the library's own rule in qsp_layout.h): the
+    matrix cores exactly at N = 12 .. 31 with one stage per lane and N = 24 .. 127 with two; the
+    twin's lane_walk and the device's factor_scan override it."""
+    from oracle.oracle import tw_factor_walk
+    monkeypatch.delenv("QSP_MFMA_WALK", raising=False)
+    LANE, MFMA, SCAN = 0, 1, 2
+    for S, lo, hi in ((1, 12, 31), (2, 24, 127)):
+        for N in range(1, 128):
+            want = MFMA if lo <= N <= hi else LANE
+            assert tw_factor_walk(make_opts(N=N, stages_per_lane=S)) == want, (N, S)
+            assert tw_factor_walk(make_opts(N=N, stages_per_lane=S, lane_walk=1)) == LANE, (N, S)
+            assert tw_factor_walk(make_opts(N=N, stages_per_lane=S, factor_scan=1)) == (SCAN if S == 2 else want), (N, S)
+    # the library's choice of the layout: one stage per lane up to N = 31, and in nlp_mode 1
+    assert [tw_factor_walk(make_opts(N=N)) for N in (11, 12, 31, 32, 50)] == [LANE, MFMA, MFMA, MFMA, MFMA]
+    assert tw_factor_walk(make_opts(N=40, nlp_mode=1)) == LANE
+    monkeypatch.setenv("QSP_MFMA_WALK", "0")
+    assert [tw_factor_walk(make_opts(N=N)) for N in (20, 50)] == [LANE, LANE]

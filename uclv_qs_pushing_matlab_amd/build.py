@@ -11,7 +11,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libqsp_nmpc.so")
 SOURCES = ["qsp_solver.hip", "qsp_capi.hip", "qsp_rollout.hip"]
-HEADERS = ["qsp_math.hpp", "qsp_fp.hpp", "qsp_types.h", "qsp_kernels.h", "../../include/qsp_nmpc.h"]
+HEADERS = ["qsp_math.hpp", "qsp_fp.hpp", "qsp_types.h", "qsp_kernels.h", "qsp_layout.h", "../../include/qsp_nmpc.h"]
 ARCH = os.environ.get("QSP_OFFLOAD_ARCH", "gfx950")
 
 

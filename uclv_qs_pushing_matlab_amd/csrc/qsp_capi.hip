@@ -150,15 +150,6 @@ static void fill_params(qsp_solver* s) {
     p.ls_eps = s->o.ls_eps;
 }
 
-static int auto_S(int N) {
-    // One stage per lane keeps the QP kernel at 2 waves/SIMD with its closed-loop walks and
-    // wins while a wavefront still holds two or more instances; once one stage per lane leaves
-    // a single instance per wave (N + 1 > 32), two stages per lane (1 wave/SIMD, 2-3 instances
-    // per wave) win.  scripts/layout_sweep.sh, round 1 (one-wave workgroups): N = 10 1.32M vs
-    // 1.17M, N = 20 493k vs 422k, N = 50 (B = 16 384) 62.6k vs 70.0k solves/s for S = 1 vs 2.
-    return N + 1 <= 32 ? 1 : 2;
-}
-
 // Binary little-endian PLY with float32 vertex properties (the reference's cad_models/*.ply).
 static int read_ply_xy(const char* path, std::vector<float>& xy) {
     FILE* f = std::fopen(path, "rb");
@@ -372,7 +363,7 @@ int qsp_create(const qsp_options* o, qsp_solver** out) {
     if (!(o->qp_tol_stat > 0.0) || !(o->qp_tol_eq > 0.0) || !(o->mu_stop > 0.0) || !(o->res_stop > 0.0))
         return fail(QSP_ERR_ARG, "qsp_create: QP stop tolerances must be > 0");
     if (!(o->Ts > 0.0)) return fail(QSP_ERR_ARG, "qsp_create: Ts must be > 0");
-    int S = o->stages_per_lane > 0 ? o->stages_per_lane : (o->nlp_mode == QSP_NLP_SQP_MERIT ? 1 : auto_S(o->N));
+    const int S = stages_per_lane(o->N, o->nlp_mode, o->stages_per_lane);
     if (S < 1 || S > 2) return fail(QSP_ERR_ARG, "qsp_create: stages_per_lane must be 1 or 2");
     if (lanes_per_instance(o->N, S) > 64)
         return fail(QSP_ERR_ARG, "qsp_create: N+1 > 64*stages_per_lane (one instance must fit in a wavefront)");

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "qsp_layout.h"
 #include "qsp_types.h"
 
 #define QSP_FLAG_CONTROLLER 1u  // NMPC_controller.solve prologue: s pre-wrap, cold/warm start, clip, Euler rollout
@@ -62,9 +63,15 @@ struct SolveArgs {
     double* qp_lam;            // B x N x 6
 };
 
+// Shape of instance i of a kernel's argument block (solver, closed loop, rollout).  The ids are device
+// data that the host cannot validate without a round trip, and the table may have shrunk since they
+// were set, so every kernel clamps them into the table, by shape_clamp.
+__device__ __forceinline__ int shape_clamp(int id, int n_shapes) { return id < 0 ? 0 : (id >= n_shapes ? n_shapes - 1 : id); }
+__device__ __forceinline__ const ShapeDev& shape_clamped(const ShapeDev* shapes, int n_shapes, const int32_t* sid, int i) {
+    return shapes[shape_clamp(sid ? sid[i] : 0, n_shapes)];
+}
 
-int lanes_per_instance(int N, int S);
-// QSP_WALK_* of a handle's QP kernels (the same rule the launchers apply: mfw_use, factor_scan)
+// QSP_WALK_* of a handle's QP kernels (the launchers' own choice: factor_alt, mfw_use)
 int factor_walk_kind(const SolveParams& p, int S);
 void mfw_prepare(SolveParams& p);   // SolveParams::mfw_on / mfw_is from N and mfma_walk
 // Multi-stream split of the SQP loop (SqpStreams::parts = P > 1): the instances are cut into

@@ -1,0 +1,106 @@
+/* qsp_layout.h — the QP kernels' layout rules, in one place: how instances map onto wavefronts,
+ * how many stages a lane holds, the LDS fields of a lane, and which horizons factorise on the
+ * matrix cores.  Plain integer arithmetic that compiles as C99 and as HIP C++ (host and device):
+ * qsp_solver.hip and qsp_capi.hip include it, and so does the CPU twin that checks the kernels bit
+ * for bit (test infrastructure may read this product header; the product never reads the twin). */
+#ifndef QSP_LAYOUT_H
+#define QSP_LAYOUT_H
+
+#ifdef __HIPCC__
+#define QSP_LAYOUT_FN __host__ __device__ constexpr
+#else
+#define QSP_LAYOUT_FN static inline
+#endif
+
+#ifdef __cplusplus
+namespace qsp {
+#endif
+
+/* ------------------------------------------------------------------ instances on wavefronts
+ * One instance owns L = ceil((N + 1) / S) consecutive lanes of a wavefront (S stages per lane);
+ * a wavefront holds G = 64 / L whole instances and every QP workgroup is one wavefront. */
+enum { WAVE = 64 };
+QSP_LAYOUT_FN int lanes_per_instance(int N, int S) { return (N + S) / S; }
+QSP_LAYOUT_FN int instances_per_wave(int N, int S) { return WAVE / lanes_per_instance(N, S); }
+QSP_LAYOUT_FN long waves_for(long nI, int N, int S) {
+    return (nI + instances_per_wave(N, S) - 1) / instances_per_wave(N, S);
+}
+
+/* Stages per lane of a handle: the explicit request, else one for nlp_mode 1 (its kernels exist at
+ * one stage per lane only), else by the horizon.  One stage per lane keeps the QP kernel at
+ * 2 waves/SIMD with its closed-loop walks and wins while a wavefront still holds two or more
+ * instances; once one stage per lane leaves a single instance per wave (N + 1 > 32), two stages
+ * per lane (1 wave/SIMD, 2-3 instances per wave) win.  scripts/layout_sweep.sh, round 1 (one-wave
+ * workgroups): N = 10 1.32M vs 1.17M, N = 20 493k vs 422k, N = 50 (B = 16 384) 62.6k vs 70.0k
+ * solves/s for S = 1 vs 2. */
+QSP_LAYOUT_FN int stages_per_lane(int N, int nlp_mode, int requested) {
+    return requested > 0 ? requested : (nlp_mode == 1 || N + 1 <= 32 ? 1 : 2);
+}
+
+/* ------------------------------------------------------------------ a lane's LDS column
+ * Registers hold what the horizon recursions read on every step (stage model, gradient, Riccati
+ * factors); LDS holds what only the stage-parallel phases touch (iterate, slacks/multipliers,
+ * barrier terms, QP solution pieces): per stage slot the fields below, WAVE doubles each. */
+enum LdsField {
+    F_T = 0,      /* 6  slacks        s_lo s_hi un_lo un_hi ut_lo ut_hi */
+    F_LM = 6,     /* 6  multipliers */
+    F_V = 12,     /* 3  bounded components of the SQP iterate (s_k, u_n, u_t) */
+    F_DU = 15,    /* 2  damped QP control step */
+    F_RT = 17,    /* 6  1 / slack, refreshed whenever the slacks change */
+    F_VA = 23,    /* 3  affine-predictor bounded components (ds, dun, dut) */
+    F_VN = 26,    /* 3  corrector bounded components */
+    F_DX = 23,    /* 4  final QP state step (written after the IPM: aliases F_VA / F_VN) */
+    F_HG = 29,    /* 6  barrier Hessian (0..2) / gradient (3..5) additions */
+    F_COUNT = 35
+};
+
+/* ------------------------------------------------------------------ the matrix-core factor walk
+ * Its stage records overlay F_VA .. F_HG of every slot (free while the predictor factorises) and
+ * mfw_extra(S) more fields at the end of the workgroup's LDS (factor_walk_mfma in qsp_solver.hip).
+ * A record, row-major in the order the block lanes read it: */
+enum MfwSlot { R_G = 0, R_A = 12, R_GX = 18, R_HX3 = 22, R_HU = 23, R_GU = 25, MFW_REC = 27 };
+enum MfwOut { O_K = 0, O_Z = 8, O_COUNT = 16 };   /* K (2 x 4), rows 0, 1 of Z = [R~ | r~ | .] */
+/* the operand constants (A's ones and zeros, the zero column of [B | b | 0], Hx's fixed diagonal),
+ * at the end of the region */
+enum MfwConst { C_ONE = 0, C_ZERO = 1, C_HX = 2, C_COUNT = 5 };
+
+/* One stage per lane: two extra fields, 18 944 bytes per workgroup, so eight one-wave workgroups and
+ * a packing-sort workgroup still share a CU's LDS.  Two stages per lane: four, 37 888 bytes per
+ * workgroup -- three (1 728 doubles of records) are too few for the stride padding between
+ * the instances' records at N = 30, 31 (1 757 doubles) and N = 62, 63 (1 739), and for the five
+ * constants behind the 64 records of one instance at N = 126, 127 (1 733). */
+QSP_LAYOUT_FN int mfw_extra(int S) { return S == 1 ? 2 : 4; }
+QSP_LAYOUT_FN int lds_doubles(int S) { return (F_COUNT * S + mfw_extra(S)) * WAVE; }
+/* LDS doubles the stage records may occupy: F_VA .. F_HG of every slot plus the extra fields. */
+QSP_LAYOUT_FN int mfw_region(int S) { return ((F_COUNT - F_VA) * S + mfw_extra(S)) * WAVE; }
+/* The records of a wave's instances do not fit at once: the walk runs in two phases, stages
+ * H .. N - 1 with the terminal record, then 0 .. H - 1; CM records per instance and phase. */
+QSP_LAYOUT_FN int mfw_split(int N) { return (N + 1) / 2; }
+QSP_LAYOUT_FN int mfw_records(int N) { return N + 1 - mfw_split(N); }
+/* The instances' record regions start IS doubles apart, IS >= CM records: a stride whose multiples
+ * put the instances' reads of one operand (at most six consecutive doubles per half wave) on
+ * disjoint LDS banks (32 doubles): 9 ... 11 or 21 ... 23 mod 32 for three instances, 8 or 24 for
+ * four, 6 ... 26 for two. */
+QSP_LAYOUT_FN int mfw_stride(int CM, int G) {
+    int is = CM * MFW_REC;
+    for (;; ++is) {
+        const int m = is & 31;
+        if (G <= 1 || (G == 2 && m >= 6 && m <= 26) || (G == 3 && ((m >= 9 && m <= 11) || (m >= 21 && m <= 23))) ||
+            (G >= 4 && (m == 8 || m == 24)))
+            return is;
+    }
+}
+/* Which horizons factorise on the matrix cores: one instance per 16-lane block (G <= 4: at one
+ * stage per lane N >= 12, at two N >= 24) and the records of a phase in the region.  That is
+ * N = 12 .. 31 at one stage per lane and N = 24 .. 127 at two, narrowly: one stage per lane at
+ * N = 20 fills 896 of 896 doubles, two at N = 30, 31 use 1757 of 1792 (tests/test_twin.py pins
+ * the table). */
+QSP_LAYOUT_FN int mfw_fits(int N, int S) {
+    const int G = instances_per_wave(N, S), CM = mfw_records(N);
+    return G <= 4 && (G - 1) * mfw_stride(CM, G) + CM * MFW_REC + C_COUNT <= mfw_region(S) && (S == 2 || N <= 31);
+}
+
+#ifdef __cplusplus
+}  /* namespace qsp */
+#endif
+#endif

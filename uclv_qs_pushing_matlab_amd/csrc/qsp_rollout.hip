@@ -89,14 +89,9 @@ __device__ __forceinline__ void rollout_one(const RolloutArgs& A, const ShapeDev
     for (int c = 0; c < 4; ++c) o.x[c] = x[c];
 }
 
-__device__ __forceinline__ int shape_index(const RolloutArgs& A, int lane) {
-    const int id = A.shape_id ? A.shape_id[lane] : 0;   // device data: clamped like shape_of
-    return id < 0 ? 0 : (id >= A.n_shapes ? A.n_shapes - 1 : id);
-}
-
 // LDS image of one lane: [shape | yref N x 6 | yref_e 4 | tail N x 2 (landscape)]
 __device__ __forceinline__ void stage_lane(const RolloutArgs& A, int lane, double* lds, bool tail) {
-    const double* sh = reinterpret_cast<const double*>(A.shapes + shape_index(A, lane));
+    const double* sh = reinterpret_cast<const double*>(&shape_clamped(A.shapes, A.n_shapes, A.shape_id, lane));
     for (int q = threadIdx.x; q < RO_SHAPE_D; q += blockDim.x) lds[q] = sh[q];
     double* yr = lds + RO_SHAPE_D;
     const double* gy = A.yref + (size_t)lane * A.N * 6;
@@ -169,8 +164,8 @@ __global__ void __launch_bounds__(RO_BLOCK) rollout_cost_kernel(RolloutArgs A, i
         if (ll >= lpb || lane >= A.B) return;
         const size_t g = (size_t)lane * A.M + m;
         RollOut r;
-        rollout_one<INTEG>(A, A.shapes[shape_index(A, (int)lane)], A.x0 + (size_t)lane * 4, A.yref + (size_t)lane * A.N * 6,
-                           A.yref_e + (size_t)lane * 4, UGlobal{A.U + g * A.N * 2, vec != 0}, r);
+        rollout_one<INTEG>(A, shape_clamped(A.shapes, A.n_shapes, A.shape_id, (int)lane), A.x0 + (size_t)lane * 4,
+                           A.yref + (size_t)lane * A.N * 6, A.yref_e + (size_t)lane * 4, UGlobal{A.U + g * A.N * 2, vec != 0}, r);
         store_rollout(A, g, r);
     }
 }

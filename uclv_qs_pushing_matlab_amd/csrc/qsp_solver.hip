@@ -32,8 +32,10 @@
 #include <stdint.h>
 
 #include <atomic>
+#include <type_traits>
 
 #include "../../include/qsp_nmpc.h"
+#include "qsp_layout.h"
 #include "qsp_math.hpp"
 #include "qsp_kernels.h"
 
@@ -170,30 +172,9 @@ __device__ __forceinline__ int pack_key(int packed, int maxkey) {
 __device__ __forceinline__ int pack_record(int old, int nit) { return (int)(((unsigned)old << 8) | (unsigned)(nit & 0xff)); }
 
 // ------------------------------------------------------------- per-lane state
-// Registers hold what the horizon recursions read on every step (stage model,
-// gradient, Riccati factors); LDS holds what only the stage-parallel phases touch
-// (iterate, slacks/multipliers, barrier terms, QP solution pieces).
-constexpr int BLOCK = 64;                  // threads per workgroup: one wave (see launch_qp_step)
-enum LdsField : int {
-    F_T = 0,      // 6  slacks        s_lo s_hi un_lo un_hi ut_lo ut_hi
-    F_LM = 6,     // 6  multipliers
-    F_V = 12,     // 3  bounded components of the SQP iterate (s_k, u_n, u_t)
-    F_DU = 15,    // 2  damped QP control step
-    F_RT = 17,    // 6  1 / slack, refreshed whenever the slacks change
-    F_VA = 23,    // 3  affine-predictor bounded components (ds, dun, dut)
-    F_VN = 26,    // 3  corrector bounded components
-    F_DX = 23,    // 4  final QP state step (written after the IPM: aliases F_VA / F_VN)
-    F_HG = 29,    // 6  barrier Hessian (0..2) / gradient (3..5) additions
-    F_COUNT = 35
-};
-// S = 1: the matrix-core factor walk's stage records overlay F_VA .. F_HG (free while the predictor
-// factorises) and mfw_extra<S>() more fields (factor_walk_mfma)
-// (S = 1: two, so eight one-wave workgroups and a packing-sort workgroup still share a CU's LDS; S = 2:
-// three, every horizon up to N = 127)
-template <int S>
-constexpr int mfw_extra() { return S == 1 ? 2 : 4; }
-template <int S>
-constexpr int lds_bytes() { return (F_COUNT * S + mfw_extra<S>()) * BLOCK * 8; }
+// The LDS fields of a lane (LdsField) and the workgroup's LDS size: qsp_layout.h.
+constexpr int BLOCK = WAVE;                // threads per workgroup: one wave (see launch_qp_waves)
+constexpr int lds_bytes(int S) { return lds_doubles(S) * 8; }
 
 template <int S>
 struct Stage {
@@ -219,6 +200,27 @@ struct Ctx {
     int inst;
     GroupScan gs;
 };
+
+// Wave geometry of a thread (qsp_layout.h): its group of L lanes, its place in it, and the instance
+// of the launch's range [0, nI) the group holds (real: there is one).  sqp_loop_kernel's and
+// merit_ls_kernel's; qp_step_kernel writes the same lines out (the call there changes the
+// instructions of one of its instantiations).
+template <int S>
+__device__ __forceinline__ Ctx ctx_of(int lane, int N, int nI) {
+    Ctx c;
+    c.lane = lane;
+    c.N = N;
+    c.L = lanes_per_instance(N, S);
+    const int G = WAVE / c.L;
+    c.grp = c.lane / c.L;
+    c.lig = c.lane - c.grp * c.L;
+    c.base = c.grp * c.L;
+    c.gs.init(c.base, c.L);
+    const int wave = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+    c.inst = wave * G + c.grp;
+    c.real = (c.grp < G) && (c.inst < nI);
+    return c;
+}
 
 template <int S>
 __device__ __forceinline__ int kof(const Ctx& c, int ls) { return c.lig * S + ls; }
@@ -409,20 +411,19 @@ __device__ __forceinline__ void dyn_step(const double a[6], const double B[8], c
 // ~45 VALU instead of the lane walk's ~210 VALU on 1 of 21 lanes.
 // The stage data reaches the blocks through LDS: before the walk every stage lane writes a
 // 27-double record (MfwSlot) over the fields that are free while the predictor factorises (F_VA ..
-// F_HG and mfw_extra<S>() more); the block lanes read their operand elements from it, one step ahead,
+// F_HG and mfw_extra(S) more); the block lanes read their operand elements from it, one step ahead,
 // and write the stage's K and [R~ | r~] back over its first 16 slots, which the stage lane collects
 // after the walk (forming -R~^-1 and kk itself, in parallel).  The records of a wave's G instances do not fit at once: the walk runs in two
 // phases (stages H .. N-1 with the terminal record, then 0 .. H-1).
 // (a record row-major in the order the block lanes read it: [B | b] row by row, so the lanes of two matrix
 // rows read at most six consecutive doubles per operand, which the three instances' records -- 9 apart
 // mod 32 at N = 20 -- keep on disjoint LDS banks)
-enum MfwSlot : int { R_G = 0, R_A = 12, R_GX = 18, R_HX3 = 22, R_HU = 23, R_GU = 25, MFW_REC = 27 };
-enum MfwOut : int { O_K = 0, O_Z = 8, O_COUNT = 16 };   // K (2 x 4), rows 0, 1 of Z = [R~ | r~ | .]
-// the operand constants (A's ones and zeros, the zero column of [B | b | 0], Hx's fixed diagonal), at the
-// end of the region: the lanes whose operand element is one read it there instead of from the record
-enum MfwConst : int { C_ONE = 0, C_ZERO = 1, C_HX = 2, C_COUNT = 5 };
-static_assert((F_COUNT - F_VA + mfw_extra<1>()) * BLOCK >= 33 * MFW_REC + C_COUNT, "S = 1: records of G (N/2 + 1) stages, 12 <= N <= 31");
-static_assert(((F_COUNT - F_VA) * 2 + mfw_extra<2>()) * BLOCK >= 64 * MFW_REC + C_COUNT, "S = 2: records of G (N/2 + 1) stages, N <= 127");
+// (MfwSlot, MfwOut, MfwConst and the region's size: qsp_layout.h)
+static_assert(mfw_region(1) >= 33 * MFW_REC + C_COUNT, "S = 1: records of G (N/2 + 1) stages, 12 <= N <= 31");
+static_assert(mfw_region(2) >= 64 * MFW_REC + C_COUNT, "S = 2: records of G (N/2 + 1) stages, N <= 127");
+// The walk's prefetch reads one record past a phase's last stage: for block 0 in phase 1 that is the
+// record below the region, on the live fields F_T .. F_RT, and must stay inside the allocation.
+static_assert(F_VA * BLOCK >= MFW_REC, "the record below the region lies in the workgroup's LDS");
 
 __device__ __forceinline__ double mfma4(double a, double b, double c) {   // a'b + c per 4x4 block
     return __builtin_amdgcn_mfma_f64_4x4x4f64(a, b, c, 0, 0, 0);
@@ -442,35 +443,13 @@ __device__ __forceinline__ double quad_bcast(double v) {   // DPP quad_perm: one
     return __hiloint2double(hi, lo);
 }
 
-// LDS doubles the stage records may occupy: F_VA .. F_HG of every slot plus the extra fields.
-template <int S>
-constexpr int mfw_region() { return ((F_COUNT - F_VA) * S + mfw_extra<S>()) * BLOCK; }
-// Which horizons factorise on the matrix cores: one instance per 16-lane block (G <= 4: at one
-// stage per lane N >= 12, at two N >= 24), the records of a phase in the region.  One stage per lane
-// takes the walk as its ALT kernel variant; two stages per lane by a uniform switch, since
-// ALT is the factorisation scan there.
-// The instances' record regions start IS doubles apart, IS >= CM records: a stride whose multiples put
-// the instances' reads of one operand (at most six consecutive doubles per half wave) on disjoint LDS banks
-// (32 doubles): 9 ... 11 or 21 ... 23 mod 32 for three instances, 8 or 24 for four, 6 ... 26 for two.
-__host__ __device__ __forceinline__ int mfw_stride(int CM, int G) {
-    const int rs = CM * MFW_REC;
-    for (int is = rs;; ++is) {
-        const int m = is & 31;
-        if (G <= 1 || (G == 2 && m >= 6 && m <= 26) || (G == 3 && ((m >= 9 && m <= 11) || (m >= 21 && m <= 23))) ||
-            (G >= 4 && (m == 8 || m == 24)))
-            return is;
-    }
-}
-__host__ __device__ __forceinline__ bool mfw_fits(int N, int S) {
-    const int L = (N + S) / S, G = 64 / L, H = (N + 1) / 2, CM = N + 1 - H;
-    const int cap = S == 1 ? mfw_region<1>() : mfw_region<2>();
-    return G <= 4 && (G - 1) * mfw_stride(CM, G) + CM * MFW_REC + C_COUNT <= cap && (S == 2 || N <= 31);
-}
+// Which horizons take the walk: mfw_fits (qsp_layout.h).  One stage per lane takes it as its ALT kernel
+// variant; two stages per lane by a uniform switch, since ALT is the factorisation scan there.
 __host__ __device__ __forceinline__ bool mfw_use(const SolveParams& p, int S) { return p.mfw_on[S - 1] != 0; }
 // (host, whenever N or mfma_walk change: the kernels read the choice and the stride instead of searching it)
 void mfw_prepare(SolveParams& p) {
     for (int S = 1; S <= 2; ++S) {
-        const int L = (p.N + S) / S, G = 64 / L, H = (p.N + 1) / 2, CM = p.N + 1 - H;
+        const int G = instances_per_wave(p.N, S), CM = mfw_records(p.N);
         p.mfw_on[S - 1] = p.mfma_walk != 0 && mfw_fits(p.N, S);
         p.mfw_is[S - 1] = G >= 1 && G <= 4 ? mfw_stride(CM, G) : CM * MFW_REC;
     }
@@ -479,8 +458,8 @@ void mfw_prepare(SolveParams& p) {
 template <int S>
 __device__ __forceinline__ void factor_walk_mfma(const Ctx& c, const SolveParams& p, Stage<S>& st, const double (&hx3)[S],
                                                  const double (&hu)[S][2], const double (&gx3)[S], const double (&gu)[S][2]) {
-    const int N = c.N, G = 64 / c.L;
-    const int H = (N + 1) / 2, CM = N + 1 - H;   // phase split; records per instance and phase
+    const int N = c.N, G = WAVE / c.L;
+    const int H = mfw_split(N);                   // phase split (CM = mfw_records(N) records per instance and phase)
     const int IS = p.mfw_is[S - 1];               // doubles from one instance's records to the next's (mfw_prepare)
     double* const reg = st.lds - (threadIdx.x & 63) + F_VA * S * BLOCK;
     // block-lane geometry and the record slot of each operand element (-1: structural constant)
@@ -501,7 +480,7 @@ __device__ __forceinline__ void factor_walk_mfma(const Ctx& c, const SolveParams
     if (r < 2 && r == cc) zo = R_HU + r;
     else if (r < 2 && cc == 2) zo = R_GU + r;
     const int qo = cc == 2 ? R_GX + r : -1;            // q~'s C: gx in column 2 (p lives there only)
-    double* const cst = reg + mfw_region<S>() - C_COUNT;
+    double* const cst = reg + mfw_region(S) - C_COUNT;
     const int ac = r == cc ? C_ONE : C_ZERO, hc = r == cc && r < 3 ? C_HX + r : C_ZERO;
     if (c.lane < C_COUNT)   // the constants (the region's other fields change between walks)
         cst[c.lane] = c.lane == C_ONE ? 1.0 : (c.lane == C_ZERO ? 0.0 : p.tau * p.W[c.lane < C_HX ? 0 : c.lane - C_HX]);
@@ -1586,11 +1565,9 @@ __device__ __forceinline__ void qp_adjoint_store(const Ctx& c, const SolveParams
 // Workspace (SolveArgs::w*): SQP iterate X/U, wrapped x0, stage data in SoA.
 enum LinField : int { L_A = 0, L_B = 6, L_BB = 14, L_G = 18, L_COUNT = 24 };
 
-// Shape of instance i.  Ids from qsp_solve_device are device data that the host cannot
-// validate without a round trip, so they are clamped into the table here.
 __device__ __forceinline__ const ShapeDev& shape_of(const SolveArgs& A, int i) {
     const int id = A.shape_id ? A.shape_id[i] : 0;
-    return A.shapes[id < 0 ? 0 : (id >= A.n_shapes ? A.n_shapes - 1 : id)];
+    return A.shapes[shape_clamp(id, A.n_shapes)];
 }
 
 // nlp_mode 1 workspace (SoA over (instance, stage), like wlin)
@@ -1835,6 +1812,42 @@ __device__ __forceinline__ bool qp_outcome(const SolveArgs& A, const Ctx& c, con
     return failed;
 }
 
+// ---- pieces the SQP kernels (qp_step_kernel, sqp_loop_kernel) share as functions.  The fused kernel's
+// bit identity to the per-iteration launches rests on both computing the same: the wave geometry, the
+// linearisation's stage load and dx0 are still written out in both (as functions they change the
+// instructions the compiler emits for these kernels), and must be edited together.
+// debug (QSP_FLAG_POISON): this thread's LDS column filled with NaN
+template <int S>
+__device__ __forceinline__ void poison_lds(double* col) {
+    for (int f = 0; f < F_COUNT * S + mfw_extra(S); ++f) col[f * BLOCK] = __builtin_nan("");
+}
+
+// the bounded components (s_k, u_n, u_t) of slot ls's stage into LDS (kc, ku: the stage clamped to N, N - 1)
+template <int S>
+__device__ __forceinline__ void load_bounded(const Stage<S>& st, int ls, int kc, int ku, const double* X, const double* U) {
+    st.v(ls, 0) = X[4 * kc + 3];
+    st.v(ls, 1) = U[2 * ku];
+    st.v(ls, 2) = U[2 * ku + 1];
+}
+
+// the full Gauss-Newton step: X += dx, U += du, and the instance's IPM iteration count
+template <int S>
+__device__ __forceinline__ void iterate_update(const SolveArgs& A, const Ctx& c, const Stage<S>& st, int iv, int nit,
+                                               double* X, double* U) {
+    const int N = c.N;
+#pragma unroll
+    for (int ls = 0; ls < S; ++ls) {
+        const int k = kof<S>(c, ls);
+        if (k <= N)
+            for (int q = 0; q < 4; ++q) X[4 * k + q] += st.dxs(ls, q);
+        if (k < N) {
+            U[2 * k] += st.du(ls, 0);
+            U[2 * k + 1] += st.du(ls, 1);
+        }
+        if (k == 0) A.qp_iter[iv] += nit;
+    }
+}
+
 template <int S, bool MERIT = false, bool LIN = false, bool ALT = false>
 __global__ void __launch_bounds__(BLOCK, QSP_MIN_WAVES) qp_step_kernel(SolveArgs A, int it) {
     SEG_T(t_k);
@@ -1843,8 +1856,8 @@ __global__ void __launch_bounds__(BLOCK, QSP_MIN_WAVES) qp_step_kernel(SolveArgs
     Ctx c;
     c.lane = threadIdx.x & 63;
     c.N = p.N;
-    c.L = (p.N + S) / S;                 // ceil((N+1)/S)
-    const int G = 64 / c.L;
+    c.L = lanes_per_instance(p.N, S);
+    const int G = WAVE / c.L;
     c.grp = c.lane / c.L;
     c.lig = c.lane - c.grp * c.L;
     c.base = c.grp * c.L;
@@ -1861,7 +1874,7 @@ __global__ void __launch_bounds__(BLOCK, QSP_MIN_WAVES) qp_step_kernel(SolveArgs
     Stage<S> st;
     st.lds = smem + threadIdx.x;
     if (A.flags & QSP_FLAG_POISON) {
-        for (int f = 0; f < F_COUNT * S + mfw_extra<S>(); ++f) st.lds[f * BLOCK] = __builtin_nan("");
+        for (int f = 0; f < F_COUNT * S + mfw_extra(S); ++f) st.lds[f * BLOCK] = __builtin_nan("");
     }
     double* X = A.wX + (size_t)iv * (N + 1) * 4;
     double* U = A.wU + (size_t)iv * N * 2;
@@ -1930,9 +1943,7 @@ __global__ void __launch_bounds__(BLOCK, QSP_MIN_WAVES) qp_step_kernel(SolveArgs
 #pragma unroll
             for (int q = 0; q < 6; ++q) st.g[ls][q] = in[(L_G + q) * tot];
         }
-        st.v(ls, 0) = X[4 * kc + 3];
-        st.v(ls, 1) = U[2 * ku];
-        st.v(ls, 2) = U[2 * ku + 1];
+        load_bounded<S>(st, ls, kc, ku, X, U);
     }
     if constexpr (MERIT && LIN) {
         // the line search (merit_ls_kernel) evaluates the defect and gradient at the same point
@@ -2020,17 +2031,7 @@ __global__ void __launch_bounds__(BLOCK, QSP_MIN_WAVES) qp_step_kernel(SolveArgs
     qp_adjoint_store<S>(c, p, st, A.PI_out + (size_t)iv * N * 4, c.real && !skip && !failed,
                         (A.flags & QSP_FLAG_SHIFT) != 0);
     if (!c.real || skip || failed) return;
-#pragma unroll
-    for (int ls = 0; ls < S; ++ls) {
-        const int k = kof<S>(c, ls);
-        if (k <= N)
-            for (int q = 0; q < 4; ++q) X[4 * k + q] += st.dxs(ls, q);
-        if (k < N) {
-            U[2 * k] += st.du(ls, 0);
-            U[2 * k + 1] += st.du(ls, 1);
-        }
-        if (k == 0) A.qp_iter[iv] += nit;
-    }
+    iterate_update<S>(A, c, st, iv, nit, X, U);
     SEG_ADD(12, t_k);
 }
 
@@ -2045,33 +2046,18 @@ __global__ void __launch_bounds__(BLOCK, QSP_MIN_WAVES) sqp_loop_kernel(SolveArg
     extern __shared__ double smem[];
     const SolveParams& p = A.p;
     const int N = p.N;
-    if (A.flags & QSP_FLAG_POISON) {
-        for (int f = 0; f < F_COUNT * S + mfw_extra<S>(); ++f) smem[threadIdx.x + f * BLOCK] = __builtin_nan("");
-    }
+    if (A.flags & QSP_FLAG_POISON) poison_lds<S>(smem + threadIdx.x);
     bool stopped = false;   // group-uniform: a failed QP stops the instance's SQP
     for (int it = 0; it < p.sqp_iters; ++it) {
         if (it > 0) __syncthreads();   // the neighbour lanes' X, U stores of the last iteration
         // debug: re-poisoned at every SQP iteration, so a read of a word the current iteration
         // did not write shows up (the last iteration's finite values would hide it)
-        if (it > 0 && (A.flags & QSP_FLAG_POISON)) {
-            for (int f = 0; f < F_COUNT * S + mfw_extra<S>(); ++f) smem[threadIdx.x + f * BLOCK] = __builtin_nan("");
-        }
+        if (it > 0 && (A.flags & QSP_FLAG_POISON)) poison_lds<S>(smem + threadIdx.x);
         // lane geometry and addresses re-derived every iteration from an opaque lane id: hoisted
         // out of the loop they would stay live through the interior point (register budget)
         int lane = threadIdx.x & 63;
         asm volatile("" : "+v"(lane));
-        Ctx c;
-        c.lane = lane;
-        c.N = N;
-        c.L = (N + S) / S;
-        const int G = 64 / c.L;
-        c.grp = c.lane / c.L;
-        c.lig = c.lane - c.grp * c.L;
-        c.base = c.grp * c.L;
-        c.gs.init(c.base, c.L);
-        const int wave = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
-        c.inst = wave * G + c.grp;
-        c.real = (c.grp < G) && (c.inst < A.nI);
+        const Ctx c = ctx_of<S>(lane, N, A.nI);
         const int iv = A.i0 + (c.real ? c.inst : A.nI - 1);
         double* X = A.wX + (size_t)iv * (N + 1) * 4;
         double* U = A.wU + (size_t)iv * N * 2;
@@ -2115,9 +2101,7 @@ __global__ void __launch_bounds__(BLOCK, QSP_MIN_WAVES) sqp_loop_kernel(SolveArg
                 st.g[ls][4] = 0.0;
                 st.g[ls][5] = 0.0;
             }
-            st.v(ls, 0) = X[4 * kc + 3];
-            st.v(ls, 1) = U[2 * ku];
-            st.v(ls, 2) = U[2 * ku + 1];
+            load_bounded<S>(st, ls, kc, ku, X, U);
         }
         double dx0[4];
 #pragma unroll
@@ -2129,19 +2113,7 @@ __global__ void __launch_bounds__(BLOCK, QSP_MIN_WAVES) sqp_loop_kernel(SolveArg
         const bool failed = qp_outcome<S>(A, c, st, iv, it, exit, skip);
         qp_adjoint_store<S>(c, p, st, A.PI_out + (size_t)iv * N * 4, c.real && !skip && !failed,
                             (A.flags & QSP_FLAG_SHIFT) != 0);
-        if (c.real && !skip && !failed) {
-#pragma unroll
-            for (int ls = 0; ls < S; ++ls) {
-                const int k = kof<S>(c, ls);
-                if (k <= N)
-                    for (int q = 0; q < 4; ++q) X[4 * k + q] += st.dxs(ls, q);
-                if (k < N) {
-                    U[2 * k] += st.du(ls, 0);
-                    U[2 * k + 1] += st.du(ls, 1);
-                }
-                if (k == 0) A.qp_iter[iv] += nit;
-            }
-        }
+        if (c.real && !skip && !failed) iterate_update<S>(A, c, st, iv, nit, X, U);
         stopped = stopped || failed;
     }
 }
@@ -2220,18 +2192,7 @@ __global__ void iota_kernel(int B, int32_t* perm) {
 // the last alpha tried is taken); X, U, PI, LAM updated with that alpha.
 __global__ void __launch_bounds__(64) merit_ls_kernel(SolveArgs A) {
     const SolveParams& p = A.p;
-    Ctx c;
-    c.lane = threadIdx.x & 63;
-    c.N = p.N;
-    c.L = p.N + 1;
-    const int G = 64 / c.L;
-    c.grp = c.lane / c.L;
-    c.lig = c.lane - c.grp * c.L;
-    c.base = c.grp * c.L;
-    c.gs.init(c.base, c.L);
-    const int wave = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
-    c.inst = wave * G + c.grp;
-    c.real = (c.grp < G) && (c.inst < A.nI);
+    const Ctx c = ctx_of<1>(threadIdx.x & 63, p.N, A.nI);
     // the QP launch's wave packing (instances ordered by their predicted IPM count) also groups
     // the line searches: a wave backtracks until the last of its instances accepts a step
     const int slot = A.i0 + (c.real ? c.inst : A.nI - 1);
@@ -2457,11 +2418,6 @@ __device__ double reproject_contact(const ShapeDev& sh, double px, double py, do
     return s;
 }
 
-__device__ __forceinline__ const ShapeDev& shape_clamped(const ShapeDev* shapes, int n_shapes, const int32_t* sid, int i) {
-    const int id = sid ? sid[i] : 0;   // clamped like shape_of (the table may have shrunk since the ids were set)
-    return shapes[id < 0 ? 0 : (id >= n_shapes ? n_shapes - 1 : id)];
-}
-
 __global__ void closed_loop_pre_kernel(ClosedLoopArgs a, int t) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.B) return;
@@ -2683,34 +2639,40 @@ static hipError_t lds_attr_once(const void* kernel, int bytes, std::atomic<uint6
     return e;
 }
 
-// LIN: the SQP iteration's linearisation runs inside the QP kernel (nlp_mode 0); without
-// it the kernel reads the stage data the workspace holds (qsp_qp_solve).
-// ALT: the alternative factorisation of the stage count — S = 2: the associative scan
-// (SolveParams::factor_scan); S = 1: the walk on the matrix cores (mfw_use)
-template <int S, bool LIN, bool ALT = false>
-static hipError_t launch_qp_step(const SolveArgs& a, int it, hipStream_t stream) {
-    const int L = (a.p.N + S) / S;
-    const int G = 64 / L;
-    const int waves = (a.nI + G - 1) / G;
-    const int blocks = (waves * 64 + BLOCK - 1) / BLOCK;
-    static std::atomic<uint64_t> attr{0};
-    const hipError_t e = lds_attr_once((const void*)qp_step_kernel<S, false, LIN, ALT>, lds_bytes<S>(), attr);
+// The QP kernels' grid: one workgroup per wave of instances, with the stage count's dynamic LDS
+// (allowed once per kernel and device).  extra: the kernel's arguments after SolveArgs.
+template <auto KERNEL, int S, class... Extra>
+static hipError_t launch_qp_waves(const SolveArgs& a, hipStream_t stream, Extra... extra) {
+    static std::atomic<uint64_t> attr{0};   // one per KERNEL
+    const hipError_t e = lds_attr_once((const void*)KERNEL, lds_bytes(S), attr);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((qp_step_kernel<S, false, LIN, ALT>), dim3(blocks), dim3(BLOCK), lds_bytes<S>(), stream, a, it);
+    hipLaunchKernelGGL(KERNEL, dim3((unsigned)waves_for(a.nI, a.p.N, S)), dim3(BLOCK), lds_bytes(S), stream, a, extra...);
     return hipGetLastError();
 }
 
-template <int S, bool ALT = false>
-static hipError_t launch_sqp_loop(const SolveArgs& a, hipStream_t stream) {
-    const int L = (a.p.N + S) / S;
-    const int G = 64 / L;
-    const int waves = (a.nI + G - 1) / G;
-    const int blocks = (waves * 64 + BLOCK - 1) / BLOCK;
-    static std::atomic<uint64_t> attr{0};
-    const hipError_t e = lds_attr_once((const void*)sqp_loop_kernel<S, ALT>, lds_bytes<S>(), attr);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((sqp_loop_kernel<S, ALT>), dim3(blocks), dim3(BLOCK), lds_bytes<S>(), stream, a);
-    return hipGetLastError();
+// The kernel variant of a handle.  ALT is the alternative factorisation of the stage count: at one
+// stage per lane the walk on the matrix cores (mfw_use), at two the associative scan
+// (SolveParams::factor_scan); two stages per lane take the matrix cores inside the kernel (mfw_use).
+// Every launcher selects through factor_alt / with_variant, and factor_walk_kind reports from it.
+static bool factor_alt(const SolveParams& p, int S) { return S == 1 ? mfw_use(p, 1) : p.factor_scan != 0; }
+
+int factor_walk_kind(const SolveParams& p, int S) {
+    if (S != 1 && S != 2) return QSP_WALK_LANE;
+    if (factor_alt(p, S)) return S == 1 ? QSP_WALK_MFMA : QSP_WALK_SCAN;
+    return mfw_use(p, S) ? QSP_WALK_MFMA : QSP_WALK_LANE;
+}
+
+// f(S, ALT) with the handle's variant as compile-time constants
+template <class F>
+static hipError_t with_variant(const SolveParams& p, int S, F&& f) {
+    using one = std::integral_constant<int, 1>;
+    using two = std::integral_constant<int, 2>;
+    const bool alt = factor_alt(p, S);
+    switch (S) {
+        case 1: return alt ? f(one{}, std::true_type{}) : f(one{}, std::false_type{});
+        case 2: return alt ? f(two{}, std::true_type{}) : f(two{}, std::false_type{});
+        default: return hipErrorInvalidValue;
+    }
 }
 
 // sqp_loop_kernel keeps more state live across its SQP loop than qp_step_kernel and runs at
@@ -2719,26 +2681,18 @@ static hipError_t launch_sqp_loop(const SolveArgs& a, hipStream_t stream) {
 // S = 1, solves/s per-iteration launches -> fused): B = 1 024 58.7k -> 76.5k; 2 048 115k ->
 // 123k; 3 072 (1 024 waves) 173k -> 224k; 4 096 (1 366 waves, two rounds) 227k -> 169k.
 int sqp_fused_auto(int B, int N, int S, int nlp_mode, int cus) {
-    const int G = 64 / lanes_per_instance(N, S);
-    const long waves = ((long)B + G - 1) / G;
+    const long waves = waves_for(B, N, S);
     return (nlp_mode == 0 && (S == 1 || S == 2) && waves <= 4L * cus) ? 1 : 0;
 }
 
+// lin: the SQP iteration's linearisation runs inside the QP kernel (nlp_mode 0); without it the
+// kernel reads the stage data the workspace holds (qsp_qp_solve).
 static hipError_t launch_qp_any(const SolveArgs& a, int S, int it, hipStream_t stream, bool lin) {
-    switch (S) {
-        case 1:
-            if (mfw_use(a.p, 1))
-                return lin ? launch_qp_step<1, true, true>(a, it, stream) : launch_qp_step<1, false, true>(a, it, stream);
-            return lin ? launch_qp_step<1, true>(a, it, stream) : launch_qp_step<1, false>(a, it, stream);
-        case 2:
-            if (a.p.factor_scan)
-                return lin ? launch_qp_step<2, true, true>(a, it, stream) : launch_qp_step<2, false, true>(a, it, stream);
-            return lin ? launch_qp_step<2, true>(a, it, stream) : launch_qp_step<2, false>(a, it, stream);
-        default: return hipErrorInvalidValue;
-    }
+    return with_variant(a.p, S, [&](auto s, auto alt) {
+        return lin ? launch_qp_waves<qp_step_kernel<s(), false, true, alt()>, s()>(a, stream, it)
+                   : launch_qp_waves<qp_step_kernel<s(), false, false, alt()>, s()>(a, stream, it);
+    });
 }
-
-int lanes_per_instance(int N, int S) { return (N + S) / S; }
 
 #ifdef QSP_SEGSTAMP
 // diagnostic build: read (and optionally clear) the segment cycle sums
@@ -2752,29 +2706,12 @@ extern "C" int qsp_debug_segments(unsigned long long* out, int reset) {
 }
 #endif
 
-int factor_walk_kind(const SolveParams& p, int S) {
-    if (S == 2 && p.factor_scan) return QSP_WALK_SCAN;
-    return (S == 1 || S == 2) && mfw_use(p, S) ? QSP_WALK_MFMA : QSP_WALK_LANE;
-}
-
+// nlp_mode 1 (one stage per lane): the QP with the KKT test, then the line search
 static hipError_t launch_sqp_merit(const SolveArgs& a, int it, hipStream_t stream) {
-    const int L = a.p.N + 1;
-    const int G = 64 / L;
-    const int waves = (a.nI + G - 1) / G;
-    const int blocks = (waves * 64 + BLOCK - 1) / BLOCK;
-    static std::atomic<uint64_t> attr{0}, attr_alt{0};
-    if (mfw_use(a.p, 1)) {
-        const hipError_t ea = lds_attr_once((const void*)qp_step_kernel<1, true, true, true>, lds_bytes<1>(), attr_alt);
-        if (ea != hipSuccess) return ea;
-        hipLaunchKernelGGL((qp_step_kernel<1, true, true, true>), dim3(blocks), dim3(BLOCK), lds_bytes<1>(), stream, a, it);
-    } else {
-        const hipError_t ea = lds_attr_once((const void*)qp_step_kernel<1, true, true>, lds_bytes<1>(), attr);
-        if (ea != hipSuccess) return ea;
-        hipLaunchKernelGGL((qp_step_kernel<1, true, true>), dim3(blocks), dim3(BLOCK), lds_bytes<1>(), stream, a, it);
-    }
-    hipError_t e = hipGetLastError();
+    const hipError_t e = factor_alt(a.p, 1) ? launch_qp_waves<qp_step_kernel<1, true, true, true>, 1>(a, stream, it)
+                                            : launch_qp_waves<qp_step_kernel<1, true, true, false>, 1>(a, stream, it);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(merit_ls_kernel, dim3(waves), dim3(64), 0, stream, a);   // one wave per workgroup
+    hipLaunchKernelGGL(merit_ls_kernel, dim3((unsigned)waves_for(a.nI, a.p.N, 1)), dim3(WAVE), 0, stream, a);   // one wave per workgroup
     return hipGetLastError();
 }
 
@@ -2785,8 +2722,7 @@ static hipError_t launch_sqp_merit(const SolveArgs& a, int it, hipStream_t strea
 // 473k -> 509k; B = 65 536 491k -> 512k; N = 50, B = 16 384 (S = 2) 69.7k -> 74.8k; merit
 // SQP (max_iter 30) B = 65 536 619k -> 672k, and at N = 10 1.42M -> 1.65M.
 int sqp_parts_auto(int B, int N, int S, int cus) {
-    const int G = 64 / lanes_per_instance(N, S);
-    const long waves = ((long)B + G - 1) / G;
+    const long waves = waves_for(B, N, S);
     return waves >= 8L * cus ? 2 : 1;   // 2 waves/SIMD x 4 SIMDs per CU: 2 048 slots on a whole MI355X
 }
 
@@ -2808,11 +2744,11 @@ static hipError_t sqp_iteration(const SolveArgs& as, int S, bool sorted, int it,
 }
 
 hipError_t launch_sqp(const SolveArgs& a, int S, hipStream_t stream, hipEvent_t* ev, const SqpStreams* split) {
-    const int G = 64 / lanes_per_instance(a.p.N, S);
+    const int G = instances_per_wave(a.p.N, S);
     // parts of whole waves (the last part takes the remainder); at least one wave each
     int P = split ? split->parts : 1;
     if (P > SQP_MAX_PARTS) P = SQP_MAX_PARTS;
-    const int wtot = (a.B + G - 1) / G;
+    const int wtot = (int)waves_for(a.B, a.p.N, S);
     if (P > wtot) P = wtot;
     for (int q = 1; q < P; ++q)
         if (!split->aux[q - 1] || !split->join[q - 1] || !split->fork) P = 1;
@@ -2845,8 +2781,9 @@ hipError_t launch_sqp(const SolveArgs& a, int S, hipStream_t stream, hipEvent_t*
     if (e == hipSuccess) e = mark();
     if (fused) {
         if (e == hipSuccess)
-            e = S == 1 ? (mfw_use(as.p, 1) ? launch_sqp_loop<1, true>(as, stream) : launch_sqp_loop<1>(as, stream))
-                       : (as.p.factor_scan ? launch_sqp_loop<2, true>(as, stream) : launch_sqp_loop<2>(as, stream));
+            e = with_variant(as.p, S, [&](auto s, auto alt) {
+                return launch_qp_waves<sqp_loop_kernel<s(), alt()>, s()>(as, stream);
+            });
         ne = 2 * K + 1;
         if (e == hipSuccess) e = mark();
     } else if (!two) {

@@ -60,7 +60,7 @@ struct qsp_solver {
     // per-lane controller input buffer u_buff_contr (B x D x 2, column 0 newest); closed-loop state
     int32_t D = 0;
     DevBuf ubc, ubp, cl_x, cl_xsim, cl_amp;
-    DevBuf wX, wU, wx0, wlin, wnlp, wdone, wres, wqp, wperm, wnit, whist;
+    DevBuf wX, wU, wx0, wlin, wnlp, wdone, wres, wqp, wperm, wnit, whist, wadj, wadjv;
     DevBuf scratch[12];
     DevBuf ro[12];                  // staging of the rollout entry points' host arrays
     bool solved = false;            // wU holds a solve's iterate (qsp_cost_landscape with U_tail = NULL)
@@ -224,6 +224,8 @@ static SolveArgs make_args(qsp_solver* s) {
     if (s->poison) a.flags |= QSP_FLAG_POISON;
     a.wnit = s->wnit.as<int32_t>();
     a.whist = s->whist.as<int32_t>();
+    a.wadj = s->wadj.as<double>();
+    a.wadjv = s->wadjv.as<int32_t>();
     a.PI_in = s->PI.as<double>();   // 'init_pi' (solve) / shifted warm start (controller)
     return a;
 }
@@ -428,6 +430,11 @@ int qsp_create(const qsp_options* o, qsp_solver** out) {
         al(s->wnlp, B * (N + 1) * 20 * 8);
         al(s->wqp, B * (N + 1) * 16 * 8);
         al(s->wres, B * 4 * 8);
+    } else {
+        // fixed-K path: the adjoint record of each instance's last successful QP; the dynamics
+        // multipliers are computed from it once per solve (epilogue_kernel)
+        al(s->wadj, B * N * 11 * 8);
+        al(s->wadjv, B * 4);
     }
     if (e == hipSuccess) e = hipMemsetAsync(s->shape_id.p, 0, B * 4, s->stream);
     if (e == hipSuccess) e = hipMemsetAsync(s->warm_valid.p, 0, B, s->stream);
@@ -445,7 +452,7 @@ int qsp_create(const qsp_options* o, qsp_solver** out) {
     s->poison = pz && pz[0] == '1';
     if (s->poison) {
         DevBuf* ws[] = {&s->wX, &s->wU, &s->wx0, &s->wlin, &s->wnlp, &s->wdone, &s->wres, &s->wqp, &s->wperm, &s->wnit,
-                        &s->X, &s->U, &s->PI, &s->Xo, &s->Uo, &s->PIo, &s->u0, &s->cost, &s->yref, &s->yref_e};
+                        &s->wadj, &s->wadjv, &s->X, &s->U, &s->PI, &s->Xo, &s->Uo, &s->PIo, &s->u0, &s->cost, &s->yref, &s->yref_e};
         for (DevBuf* b : ws)
             if (e == hipSuccess && b->p) e = hipMemsetAsync(b->p, 0xff, b->n, s->stream);
         // ... except what a caller legitimately relies on being zero: the initial guess and warm state
@@ -473,7 +480,7 @@ int qsp_destroy(qsp_solver* s) {
                       &s->Uo, &s->PIo, &s->u0, &s->status, &s->sqp_iter, &s->qp_iter, &s->qp_capped, &s->qp_stalled, &s->cost,
                       &s->warm_valid,
                       &s->traj, &s->index_time, &s->wX, &s->wU, &s->wx0, &s->wlin, &s->wnlp, &s->wdone, &s->wres, &s->wqp, &s->wperm, &s->wnit,
-                      &s->whist};
+                      &s->whist, &s->wadj, &s->wadjv};
     for (DevBuf* b : bufs) b->release();
     for (auto& b : s->scratch) b.release();
     for (auto& b : s->ro) b.release();

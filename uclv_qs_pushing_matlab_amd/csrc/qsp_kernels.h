@@ -56,6 +56,9 @@ struct SolveArgs {
     int32_t* wnit;             // B               IPM iterations of each instance's last four QPs (8 bits each, last lowest)
     int32_t* whist;            // 4 x 1024        per parity of the SQP iteration: histogram of the wave-packing
                                //                 keys (accumulated by the QP kernel) and running scatter offsets
+    double* wadj;              // B x N x 11      nlp_mode 0: adjoint record of the instance's last successful QP
+                               //                 (ADJ_REC doubles per stage 1..N, instance-major; qsp_solver.hip)
+    int32_t* wadjv;            // B               nlp_mode 0: the record is valid (a QP of this solve wrote it)
     // QP-level interface only (qsp_qp_solve): when qp_dx != nullptr the QP kernel
     // reports the QP solution instead of updating the iterate
     double* qp_dx;             // B x (N+1) x 4

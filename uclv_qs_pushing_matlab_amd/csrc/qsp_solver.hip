@@ -1560,6 +1560,65 @@ __device__ __forceinline__ void qp_adjoint_store(const Ctx& c, const SolveParams
     }
 }
 
+// The fixed-K SQP (nlp_mode 0) reads no multipliers between its iterations, so its QP kernels
+// do not walk the adjoint recursion: every stage lane stores what the recursion takes from its
+// own stage (the adjoint record, ADJ_REC doubles per stage 1..N, instance-major), every
+// successful QP overwrites the record, and the epilogue walks the recursion once per solve from
+// the record of the instance's last successful QP (adjoint_from_record).  The terms are those of
+// adjoint_step in its order, so PI keeps its bits.
+//   stage 1 <= k < N, at (k - 1) ADJ_REC: c_i = tau W_i dx_k,i + g_k,i (4), a_k (6), (lam_hi - lam_lo)_s
+//   stage N, at (N - 1) ADJ_REC:          pi_{N-1} = We dx_N + g_N (4)
+constexpr int ADJ_REC = 11;
+
+template <int S>
+__device__ __forceinline__ void qp_adjoint_record(const Ctx& c, const SolveParams& p, const Stage<S>& st, double* rec) {
+#pragma unroll
+    for (int ls = 0; ls < S; ++ls) {
+        const int k = kof<S>(c, ls);
+        if (k < 1 || k > c.N) continue;
+        double* r = rec + (size_t)(k - 1) * ADJ_REC;
+        if (k == c.N) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) r[i] = qfma(p.We[i], st.dxs(ls, i), st.g[ls][i]);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) r[i] = qfma(p.tau * p.W[i], st.dxs(ls, i), st.g[ls][i]);
+#pragma unroll
+            for (int i = 0; i < 6; ++i) r[4 + i] = st.a[ls][i];
+            r[10] = st.lm(ls, 1) - st.lm(ls, 0);
+        }
+    }
+}
+
+// PI (N x 4) of one instance from its adjoint record: qp_adjoint_store's recursion and its
+// shifted / unshifted rows (shift: row k - 1 for k >= 1, the last row duplicated).
+__device__ __forceinline__ void adjoint_from_record(int N, const double* rec, double* PI, bool shift) {
+    double pi[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) pi[i] = rec[(size_t)(N - 1) * ADJ_REC + i];
+    for (int k = N - 1; k >= 0; --k) {
+        if (!shift || k >= 1) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) PI[(size_t)(shift ? k - 1 : k) * 4 + i] = pi[i];
+        }
+        if (shift && k == N - 1) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) PI[(size_t)k * 4 + i] = pi[i];
+        }
+        if (k >= 1) {
+            const double* r = rec + (size_t)(k - 1) * ADJ_REC;
+            double np[4];
+            np[0] = r[0] + pi[0];
+            np[1] = r[1] + pi[1];
+            np[2] = r[2] + (qfma(r[6], pi[1], r[4] * pi[0]) + pi[2]);
+            np[3] = r[3] + qfma(r[9], pi[3], qfma(r[8], pi[2], qfma(r[7], pi[1], r[5] * pi[0])));
+            np[3] += r[10];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) pi[i] = np[i];
+        }
+    }
+}
+
 // ------------------------------------------------------------------ kernels
 // One solve = prologue, K x (linearize, qp), epilogue; all on one stream.
 // Workspace (SolveArgs::w*): SQP iterate X/U, wrapped x0, stage data in SoA.
@@ -1617,6 +1676,7 @@ __global__ void prologue_kernel(SolveArgs A) {
     if (A.qp_stalled) A.qp_stalled[i] = 0;
     if (A.wdone) A.wdone[i] = 0;
     if (A.wnit) A.wnit[i] = 0;
+    if (A.wadjv) A.wadjv[i] = 0;   // no successful QP yet: PI_out keeps what it holds (the warm start's)
     if (!(A.flags & QSP_FLAG_CONTROLLER)) {
         for (int q = 0; q < (N + 1) * 4; ++q) X[q] = A.X_in[(size_t)i * (N + 1) * 4 + q];
         for (int q = 0; q < N * 2; ++q) U[q] = A.U_in[(size_t)i * N * 2 + q];
@@ -2026,11 +2086,13 @@ __global__ void __launch_bounds__(BLOCK, QSP_MIN_WAVES) qp_step_kernel(SolveArgs
         }
         return;
     }
-    // multipliers of every successful QP (the output holds the last one, also for an
-    // instance that stops early)
-    qp_adjoint_store<S>(c, p, st, A.PI_out + (size_t)iv * N * 4, c.real && !skip && !failed,
-                        (A.flags & QSP_FLAG_SHIFT) != 0);
     if (!c.real || skip || failed) return;
+    SEG_NEXT(12, t_k);
+    // adjoint record of every successful QP (the epilogue forms the multipliers of the last
+    // one, also for an instance that stops early: a failed QP leaves the record as it was)
+    qp_adjoint_record<S>(c, p, st, A.wadj + (size_t)iv * N * ADJ_REC);
+    if (c.lig == 0) A.wadjv[iv] = 1;
+    SEG_NEXT(16, t_k);
     iterate_update<S>(A, c, st, iv, nit, X, U);
     SEG_ADD(12, t_k);
 }
@@ -2111,9 +2173,11 @@ __global__ void __launch_bounds__(BLOCK, QSP_MIN_WAVES) sqp_loop_kernel(SolveArg
         const int nit = qp_ipm<S, ALT>(c, p, st, dx0, exit, skip);
         qp_rollout<S>(c, st, dx0);
         const bool failed = qp_outcome<S>(A, c, st, iv, it, exit, skip);
-        qp_adjoint_store<S>(c, p, st, A.PI_out + (size_t)iv * N * 4, c.real && !skip && !failed,
-                            (A.flags & QSP_FLAG_SHIFT) != 0);
-        if (c.real && !skip && !failed) iterate_update<S>(A, c, st, iv, nit, X, U);
+        if (c.real && !skip && !failed) {
+            qp_adjoint_record<S>(c, p, st, A.wadj + (size_t)iv * N * ADJ_REC);
+            if (c.lig == 0) A.wadjv[iv] = 1;
+            iterate_update<S>(A, c, st, iv, nit, X, U);
+        }
         stopped = stopped || failed;
     }
 }
@@ -2368,6 +2432,11 @@ __global__ void epilogue_kernel(SolveArgs A) {
             const int src = (k + sh < N) ? k + sh : N - 1;
             for (int q = 0; q < 4; ++q) Po[4 * k + q] = A.wnlp[(W_PI + q) * tot + (size_t)i * (N + 1) + src];
         }
+    }
+    if (p.nlp_mode == 0 && A.wadjv && A.wadjv[i] != 0) {
+        // dynamics multipliers of the last successful QP, once per solve; an instance without
+        // one (stage-0 bound, a failure at the first QP) keeps what PI_out held
+        adjoint_from_record(N, A.wadj + (size_t)i * N * ADJ_REC, A.PI_out + (size_t)i * N * 4, sh != 0);
     }
     if (A.warm_valid && (A.flags & QSP_FLAG_CONTROLLER)) A.warm_valid[i] = 1;
 }
@@ -2744,6 +2813,7 @@ static hipError_t sqp_iteration(const SolveArgs& as, int S, bool sorted, int it,
 }
 
 hipError_t launch_sqp(const SolveArgs& a, int S, hipStream_t stream, hipEvent_t* ev, const SqpStreams* split) {
+    if (a.p.nlp_mode == 0 && (!a.wadj || !a.wadjv)) return hipErrorInvalidValue;   // the QP kernels' adjoint record
     const int G = instances_per_wave(a.p.N, S);
     // parts of whole waves (the last part takes the remainder); at least one wave each
     int P = split ? split->parts : 1;

@@ -39,9 +39,10 @@ extern "C" {
 #define QSP_NY_E 4
 #define QSP_NH 3          /* h = [s; u_n; u_t]      (NMPC_controller.m:237) */
 #define QSP_MAX_CTRL 64   /* spline control points per shape */
-#define QSP_ABI_VERSION 5 /* 2: struct_size fields, qp_mu_max, qsp_get_qp_stalled, QP-failure exits;
+#define QSP_ABI_VERSION 6 /* 2: struct_size fields, qp_mu_max, qsp_get_qp_stalled, QP-failure exits;
                              3: qsp_options.factor_scan; 4: qsp_get_factor_walk;
-                             5: qsp_rollout_cost, qsp_rollout_cost_device, qsp_cost_landscape */
+                             5: qsp_rollout_cost, qsp_rollout_cost_device, qsp_cost_landscape;
+                             6: qsp_eval_modes, qsp_get_modes, qsp_open_loop, qsp_open_loop_device */
 
 #define QSP_OK 0
 #define QSP_ERR_ARG (-1)
@@ -403,6 +404,84 @@ typedef struct {
 } qsp_landscape_io;
 int qsp_cost_landscape_device(qsp_solver* s, const qsp_rollout_opts* opts, const qsp_landscape_io* io,
                               void* hip_stream);
+
+/* ------------------------------------- contact modes and the open-loop simulation */
+/* The contact mode of (x, u): which branch of f the input selects, in helper.convert_str2num's coding,
+ * taken from the OCP model's indicators (PusherSliderModel.m:587-589)
+ *     ST  gamma_r <= u_t / u_n <= gamma_l      SL  u_t / u_n > gamma_l      SR  u_t / u_n < gamma_r
+ * with the motion cone's edges gamma_l, gamma_r at the contact point (:547-548).  The mode and the edges
+ * are bit for bit the ones qsp_eval_dynamics blends with (J[3][5] = 1 exactly when sliding, J[3][4] =
+ * -gamma_l on SL and -gamma_r on SR).  They depend on s and u only.
+ * QSP_MODE_NONE: no indicator is set -- u_t / u_n is NaN (u_n = u_t = 0, as a delayed plant's input buffer
+ * holds at its start) or s / an input is not finite; f is 0 then.  The one deviation from the reference:
+ * the numeric eval_model_variable_shape's if-chain (PusherSliderModel.m:353-362) ends in an else and would
+ * label that case "SR".  Its "NC" cannot occur for a contact point given by s.  u_n = 0 with u_t != 0 is
+ * an infinite ratio: SL for u_t > 0, SR for u_t < 0, as in the reference. */
+#define QSP_MODE_NONE 0
+#define QSP_MODE_ST 1
+#define QSP_MODE_SL 2
+#define QSP_MODE_SR 3
+/* building block, beside qsp_eval_dynamics: cone (optional) = gamma_l, gamma_r, u_t / u_n per point */
+int qsp_eval_modes(qsp_solver* s, int32_t n, const int32_t* shape_id, const double* x /* n x 4 */,
+                   const double* u /* n x 2 */, int32_t* mode /* n */, double* cone /* n x 3 or NULL */);
+/* Stage k's mode at (x_k, u_k), k = 0..N-1, of exactly what qsp_get_x and qsp_get_u return (after
+ * qsp_controller_solve: the shifted warm start), evaluated on the device-resident trajectories with the
+ * handle's shape ids.  mode: B x N; cone: B x N x 3 or NULL. */
+int qsp_get_modes(qsp_solver* s, int32_t* mode, double* cone);
+
+/* helper.open_loop_matlab (helper.m:132-193), batched over B lanes x M input candidates per lane.
+ * Per step i = 0..n_steps-1, in this order:
+ *   1. x += noise[i]                      (sim_noise, :155; the logged state includes it)
+ *   2. clip (:162-166)                    v = v_alpha / |angle_rate(mod(s, b))|, u_t <- (v < u_t ? v : u_t):
+ *                                         MATLAB's min, a NaN never wins, a negative u_t passes through
+ *   3. applied input (:169-177)           u itself without a plant delay; else the delay buffer's last
+ *                                         column, after which the clipped u is pushed (the buffer starts at
+ *                                         zero and is local to the call)
+ *   4. mode of (x, u_applied)
+ *   5. x <- x + Ts f(x, u_applied)        the OCP's f (evalModelVariableShape), qsp_closed_loop's plant step */
+typedef struct {
+    int32_t struct_size;      /* sizeof(qsp_open_loop_opts) (qsp_default_open_loop_opts sets it; checked) */
+    int32_t n_steps;          /* T = length(0:sample_time:time_sim) */
+    int32_t M;                /* input candidates per lane */
+    int32_t u_steps;          /* 1: U is B x M x 2, held constant (repmat, :144); n_steps: U is B x M x T x 2 */
+    int32_t clip;             /* 1 (default): step 2 */
+    int32_t store_tile;       /* how the trajectories are written.  0 (default): the library's choice, the faster
+                                 path measured for the call's M (steps of 4 below 64 candidates per lane, else 1);
+                                 1: every thread stores its own rows; 4 or 8: that many steps are collected
+                                 per thread in LDS and written out with consecutive threads on consecutive
+                                 addresses.  Results are identical; a measurement knob */
+    double Ts;                /* sample_time; 0: the handle's */
+    double v_alpha;           /* 1.0 = 0.005 * 200 (:162) */
+    double plant_delay;       /* plant.time_delay [s]: ceil(delay / Ts) buffer columns, as qsp_closed_loop_opts' */
+} qsp_open_loop_opts;
+void qsp_default_open_loop_opts(qsp_open_loop_opts* opts);   /* n_steps 1, M 1, u_steps 1, clip on, v_alpha 1 */
+/* x0: B x 4; U: B x M x u_steps x 2; noise: n_steps x B x 4 or NULL (shared by a lane's candidates);
+ * shapes per lane as qsp_set_shape_ids.  Outputs, each optional except x_end:
+ *   X          B x M x (n_steps + 1) x 4   the states, row n_steps the final one
+ *   U_out      B x M x n_steps x 2         the commanded input after the clip (the reference's returned u)
+ *   S_p        B x M x n_steps x 2         C(mod(s, b)), the contact point in the slider frame (:187)
+ *   mode       B x M x n_steps             QSP_MODE_* of the applied input
+ *   mode_steps B x M x 4                   steps spent in modes 0..3 (a sweep can skip the trajectories)
+ *   x_end      B x M x 4 */
+int qsp_open_loop(qsp_solver* s, const qsp_open_loop_opts* opts, const double* x0, const double* U,
+                  const double* noise, double* X, double* U_out, double* S_p, int32_t* mode, int32_t* mode_steps,
+                  double* x_end);
+/* The same on caller-owned device memory, asynchronous on hip_stream (NULL: the handle's).  X, U_out and
+ * S_p must be 16-byte aligned (device allocations are).  With the clip and a plant delay the delay buffer
+ * is the handle's: one such call at a time per handle. */
+typedef struct {
+    const double* x0;        /* B x 4 */
+    const double* U;         /* B x M x u_steps x 2 */
+    const double* noise;     /* n_steps x B x 4 or NULL */
+    const int32_t* shape_id; /* B or NULL: the handle's */
+    double* X;               /* NULL or as above */
+    double* U_out;
+    double* S_p;
+    int32_t* mode;
+    int32_t* mode_steps;
+    double* x_end;           /* B x M x 4 */
+} qsp_open_loop_io;
+int qsp_open_loop_device(qsp_solver* s, const qsp_open_loop_opts* opts, const qsp_open_loop_io* io, void* hip_stream);
 
 #ifdef __cplusplus
 }

@@ -12,7 +12,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 # QSP_LIB_PATH: developer override (A/B runs of differently compiled libraries)
 LIB_PATH = os.environ.get("QSP_LIB_PATH") or os.path.join(_PKG, "libqsp_nmpc.so")
 MAX_CTRL = 64
-ABI_VERSION = 5   # include/qsp_nmpc.h QSP_ABI_VERSION
+ABI_VERSION = 6   # include/qsp_nmpc.h QSP_ABI_VERSION
 
 _lib = None
 
@@ -73,6 +73,17 @@ class LandscapeIO(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in
                 ("x0", "U_tail", "un_grid", "ut_grid", "yref", "yref_e", "shape_id", "cost", "u_min", "cost_min",
                  "idx_min")] + [("n_un", C.c_int32), ("n_ut", C.c_int32)]
+
+
+class OpenLoopOpts(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("n_steps", C.c_int32), ("M", C.c_int32), ("u_steps", C.c_int32),
+                ("clip", C.c_int32), ("store_tile", C.c_int32), ("Ts", C.c_double), ("v_alpha", C.c_double),
+                ("plant_delay", C.c_double)]
+
+
+class OpenLoopIO(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in
+                ("x0", "U", "noise", "shape_id", "X", "U_out", "S_p", "mode", "mode_steps", "x_end")]
 
 
 _P = C.c_void_p
@@ -146,9 +157,14 @@ _SIGS = {
     "qsp_rollout_cost_device": [_P, C.POINTER(RolloutOpts), _I, C.POINTER(RolloutIO), _P],
     "qsp_cost_landscape": [_P, C.POINTER(RolloutOpts), _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P],
     "qsp_cost_landscape_device": [_P, C.POINTER(RolloutOpts), C.POINTER(LandscapeIO), _P],
+    "qsp_eval_modes": [_P, _I, _P, _P, _P, _P, _P],
+    "qsp_get_modes": [_P, _P, _P],
+    "qsp_default_open_loop_opts": [C.POINTER(OpenLoopOpts)],
+    "qsp_open_loop": [_P, C.POINTER(OpenLoopOpts), _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "qsp_open_loop_device": [_P, C.POINTER(OpenLoopOpts), C.POINTER(OpenLoopIO), _P],
     "qsp_last_error": [],
 }
-_VOID = {"qsp_default_options", "qsp_default_rollout_opts"}
+_VOID = {"qsp_default_options", "qsp_default_rollout_opts", "qsp_default_open_loop_opts"}
 EXPORTED = tuple(_SIGS)
 
 

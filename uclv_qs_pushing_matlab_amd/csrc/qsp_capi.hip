@@ -63,6 +63,8 @@ struct qsp_solver {
     DevBuf wX, wU, wx0, wlin, wnlp, wdone, wres, wqp, wperm, wnit, whist, wadj, wadjv;
     DevBuf scratch[12];
     DevBuf ro[12];                  // staging of the rollout entry points' host arrays
+    DevBuf ol[10];                  // staging of qsp_eval_modes / qsp_get_modes / qsp_open_loop's host arrays
+    DevBuf ol_ring;                 // qsp_open_loop's plant delay buffer (clipped u_t of the last D steps)
     bool solved = false;            // wU holds a solve's iterate (qsp_cost_landscape with U_tail = NULL)
     int32_t T = 0;
     bool have_traj = false;
@@ -484,6 +486,8 @@ int qsp_destroy(qsp_solver* s) {
     for (DevBuf* b : bufs) b->release();
     for (auto& b : s->scratch) b.release();
     for (auto& b : s->ro) b.release();
+    for (auto& b : s->ol) b.release();
+    s->ol_ring.release();
     for (hipEvent_t e : s->kev) (void)hipEventDestroy(e);
     if (s->ev0) (void)hipEventDestroy(s->ev0);
     if (s->ev1) (void)hipEventDestroy(s->ev1);
@@ -1462,6 +1466,152 @@ int qsp_cost_landscape_device(qsp_solver* s, const qsp_rollout_opts* opts, const
     a.cost_min = io->cost_min;
     a.idx_min = io->idx_min;
     HIPCHK(launch_cost_landscape(a, stream ? (hipStream_t)stream : s->stream));
+    return QSP_OK;
+}
+
+// ------------------------------------- contact modes and the open-loop simulation
+int qsp_eval_modes(qsp_solver* s, int32_t n, const int32_t* sid, const double* x, const double* u, int32_t* mode,
+                   double* cone) {
+    if (!s || !sid || !x || !u || !mode || n < 1) return fail(QSP_ERR_ARG, "qsp_eval_modes: bad argument");
+    int r = check_ids(s, n, sid);
+    if (r) return r;
+    HIPCHK(hipSetDevice(s->o.device));
+    auto& b = s->ol;
+    if ((r = stage_in(s, b[0], sid, n)) || (r = stage_in(s, b[1], x, (size_t)4 * n)) || (r = stage_in(s, b[2], u, (size_t)2 * n)))
+        return r;
+    HIPCHK(b[3].ensure((size_t)n * 4));
+    if (cone) HIPCHK(b[4].ensure((size_t)n * 3 * 8));
+    HIPCHK(launch_modes(s->shapes.as<ShapeDev>(), s->n_shapes, b[0].as<int32_t>(), n, 1, 1, b[1].as<double>(),
+                        b[2].as<double>(), b[3].as<int32_t>(), cone ? b[4].as<double>() : nullptr, s->stream));
+    if ((r = stage_out(s, mode, b[3], (size_t)n))) return r;
+    if (cone && (r = stage_out(s, cone, b[4], (size_t)3 * n))) return r;
+    HIPCHK(hipStreamSynchronize(s->stream));
+    return QSP_OK;
+}
+
+int qsp_get_modes(qsp_solver* s, int32_t* mode, double* cone) {
+    if (!s || !mode) return fail(QSP_ERR_ARG, "qsp_get_modes: null argument");
+    if (s->n_shapes < 1) return fail(QSP_ERR_STATE, "qsp_get_modes: no shapes set");
+    const size_t n = (size_t)s->o.batch * s->o.N;
+    HIPCHK(hipSetDevice(s->o.device));
+    auto& b = s->ol;
+    HIPCHK(b[3].ensure(n * 4));
+    if (cone) HIPCHK(b[4].ensure(n * 3 * 8));
+    // the buffers qsp_get_x / qsp_get_u copy out
+    const DevBuf& X = s->last_controller ? s->X : s->Xo;
+    const DevBuf& U = s->last_controller ? s->U : s->Uo;
+    HIPCHK(launch_modes(s->shapes.as<ShapeDev>(), s->n_shapes, s->shape_id.as<int32_t>(), (long long)n, s->o.N, s->o.N + 1,
+                        X.as<double>(), U.as<double>(), b[3].as<int32_t>(), cone ? b[4].as<double>() : nullptr, s->stream));
+    int r;
+    if ((r = stage_out(s, mode, b[3], n))) return r;
+    if (cone && (r = stage_out(s, cone, b[4], 3 * n))) return r;
+    HIPCHK(hipStreamSynchronize(s->stream));
+    return QSP_OK;
+}
+
+void qsp_default_open_loop_opts(qsp_open_loop_opts* o) {
+    std::memset(o, 0, sizeof(*o));
+    o->struct_size = (int32_t)sizeof(qsp_open_loop_opts);
+    o->n_steps = 1;
+    o->M = 1;
+    o->u_steps = 1;
+    o->clip = 1;
+    o->v_alpha = 1.0;   // 0.005 * 200 (helper.m:162)
+}
+
+// the options' checks and the handle's shapes into a kernel argument block; the delay ring when one is needed
+static int open_loop_args(qsp_solver* s, const qsp_open_loop_opts* o, const char* who, OpenLoopArgs& a) {
+    const std::string w(who);
+    if (!s || !o) return fail(QSP_ERR_ARG, w + ": null argument");
+    if (o->struct_size != (int32_t)sizeof(qsp_open_loop_opts))
+        return fail(QSP_ERR_ARG, w + ": qsp_open_loop_opts.struct_size != sizeof(qsp_open_loop_opts) (stale layout?)");
+    if (o->n_steps < 1) return fail(QSP_ERR_ARG, w + ": n_steps must be >= 1");
+    if (o->M < 1) return fail(QSP_ERR_ARG, w + ": M must be >= 1");
+    if (o->u_steps != 1 && o->u_steps != o->n_steps) return fail(QSP_ERR_ARG, w + ": u_steps must be 1 or n_steps");
+    if (o->clip != 0 && o->clip != 1) return fail(QSP_ERR_ARG, w + ": clip must be 0 or 1");
+    if (o->store_tile != 0 && o->store_tile != 1 && o->store_tile != 4 && o->store_tile != 8)
+        return fail(QSP_ERR_ARG, w + ": store_tile must be 0, 1, 4 or 8");
+    const double Ts = o->Ts == 0.0 ? s->o.Ts : o->Ts;
+    if (!(Ts > 0.0)) return fail(QSP_ERR_ARG, w + ": Ts must be > 0 (0: the handle's)");
+    if (!(o->plant_delay >= 0.0) || std::ceil(o->plant_delay / Ts) > 4096.0)
+        return fail(QSP_ERR_ARG, w + ": plant_delay must be in [0, 4096 Ts]");
+    if (s->n_shapes < 1) return fail(QSP_ERR_STATE, w + ": no shapes set");
+    if ((long long)s->o.batch * o->M > (1ll << 31) - 1) return fail(QSP_ERR_ARG, w + ": more than 2^31 - 1 rows (B M)");
+    std::memset(&a, 0, sizeof a);
+    a.B = s->o.batch;
+    a.M = o->M;
+    a.T = o->n_steps;
+    a.u_steps = o->u_steps;
+    a.D = (int)std::ceil(o->plant_delay / Ts);   // delay_buff_plant (helper.m:147)
+    a.clip = o->clip;
+    a.tile = o->store_tile;
+    a.Ts = Ts;
+    a.v_alpha = o->v_alpha;
+    a.shapes = s->shapes.as<ShapeDev>();
+    a.n_shapes = s->n_shapes;
+    a.shape_id = s->shape_id.as<int32_t>();
+    HIPCHK(hipSetDevice(s->o.device));
+    if (a.clip && a.D > 0) {
+        HIPCHK(s->ol_ring.ensure((size_t)a.D * a.B * a.M * 8));
+        a.ring = s->ol_ring.as<double>();
+    }
+    return QSP_OK;
+}
+
+int qsp_open_loop(qsp_solver* s, const qsp_open_loop_opts* opts, const double* x0, const double* U, const double* noise,
+                  double* X, double* U_out, double* S_p, int32_t* mode, int32_t* mode_steps, double* x_end) {
+    OpenLoopArgs a;
+    int r = open_loop_args(s, opts, "qsp_open_loop", a);
+    if (r) return r;
+    if (!x0 || !U || !x_end) return fail(QSP_ERR_ARG, "qsp_open_loop: null argument");
+    const size_t B = a.B, T = a.T, BM = B * (size_t)a.M;
+    auto& b = s->ol;
+    if ((r = stage_in(s, b[0], x0, B * 4)) || (r = stage_in(s, b[1], U, BM * a.u_steps * 2))) return r;
+    if (noise && (r = stage_in(s, b[2], noise, T * B * 4))) return r;
+    if (X) HIPCHK(b[5].ensure(BM * (T + 1) * 4 * 8));
+    if (U_out) HIPCHK(b[6].ensure(BM * T * 2 * 8));
+    if (S_p) HIPCHK(b[7].ensure(BM * T * 2 * 8));
+    if (mode) HIPCHK(b[3].ensure(BM * T * 4));
+    if (mode_steps) HIPCHK(b[8].ensure(BM * 4 * 4));
+    HIPCHK(b[9].ensure(BM * 4 * 8));
+    a.x0 = b[0].as<double>();
+    a.U = b[1].as<double>();
+    a.noise = noise ? b[2].as<double>() : nullptr;
+    a.X = X ? b[5].as<double>() : nullptr;
+    a.U_out = U_out ? b[6].as<double>() : nullptr;
+    a.S_p = S_p ? b[7].as<double>() : nullptr;
+    a.mode = mode ? b[3].as<int32_t>() : nullptr;
+    a.mode_steps = mode_steps ? b[8].as<int32_t>() : nullptr;
+    a.x_end = b[9].as<double>();
+    HIPCHK(launch_open_loop(a, s->stream));
+    if (X && (r = stage_out(s, X, b[5], BM * (T + 1) * 4))) return r;
+    if (U_out && (r = stage_out(s, U_out, b[6], BM * T * 2))) return r;
+    if (S_p && (r = stage_out(s, S_p, b[7], BM * T * 2))) return r;
+    if (mode && (r = stage_out(s, mode, b[3], BM * T))) return r;
+    if (mode_steps && (r = stage_out(s, mode_steps, b[8], BM * 4))) return r;
+    if ((r = stage_out(s, x_end, b[9], BM * 4))) return r;
+    HIPCHK(hipStreamSynchronize(s->stream));
+    return QSP_OK;
+}
+
+int qsp_open_loop_device(qsp_solver* s, const qsp_open_loop_opts* opts, const qsp_open_loop_io* io, void* stream) {
+    OpenLoopArgs a;
+    int r = open_loop_args(s, opts, "qsp_open_loop_device", a);
+    if (r) return r;
+    if (!io || !io->x0 || !io->U || !io->x_end) return fail(QSP_ERR_ARG, "qsp_open_loop_device: missing device pointer");
+    if ((((uintptr_t)io->X | (uintptr_t)io->U_out | (uintptr_t)io->S_p) & 15) != 0)
+        return fail(QSP_ERR_ARG, "qsp_open_loop_device: X, U_out and S_p must be 16-byte aligned");
+    a.x0 = io->x0;
+    a.U = io->U;
+    a.noise = io->noise;
+    if (io->shape_id) a.shape_id = io->shape_id;
+    a.X = io->X;
+    a.U_out = io->U_out;
+    a.S_p = io->S_p;
+    a.mode = io->mode;
+    a.mode_steps = io->mode_steps;
+    a.x_end = io->x_end;
+    HIPCHK(launch_open_loop(a, stream ? (hipStream_t)stream : s->stream));
     return QSP_OK;
 }
 

@@ -173,4 +173,33 @@ struct RolloutArgs {
 hipError_t launch_rollout_cost(const RolloutArgs& a, hipStream_t stream);
 hipError_t launch_cost_landscape(const RolloutArgs& a, hipStream_t stream);
 
+// Contact modes and the open-loop simulation (qsp_openloop.hip; helper.m:132-193).
+// modes_kernel: entry e of n belongs to group e / per (its shape: sid[group], clamped) and reads
+// x[(group * xper + e % per) * 4 ..], u[e * 2 ..] -- per = xper = 1 for a list of points, per = N and
+// xper = N + 1 for a handle's trajectories.
+hipError_t launch_modes(const ShapeDev* shapes, int n_shapes, const int32_t* sid, long long n, int per, int xper,
+                        const double* x, const double* u, int32_t* mode, double* cone, hipStream_t stream);
+struct OpenLoopArgs {
+    int32_t B, M, T;
+    int32_t u_steps;           // 1 or T
+    int32_t D;                 // plant delay columns
+    int32_t clip;
+    int32_t tile;              // 0: the launcher's choice; 1: direct stores; 4 / 8: steps per thread collected in LDS
+    double Ts, v_alpha;
+    const ShapeDev* shapes;
+    int32_t n_shapes;
+    const int32_t* shape_id;   // B (nullptr: shape 0); clamped into [0, n_shapes)
+    const double* x0;          // B x 4
+    const double* U;           // B x M x u_steps x 2
+    const double* noise;       // T x B x 4 or nullptr
+    double* ring;              // D x (B M): the clipped u_t of the last D steps (clip && D > 0; else unused)
+    double* X;                 // B x M x (T+1) x 4 or nullptr
+    double* U_out;             // B x M x T x 2 or nullptr
+    double* S_p;               // B x M x T x 2 or nullptr
+    int32_t* mode;             // B x M x T or nullptr
+    int32_t* mode_steps;       // B x M x 4 or nullptr
+    double* x_end;             // B x M x 4
+};
+hipError_t launch_open_loop(const OpenLoopArgs& a, hipStream_t stream);
+
 }  // namespace qsp

@@ -238,6 +238,60 @@ __device__ __forceinline__ void dynamics(const ShapeDev& sh, double th, double s
     o.Jut[3] = isl + isr;
 }
 
+// ---------------------------------------------------------------- contact mode
+// The motion cone at the contact point s and the branch of f that the input (un, ut) selects:
+// dynamics<> restated up to and including its three indicators, the same operations in the same
+// order (smod_model, spline_eval, frame, px / py, nl / dl, nr / dr, rho = ut / un), so gl, gr and the
+// mode are bit for bit what dynamics<> blends with (Jun[3] = -gl on SL, -gr on SR; Jut[3] = 1 when
+// sliding).  dynamics<> itself does not call this: the QP kernels' code stays as it is.
+// Mode codes are helper.convert_str2num's ("ST" 1, "SL" 2, "SR" 3), taken from the OCP model's
+// indicators (PusherSliderModel.m:587-589).  QSP_MODE_NONE: no indicator is set -- rho is NaN
+// (un = ut = 0, as the plant's delay buffer holds at its start) or s / an input is not finite; f is 0
+// then.  Deviation, documented: the numeric eval_model_variable_shape's if-chain
+// (PusherSliderModel.m:353-362) ends in an else and would label that case "SR"; its "NC" cannot occur
+// for a contact point given by s.  The cone does not depend on theta.
+#define QSP_MODE_NONE 0
+#define QSP_MODE_ST 1
+#define QSP_MODE_SL 2
+#define QSP_MODE_SR 3
+
+struct MotionCone {
+    double gl, gr, rho;   // gamma_l, gamma_r (:547-548), u_fract (:551)
+    int mode;             // QSP_MODE_*
+};
+
+__device__ __forceinline__ MotionCone motion_cone(const ShapeDev& sh, double s, double un, double ut) {
+    const double sig = smod_model(s, sh.b);
+    SplineEval e;
+    spline_eval(sh, sig, e);
+    const double l2 = qfma(e.D[0], e.D[0], e.D[1] * e.D[1]);
+    const double l = sqrt(l2);
+    const double il = 1.0 / l;
+    const double tx = e.D[0] * il, ty = e.D[1] * il;
+    const double nx = ty, ny = -tx;
+    const double Px = e.C[0], Py = e.C[1];
+    const double px = qfma(nx, Px, ny * Py);
+    const double py = qfma(tx, Px, ty * Py);
+
+    const double c2 = sh.c * sh.c, mu = sh.mu;
+    const double pxpy = px * py, px2 = px * px;
+    const double q11 = qfma(py, py, c2);
+    const double nl = qfma(mu, px2, qfma(mu, c2, -pxpy));
+    const double dl = qfma(-mu, pxpy, q11);
+    const double nr = qfma(-mu, px2, qfma(-mu, c2, -pxpy));
+    const double dr = qfma(mu, pxpy, q11);
+    MotionCone o;
+    o.gl = nl / dl;
+    o.gr = nr / dr;
+    o.rho = ut / un;
+    // every comparison with NaN is false
+    o.mode = ((o.rho >= o.gr) && (o.rho <= o.gl)) ? QSP_MODE_ST
+           : (o.rho > o.gl)                       ? QSP_MODE_SL
+           : (o.rho < o.gr)                       ? QSP_MODE_SR
+                                                  : QSP_MODE_NONE;
+    return o;
+}
+
 // ---------------------------------------------------------------- RK4 + VDE
 // x+ = phi(x,u) over h with one RK4 step (acados ERK default: 4 stages, 1 step);
 // sensitivities w.r.t. (theta0, s0, u_n, u_t).  Columns x0, y0 of dphi/dx are

@@ -14,6 +14,11 @@ of the solver's trajectory held, with its grid minimiser.  The figures (helper.m
 and closed_loop_matlab's debug_cost argument stays ignored: call debug_cost_function after a
 controller.solve.  Two deliberate deviations (include/qsp_nmpc.h): the model is the OCP's f instead of the
 fixed-shape plant.eval_model, and x0 is rolled out as given.
+
+helper.open_loop_matlab (helper.m:132-193) runs on the device as well (OcpSolver.open_loop), and the contact
+modes that the reference plots from mode_vect (convert_str2num, my_plot) come from the device too: mode_trace
+labels a closed loop's trajectories.  Coding: "ST" 1, "SL" 2, "SR" 3; 0 / "" where u_t / u_n is NaN (both
+inputs zero, as a delayed plant's buffer holds at its start), which the reference's if-chain would call "SR".
 """
 import numpy as np
 
@@ -107,3 +112,79 @@ def closed_loop_matlab(plant, controller, x0, time_sim, print_=False, sim_noise=
     x_sim = np.concatenate([np.zeros((B, T + 1, 4)), r["Xsim"]], 1)
     return (X[:, :, 0], x_sim, X[:, :, 1], X[:, :, 2], S_p[..., 0], S_p[..., 1], U[:, :, 0], U[:, :, 1],
             time_sim_vec, mode_vect, found_sol)
+
+
+MODE_NUM = {"ST": 1, "SL": 2, "SR": 3, "": 0}      # helper.m:17-23; "" = no indicator set (QSP_MODE_NONE)
+MODE_STR = np.array(["", "ST", "SL", "SR"])
+
+
+def convert_str2num(mode_vect_str):
+    """mode_vect_num = convert_str2num(mode_vect_str) (helper.m:17-23) on arrays of "ST"/"SL"/"SR" (and ""
+    for the library's mode 0): an int32 array of the same shape."""
+    a = np.asarray(mode_vect_str)
+    out = np.zeros(a.shape, np.int32)
+    for k, v in MODE_NUM.items():
+        out[a == k] = v
+    if not np.all(np.isin(a, list(MODE_NUM))):
+        raise ValueError("convert_str2num: modes must be 'ST', 'SL', 'SR' or ''")
+    return out
+
+
+def convert_num2str(mode_vect_num):
+    """The inverse: QSP_MODE_* numbers -> "ST"/"SL"/"SR" ("" for 0)."""
+    return MODE_STR[np.asarray(mode_vect_num, np.int64)]
+
+
+def applied_inputs(U, plant_delay_cols=0):
+    """What a plant with a delay buffer of D columns applies at step i of the commanded inputs U (..., T, 2):
+    zeros for i < D, then U[i - D] (u_buff_plant starts at zero: helper.m:148,174-176 and :211-212,289-296)."""
+    U = np.asarray(U, np.float64)
+    D = int(plant_delay_cols)
+    if D == 0:
+        return U.copy()
+    T = U.shape[-2]
+    out = np.zeros_like(U)
+    out[..., D:, :] = U[..., :max(T - D, 0), :]
+    return out
+
+
+def mode_trace(solver, X, U, plant_delay_cols=0, shape_id=None):
+    """Contact modes along a simulated trajectory, e.g. a closed loop's X_traj (B, T [+ 1], 4) and U_traj
+    (B, T, 2): the mode of (X[:, i], applied input at step i), the applied input being U shifted by the
+    plant's delay with zeros (applied_inputs).  shape_id (B,) or scalar; None: the solver's per-lane ids
+    (its batch must then be B).  -> (B, T) int32."""
+    U = np.asarray(U, np.float64)
+    B, T = U.shape[:2]
+    X = np.asarray(X, np.float64)[:, :T]
+    ua = applied_inputs(U, plant_delay_cols)
+    if shape_id is None:
+        if solver.B != B:
+            raise ValueError(f"mode_trace: {B} lanes on a solver of batch {solver.B}: pass shape_id")
+        shape_id = solver.shape_ids
+    sid = np.repeat(np.broadcast_to(np.asarray(shape_id, np.int32), (B,)), T)
+    return solver.eval_modes(X.reshape(-1, 4), ua.reshape(-1, 2), shape_id=sid).reshape(B, T)
+
+
+def open_loop_matlab(plant, x0, u_n, u_t, time_sim, sample_time, sim_noise=False, seed=0, solver=None):
+    """[x_s, y_s, theta_s, S_p_x, S_p_y, u_n, u_t, time_sim_vec] = open_loop_matlab(plant, x0, u_n, u_t, time_sim,
+    sample_time, sim_noise) (helper.m:132-193), batched: x0 (B, 4) or (4,); u_n, u_t scalars or (B,).  Every
+    returned trajectory is (B, T) with T = length(0:sample_time:time_sim); u_t is the commanded input after the
+    clip; S_p_y = x(4, :) as helper.m:190 returns it (the contact abscissa s, not the spline's y).  Noise is
+    drawn on the host as closed_loop_matlab's (seeded).  solver: an OcpSolver whose batch and shapes to use
+    (default: the plant's own one-lane evaluator, for B = 1)."""
+    time_sim_vec = np.arange(0.0, time_sim + 1e-9, sample_time)            # :136
+    T = len(time_sim_vec)
+    sv = plant._ev if solver is None else solver
+    B = sv.B
+    x0 = np.broadcast_to(np.asarray(x0, np.float64).reshape(-1, 4), (B, 4))
+    U = np.stack([np.broadcast_to(np.asarray(u_n, np.float64), (B,)),
+                  np.broadcast_to(np.asarray(u_t, np.float64), (B,))], 1)[:, None]     # (B, 1, 2): repmat, :144
+    noise = None
+    if sim_noise:                                                           # :154-156
+        rng = np.random.default_rng(seed)
+        noise = rng.standard_normal((T, B, 4)) * np.array([1e-5, 1e-5, 1e-3, 1e-4])
+    r = sv.open_loop(x0, U, T, noise=noise, plant_delay=plant.time_delay, clip=True, v_alpha=0.005 * 200,
+                     Ts=sample_time, want=("X", "U_out", "S_p"))
+    X = r["X"][:, 0, :T]
+    return (X[:, :, 0], X[:, :, 1], X[:, :, 2], r["S_p"][:, 0, :, 0], X[:, :, 3], r["U_out"][:, 0, :, 0],
+            r["U_out"][:, 0, :, 1], time_sim_vec)

@@ -73,6 +73,19 @@ class PusherSliderModel:
         f, _ = self._ev.eval_dynamics(x.reshape(-1, 4), u.reshape(-1, 2))
         return f.reshape(x.shape)
 
+    def eval_model_variable_shape(self, x, u):
+        """[x_dot, mode] = eval_model_variable_shape(x, u) (PusherSliderModel.m:264-382), batched over leading
+        dimensions: x_dot as evalModelVariableShape, mode "ST" / "SL" / "SR" per point from the same
+        indicators (:587-589).  Where no indicator is set -- u_t / u_n is NaN, i.e. u_n = u_t = 0, or s / an
+        input is not finite -- x_dot is 0 and mode is "" (the reference's if-chain, :353-362, ends in an else
+        and would say "SR" there; its "NC" cannot occur for a contact point given by s)."""
+        from .helper import convert_num2str
+        x = np.asarray(x, np.float64)
+        u = np.asarray(u, np.float64)
+        f, _ = self._ev.eval_dynamics(x.reshape(-1, 4), u.reshape(-1, 2))
+        mode = self._ev.eval_modes(x.reshape(-1, 4), u.reshape(-1, 2))
+        return f.reshape(x.shape), convert_num2str(mode).reshape(x.shape[:-1])
+
     def jacobian(self, x, u):
         """d f / d(x, u) (4 x 6 per point) — what CasADi's VDE would differentiate."""
         return self._ev.eval_dynamics(np.reshape(x, (-1, 4)), np.reshape(u, (-1, 2)))[1]

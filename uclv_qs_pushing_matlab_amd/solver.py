@@ -73,6 +73,7 @@ class OcpSolver:
         self._dirty = set(["x0", "yref", "init"])
         self._refs_staged = False   # the device references are a controller step's, newer than set('cost_y_ref*')
         self.n_shapes = 0
+        self.shape_ids = np.zeros(Bn, np.int32)   # host copy of the per-lane shape ids (helper.mode_trace)
         # timings=True: per-kernel HIP events around every solve, for get('time_lin'/'time_qp_sol')
         self._timings = bool(timings)
         self._last_times = None
@@ -117,6 +118,7 @@ class OcpSolver:
     def set_shape_ids(self, shape_id):
         sid = i32(np.broadcast_to(np.asarray(shape_id, np.int32), (self.B,)))
         check(self._L.qsp_set_shape_ids(self._h, ptr(sid)), "qsp_set_shape_ids")
+        self.shape_ids = sid.copy()
 
     # ----------------------------------------------------------------- set
     def _lanes(self, v, width):
@@ -226,6 +228,9 @@ class OcpSolver:
                   "qp_stalled": self._L.qsp_get_qp_stalled}[field]
             check(fn(self._h, ptr(out)), f"get('{field}')")
             return out
+        if field == "modes":       # contact mode of stage k at (x_k, u_k) of get('x') / get('u'), k = 0..N-1
+            out = self.get_modes()
+            return out if stage is None else out[:, stage]
         if field == "residuals":   # acados res_stat/eq/ineq/comp of the last KKT test (nlp_mode 1)
             out = np.zeros((B, 4))
             check(self._L.qsp_get_residuals(self._h, ptr(out)), "get('residuals')")
@@ -326,6 +331,76 @@ class OcpSolver:
         o = self._rollout_opts(integrator, cost_scale)
         check(self._L.qsp_cost_landscape_device(self._h, C.byref(o), C.byref(io),
                                                 C.c_void_p(stream) if stream else None), "qsp_cost_landscape_device")
+
+    # ------------------------------- contact modes / open-loop simulation
+    MODES = {0: "", 1: "ST", 2: "SL", 3: "SR"}   # QSP_MODE_*: helper.convert_str2num's coding, 0 = no indicator set
+    OPEN_LOOP_OUTPUTS = ("X", "U_out", "S_p", "mode", "mode_steps", "x_end")
+
+    def eval_modes(self, x, u, shape_id=None, want_cone=False):
+        """Contact mode of every (x, u) (QSP_MODE_*: 1 sticking, 2 sliding left, 3 sliding right, 0 when
+        u_t / u_n is NaN), the branch of f that qsp_eval_dynamics blends.  want_cone: also (n, 3) =
+        gamma_l, gamma_r, u_t / u_n."""
+        x = f64(x).reshape(-1, 4)
+        u = f64(u).reshape(-1, 2)
+        n = len(x)
+        mode = np.zeros(n, np.int32)
+        cone = np.zeros((n, 3)) if want_cone else None
+        check(self._L.qsp_eval_modes(self._h, n, ptr(self._sid(shape_id, n)), ptr(x), ptr(u), ptr(mode), ptr(cone)),
+              "qsp_eval_modes")
+        return (mode, cone) if want_cone else mode
+
+    def get_modes(self, want_cone=False):
+        """Stage k's mode at (x_k, u_k) of what get('x') / get('u') return: (B, N)[, cone (B, N, 3)]."""
+        mode = np.zeros((self.B, self.N), np.int32)
+        cone = np.zeros((self.B, self.N, 3)) if want_cone else None
+        check(self._L.qsp_get_modes(self._h, ptr(mode), ptr(cone)), "qsp_get_modes")
+        return (mode, cone) if want_cone else mode
+
+    def _open_loop_opts(self, n_steps, M, u_steps, plant_delay, clip, v_alpha, Ts, store_tile):
+        o = _lib.OpenLoopOpts()
+        self._L.qsp_default_open_loop_opts(C.byref(o))
+        o.n_steps, o.M, o.u_steps = int(n_steps), int(M), int(u_steps)
+        o.clip, o.v_alpha, o.plant_delay = 1 if clip else 0, float(v_alpha), float(plant_delay)
+        o.Ts, o.store_tile = 0.0 if Ts is None else float(Ts), int(store_tile)
+        return o
+
+    def open_loop(self, x0, U, n_steps, noise=None, plant_delay=0.0, clip=True, v_alpha=1.0,
+                  want=("X", "U_out", "S_p", "mode", "mode_steps"), Ts=None, store_tile=0):
+        """helper.open_loop_matlab (helper.m:132-193) for M input candidates per lane.  x0 (B, 4) or (4,);
+        U (B, M, 2): held constant, or (B, M, n_steps, 2): replayed; noise (n_steps, B, 4) or None, shared by a
+        lane's candidates; plant_delay [s]; clip: u_t <- min(v_alpha / |angle rate|, u_t) (:162-166).
+        Returns a dict with x_end (B, M, 4) and the outputs named in `want`: X (B, M, n_steps + 1, 4), U_out
+        (B, M, n_steps, 2) the commanded input after the clip, S_p (B, M, n_steps, 2), mode (B, M, n_steps),
+        mode_steps (B, M, 4) steps spent in modes 0..3.  Ts None: the handle's; store_tile: include/qsp_nmpc.h."""
+        T = int(n_steps)
+        x0 = f64(self._lanes(x0, 4))
+        U = f64(U)
+        if U.ndim == 3 and U.shape[0] == self.B and U.shape[1] >= 1 and U.shape[2] == 2:
+            u_steps = 1
+        elif U.ndim == 4 and U.shape[0] == self.B and U.shape[1] >= 1 and U.shape[2:] == (T, 2):
+            u_steps = T
+        else:
+            raise ValueError(f"U must be (B={self.B}, M >= 1, 2) or (B={self.B}, M >= 1, n_steps={T}, 2), got {U.shape}")
+        unknown = set(want) - set(self.OPEN_LOOP_OUTPUTS)
+        if unknown:
+            raise KeyError(f"OcpSolver.open_loop: unknown outputs {sorted(unknown)}")
+        M = U.shape[1]
+        nz = None if noise is None else f64(noise, (T, self.B, 4))
+        o = self._open_loop_opts(T, M, u_steps, plant_delay, clip, v_alpha, Ts, store_tile)
+        shapes = dict(X=((self.B, M, T + 1, 4), np.float64), U_out=((self.B, M, T, 2), np.float64),
+                      S_p=((self.B, M, T, 2), np.float64), mode=((self.B, M, T), np.int32),
+                      mode_steps=((self.B, M, 4), np.int32), x_end=((self.B, M, 4), np.float64))
+        out = {k: np.zeros(*shapes[k]) for k in self.OPEN_LOOP_OUTPUTS if k in want or k == "x_end"}
+        check(self._L.qsp_open_loop(self._h, C.byref(o), ptr(x0), ptr(U), ptr(nz),
+                                    *[ptr(out.get(k)) for k in self.OPEN_LOOP_OUTPUTS]), "qsp_open_loop")
+        return out
+
+    def open_loop_device(self, io, n_steps, M, u_steps=1, plant_delay=0.0, clip=True, v_alpha=1.0, Ts=None,
+                         store_tile=0, stream=None):
+        """open_loop on caller-owned device memory (io: _lib.OpenLoopIO of device pointers), asynchronous."""
+        o = self._open_loop_opts(n_steps, M, u_steps, plant_delay, clip, v_alpha, Ts, store_tile)
+        check(self._L.qsp_open_loop_device(self._h, C.byref(o), C.byref(io), C.c_void_p(stream) if stream else None),
+              "qsp_open_loop_device")
 
     # --------------------------------------------------- controller level
     def set_reference_trajectory(self, traj):

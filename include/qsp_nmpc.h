@@ -39,10 +39,12 @@ extern "C" {
 #define QSP_NY_E 4
 #define QSP_NH 3          /* h = [s; u_n; u_t]      (NMPC_controller.m:237) */
 #define QSP_MAX_CTRL 64   /* spline control points per shape */
-#define QSP_ABI_VERSION 6 /* 2: struct_size fields, qp_mu_max, qsp_get_qp_stalled, QP-failure exits;
+#define QSP_ABI_VERSION 7 /* 2: struct_size fields, qp_mu_max, qsp_get_qp_stalled, QP-failure exits;
                              3: qsp_options.factor_scan; 4: qsp_get_factor_walk;
                              5: qsp_rollout_cost, qsp_rollout_cost_device, qsp_cost_landscape;
-                             6: qsp_eval_modes, qsp_get_modes, qsp_open_loop, qsp_open_loop_device */
+                             6: qsp_eval_modes, qsp_get_modes, qsp_open_loop, qsp_open_loop_device;
+                             7: qsp_set_plant_shapes, qsp_set_plant_shape_ids, qsp_set_plant_params,
+                                qsp_clear_plant, qsp_get_plant, qsp_closed_loop_metrics */
 
 #define QSP_OK 0
 #define QSP_ERR_ARG (-1)
@@ -270,6 +272,65 @@ typedef struct {
 int qsp_closed_loop_ex(qsp_solver* s, const qsp_closed_loop_opts* opts, const double* x0, const int32_t* index0,
                        int32_t n_steps, const double* noise, double* X_traj, double* X_sim, double* U_traj,
                        int32_t* status_traj);
+/* A plant model of its own.  closed_loop_matlab(plant, controller, ...) simulates with the plant's model
+ * and solves with the controller's (helper.m:195-322).  After qsp_create the plant is the controller's
+ * model; the entries below install another one on the handle.  Lane i's plant is a shape -- the plant
+ * table's entry at the lane's plant id, or without a plant table the controller's shape of the lane --
+ * with its two physical constants mu_sp and c_ellipse replaced by the lane's overrides where given.
+ * With a plant installed these read it:
+ *   the plant's Euler step            plant.evalModelVariableShape, helper.m:292-307
+ *   the delay prediction              controller.delay_buffer_sim(plant, x), helper.m:244,
+ *                                     NMPC_controller.m:112-120
+ *   the disturbance re-projection     plant.SP, plant.slider_params.xwidth, helper.m:221-236 (the
+ *                                     plant's contour, xwidth and b)
+ *   the mode counts of qsp_closed_loop_metrics
+ * The prediction runs on the plant's model, not the controller's: the reference passes `plant` into
+ * delay_buffer_sim, and this is the literal reading of it.  qsp_delay_buffer_sim follows the installed
+ * plant too, so it stays bit-identical to the closed loop's own prediction.
+ * Everything else keeps the controller's model: NMPC_controller.solve (its warm-start rollout and clip,
+ * the OCP, v_bound), qsp_get_modes, the rollout and landscape entries, qsp_open_loop.
+ * With nothing installed every result is bit-identical to a library without these entries. */
+/* the plant's shape table: validated and converted as qsp_set_shapes; the plant ids return to 0 */
+int qsp_set_plant_shapes(qsp_solver* s, const qsp_shape* shapes, int32_t n_shapes);      /* helper.m:294-307 */
+/* ids into the plant table (default 0 for every lane); QSP_ERR_STATE without a plant table */
+int qsp_set_plant_shape_ids(qsp_solver* s, const int32_t* shape_id /* B */);            /* helper.m:294-307 */
+/* per-lane mu_sp and c_ellipse of the plant (PusherSliderModel.m:53-55, :547-548), the Monte-Carlo path:
+ * one double per lane instead of one shape per lane.  Each finite and > 0 (else QSP_ERR_ARG, and what was
+ * installed stays); NULL leaves that constant to the lane's plant shape (both NULL: no overrides).  Works
+ * with or without a plant table. */
+int qsp_set_plant_params(qsp_solver* s, const double* mu_sp /* B or NULL */,
+                         const double* c_ellipse /* B or NULL */);                       /* helper.m:294-307 */
+/* back to "the plant is the controller's model" (table, ids and overrides dropped) */
+int qsp_clear_plant(qsp_solver* s);
+/* what is installed: has_shapes = entries of the plant table (0: none); has_params = 1 (mu_sp) | 2
+ * (c_ellipse).  Either pointer may be NULL. */
+int qsp_get_plant(qsp_solver* s, int32_t* has_shapes, int32_t* has_params);
+
+/* Per-lane metrics of a closed loop without its trajectories: exactly qsp_closed_loop_ex's loop (same
+ * arguments, same state carried), but nothing of size B x n_steps is allocated or copied; only
+ * metrics (B x QSP_CL_NMETRICS), x_end (B x 4, the state after the last plant step, X_traj's last row;
+ * or NULL) and status_last (B, the last solve's status; or NULL) come back.
+ * e_i = the logged plant state of step i = 1..n_steps (X_traj's row i - 1: after disturbance and noise)
+ * minus the lane's reference-table row at the 1-based column index0 + i - 1, clamped at the table's
+ * end as get_y_ref clamps (NMPC_controller.m:307-313); the table as installed, without the delay prefix.
+ * Sums run in step order with plain products and sums (e_x * e_x + e_y * e_y, then acc + that); counts
+ * are exact doubles.  The modes are those of the applied input (after the plant's delay buffer) at the
+ * logged state under the plant's model (QSP_MODE_*; mode 0 is counted nowhere).
+ * QSP_ERR_STATE without a reference table or shapes. */
+#define QSP_CL_NMETRICS 10
+#define QSP_CLM_SUM_EXY2 0    /* sum_i (e_x^2 + e_y^2)                                              */
+#define QSP_CLM_MAX_EXY2 1    /* max_i (e_x^2 + e_y^2); a NaN step does not enter                   */
+#define QSP_CLM_SUM_ETH2 2    /* sum_i e_theta^2                                                    */
+#define QSP_CLM_END_EXY2 3    /* e_x^2 + e_y^2 of the final state against column index0 + n_steps   */
+#define QSP_CLM_SUM_U2 4      /* sum_i (u_n^2 + u_t^2) of the commanded input                       */
+#define QSP_CLM_N_FAILED 5    /* steps with status != 0 (found_sol false, helper.m:253-260)         */
+#define QSP_CLM_N_ST 6        /* steps whose applied input is sticking ...                          */
+#define QSP_CLM_N_SL 7        /* ... sliding left ...                                               */
+#define QSP_CLM_N_SR 8        /* ... sliding right                                                  */
+#define QSP_CLM_N_S_OUT 9     /* steps with the logged s not inside the handle's [lh[0], uh[0]]     */
+int qsp_closed_loop_metrics(qsp_solver* s, const qsp_closed_loop_opts* opts, const double* x0, const int32_t* index0,
+                            int32_t n_steps, const double* noise, double* metrics /* B x QSP_CL_NMETRICS */,
+                            double* x_end /* B x 4 or NULL */, int32_t* status_last /* B or NULL */);
 /* set_delay_comp (NMPC_controller.m:106-110): delay_buff_comp = ceil(delay / Ts) columns; the
  * reference table is read as set_reference_trajectory prepends it (:425-431) and the per-lane input
  * buffer u_buff_contr is zeroed (the only call that zeroes it).  get: the column count. */

@@ -12,7 +12,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 # QSP_LIB_PATH: developer override (A/B runs of differently compiled libraries)
 LIB_PATH = os.environ.get("QSP_LIB_PATH") or os.path.join(_PKG, "libqsp_nmpc.so")
 MAX_CTRL = 64
-ABI_VERSION = 6   # include/qsp_nmpc.h QSP_ABI_VERSION
+ABI_VERSION = 7   # include/qsp_nmpc.h QSP_ABI_VERSION
 
 _lib = None
 
@@ -136,6 +136,12 @@ _SIGS = {
     "qsp_controller_reset": [_P],
     "qsp_closed_loop": [_P, _P, _P, _I, _P, _P, _P, _P],
     "qsp_closed_loop_ex": [_P, C.POINTER(ClosedLoopOpts), _P, _P, _I, _P, _P, _P, _P, _P],
+    "qsp_closed_loop_metrics": [_P, C.POINTER(ClosedLoopOpts), _P, _P, _I, _P, _P, _P, _P],
+    "qsp_set_plant_shapes": [_P, C.POINTER(Shape), _I],
+    "qsp_set_plant_shape_ids": [_P, _P],
+    "qsp_set_plant_params": [_P, _P, _P],
+    "qsp_clear_plant": [_P],
+    "qsp_get_plant": [_P, C.POINTER(_I), C.POINTER(_I)],
     "qsp_set_delay_comp": [_P, _D],
     "qsp_get_delay_comp": [_P, C.POINTER(_I)],
     "qsp_delay_buffer_sim": [_P, _P, _P],

@@ -92,7 +92,9 @@ class NMPCController:
         self.delay_buff_comp = self.ocp_solver.delay_cols()
 
     def delay_buffer_sim(self, plant, x):                                  # :112-120
-        """x predicted delay_buff_comp steps ahead with the buffered inputs (oldest first)."""
+        """x predicted delay_buff_comp steps ahead with the buffered inputs (oldest first), on the model the
+        handle simulates with: the plant installed by OcpSolver.set_plant (as helper.closed_loop_matlab installs
+        a foreign `plant` for its call), else the controller's own.  `plant` is kept for the signature."""
         return self.ocp_solver.delay_buffer_sim(np.broadcast_to(np.asarray(x, np.float64).reshape(-1, 4),
                                                                 (self.batch, 4)))
 

@@ -60,6 +60,11 @@ struct qsp_solver {
     // per-lane controller input buffer u_buff_contr (B x D x 2, column 0 newest); closed-loop state
     int32_t D = 0;
     DevBuf ubc, ubp, cl_x, cl_xsim, cl_amp;
+    // the plant's own model (qsp_set_plant_*): shape table, ids, per-lane mu_sp / c_ellipse; the closed
+    // loop's metric accumulators (qsp_closed_loop_metrics)
+    int n_pshapes = 0;
+    bool has_pids = false, has_pmu = false, has_pc = false;
+    DevBuf pshapes, pshape_id, pmu, pc, cl_metrics;
     DevBuf wX, wU, wx0, wlin, wnlp, wdone, wres, wqp, wperm, wnit, whist, wadj, wadjv;
     DevBuf scratch[12];
     DevBuf ro[12];                  // staging of the rollout entry points' host arrays
@@ -478,6 +483,7 @@ int qsp_destroy(qsp_solver* s) {
     if (!s) return QSP_OK;
     (void)hipSetDevice(s->o.device);
     DevBuf* bufs[] = {&s->ubc, &s->ubp, &s->cl_x, &s->cl_xsim, &s->cl_amp,
+                      &s->pshapes, &s->pshape_id, &s->pmu, &s->pc, &s->cl_metrics,
                       &s->shapes, &s->shape_id, &s->x0, &s->yref, &s->yref_e, &s->X, &s->U, &s->PI, &s->Xo,
                       &s->Uo, &s->PIo, &s->u0, &s->status, &s->sqp_iter, &s->qp_iter, &s->qp_capped, &s->qp_stalled, &s->cost,
                       &s->warm_valid,
@@ -574,17 +580,19 @@ int qsp_shape_from_ply(const char* path, int32_t flip, double mu_sg, double mu_s
     return QSP_OK;
 }
 
-int qsp_set_shapes(qsp_solver* s, const qsp_shape* shapes, int32_t n) {
-    if (!s || !shapes || n < 1) return fail(QSP_ERR_ARG, "qsp_set_shapes: bad argument");
+// qsp_shape table -> device ShapeDev table in the handle's `table` (qsp_set_shapes, qsp_set_plant_shapes)
+static int upload_shapes(qsp_solver* s, const char* who, const qsp_shape* shapes, int32_t n, DevBuf qsp_solver::*table) {
+    const std::string w(who);
+    if (!s || !shapes || n < 1) return fail(QSP_ERR_ARG, w + ": bad argument");
     std::vector<ShapeDev> h((size_t)n);
     for (int q = 0; q < n; ++q) {
         const qsp_shape& in = shapes[q];
         if (in.struct_size != (int32_t)sizeof(qsp_shape))
-            return fail(QSP_ERR_ARG, "qsp_set_shapes: qsp_shape.struct_size != sizeof(qsp_shape) (stale layout?)");
+            return fail(QSP_ERR_ARG, w + ": qsp_shape.struct_size != sizeof(qsp_shape) (stale layout?)");
         ShapeDev& d = h[q];
         std::memset(&d, 0, sizeof d);
         const int nc = in.n_ctrl;
-        if (nc < 5 || nc > QSP_MAX_CTRL) return fail(QSP_ERR_ARG, "qsp_set_shapes: n_ctrl out of range");
+        if (nc < 5 || nc > QSP_MAX_CTRL) return fail(QSP_ERR_ARG, w + ": n_ctrl out of range");
         d.n = nc;
         d.b = in.b;
         d.c = in.c_ellipse;
@@ -607,9 +615,16 @@ int qsp_set_shapes(qsp_solver* s, const qsp_shape* shapes, int32_t n) {
         }
     }
     HIPCHK(hipSetDevice(s->o.device));
-    HIPCHK(s->shapes.ensure(sizeof(ShapeDev) * n));
-    HIPCHK(hipMemcpyAsync(s->shapes.p, h.data(), sizeof(ShapeDev) * n, hipMemcpyHostToDevice, s->stream));
+    DevBuf& dst = s->*table;
+    HIPCHK(dst.ensure(sizeof(ShapeDev) * n));
+    HIPCHK(hipMemcpyAsync(dst.p, h.data(), sizeof(ShapeDev) * n, hipMemcpyHostToDevice, s->stream));
     HIPCHK(hipStreamSynchronize(s->stream));
+    return QSP_OK;
+}
+
+int qsp_set_shapes(qsp_solver* s, const qsp_shape* shapes, int32_t n) {
+    const int r = upload_shapes(s, "qsp_set_shapes", shapes, n, &qsp_solver::shapes);
+    if (r) return r;
     s->n_shapes = n;
     return QSP_OK;
 }
@@ -620,6 +635,65 @@ int qsp_set_shape_ids(qsp_solver* s, const int32_t* ids) {
         if (ids[i] < 0 || ids[i] >= s->n_shapes) return fail(QSP_ERR_ARG, "qsp_set_shape_ids: id out of range");
     HIPCHK(hipSetDevice(s->o.device));
     HIPCHK(hipMemcpy(s->shape_id.p, ids, (size_t)s->o.batch * 4, hipMemcpyHostToDevice));
+    return QSP_OK;
+}
+
+// ------------------------------------------------- the plant's own model
+int qsp_set_plant_shapes(qsp_solver* s, const qsp_shape* shapes, int32_t n) {
+    const int r = upload_shapes(s, "qsp_set_plant_shapes", shapes, n, &qsp_solver::pshapes);
+    if (r) return r;
+    s->n_pshapes = n;
+    s->has_pids = false;   // every lane back to plant shape 0
+    return QSP_OK;
+}
+
+int qsp_set_plant_shape_ids(qsp_solver* s, const int32_t* ids) {
+    if (!s || !ids) return fail(QSP_ERR_ARG, "qsp_set_plant_shape_ids: null argument");
+    if (s->n_pshapes < 1) return fail(QSP_ERR_STATE, "qsp_set_plant_shape_ids: no plant shapes set");
+    const size_t B = s->o.batch;
+    for (size_t i = 0; i < B; ++i)
+        if (ids[i] < 0 || ids[i] >= s->n_pshapes) return fail(QSP_ERR_ARG, "qsp_set_plant_shape_ids: id out of range");
+    HIPCHK(hipSetDevice(s->o.device));
+    HIPCHK(s->pshape_id.ensure(B * 4));
+    const int r = h2d(s, s->pshape_id, ids, B * 4);
+    if (r) return r;
+    s->has_pids = true;
+    return QSP_OK;
+}
+
+int qsp_set_plant_params(qsp_solver* s, const double* mu_sp, const double* c_ellipse) {
+    if (!s) return fail(QSP_ERR_ARG, "qsp_set_plant_params: null handle");
+    const size_t B = s->o.batch;
+    for (const double* v : {mu_sp, c_ellipse})
+        for (size_t i = 0; v && i < B; ++i)
+            if (!(std::isfinite(v[i]) && v[i] > 0.0))
+                return fail(QSP_ERR_ARG, "qsp_set_plant_params: mu_sp and c_ellipse must be finite and > 0");
+    HIPCHK(hipSetDevice(s->o.device));
+    int r;
+    if (mu_sp) {
+        HIPCHK(s->pmu.ensure(B * 8));
+        if ((r = h2d(s, s->pmu, mu_sp, B * 8))) return r;
+    }
+    if (c_ellipse) {
+        HIPCHK(s->pc.ensure(B * 8));
+        if ((r = h2d(s, s->pc, c_ellipse, B * 8))) return r;
+    }
+    s->has_pmu = mu_sp != nullptr;
+    s->has_pc = c_ellipse != nullptr;
+    return QSP_OK;
+}
+
+int qsp_clear_plant(qsp_solver* s) {
+    if (!s) return fail(QSP_ERR_ARG, "qsp_clear_plant: null handle");
+    s->n_pshapes = 0;
+    s->has_pids = s->has_pmu = s->has_pc = false;
+    return QSP_OK;
+}
+
+int qsp_get_plant(qsp_solver* s, int32_t* has_shapes, int32_t* has_params) {
+    if (!s) return fail(QSP_ERR_ARG, "qsp_get_plant: null handle");
+    if (has_shapes) *has_shapes = s->n_pshapes;
+    if (has_params) *has_params = (s->has_pmu ? 1 : 0) | (s->has_pc ? 2 : 0);
     return QSP_OK;
 }
 
@@ -899,6 +973,14 @@ static ClosedLoopArgs cl_args(qsp_solver* s) {
     a.Ts = s->o.Ts;
     a.D = s->D;
     a.ubc = s->ubc.as<double>();
+    // the plant's own model, where one is installed (else nullptr: the controller's)
+    if (s->n_pshapes > 0) {
+        a.pshapes = s->pshapes.as<ShapeDev>();
+        a.n_pshapes = s->n_pshapes;
+        a.psid = s->has_pids ? s->pshape_id.as<int32_t>() : nullptr;
+    }
+    a.pmu = s->has_pmu ? s->pmu.as<double>() : nullptr;
+    a.pc = s->has_pc ? s->pc.as<double>() : nullptr;
     return a;
 }
 
@@ -938,17 +1020,23 @@ int qsp_delay_buffer_push(qsp_solver* s, const double* u) {
     return QSP_OK;
 }
 
-int qsp_closed_loop_ex(qsp_solver* s, const qsp_closed_loop_opts* o, const double* x0, const int32_t* index0,
-                       int32_t n_steps, const double* noise, double* X_traj, double* X_sim, double* U_traj,
-                       int32_t* status_traj) {
-    if (!s || !x0 || !index0 || !X_traj || !U_traj || n_steps < 1)
-        return fail(QSP_ERR_ARG, "qsp_closed_loop: bad argument");
-    if (!s->have_traj) return fail(QSP_ERR_STATE, "qsp_closed_loop: no reference trajectory");
-    if (s->n_shapes < 1) return fail(QSP_ERR_STATE, "qsp_closed_loop: no shapes set");
+static_assert(CL_NMETRICS == QSP_CL_NMETRICS, "metric columns of the kernel and of the header");
+
+// closed_loop_matlab's loop (helper.m:195-322) on the stream, for both front ends: with trajectories
+// (qsp_closed_loop_ex: B x n_steps logs in scratch 9, 10, 11 and 4) or with the per-lane metric
+// accumulators alone (qsp_closed_loop_metrics: s->cl_metrics, nothing of size B x n_steps).  The
+// final plant state is left in s->cl_x, the last status in s->status; the caller copies out and
+// synchronises.
+static int closed_loop_run(qsp_solver* s, const char* who, const qsp_closed_loop_opts* o, const double* x0,
+                           const int32_t* index0, int32_t n_steps, const double* noise, bool want_traj,
+                           bool want_xsim, bool want_metrics) {
+    const std::string w(who);
+    if (!s->have_traj) return fail(QSP_ERR_STATE, w + ": no reference trajectory");
+    if (s->n_shapes < 1) return fail(QSP_ERR_STATE, w + ": no shapes set");
     const double plant_delay = o ? o->plant_delay : 0.0;
     if (!(plant_delay >= 0.0) || std::ceil(plant_delay / s->o.Ts) > 4096.0)
-        return fail(QSP_ERR_ARG, "qsp_closed_loop: plant_delay must be in [0, 4096 Ts]");
-    if (o && o->disturbance && o->t_dist < 1) return fail(QSP_ERR_ARG, "qsp_closed_loop: t_dist must be >= 1");
+        return fail(QSP_ERR_ARG, w + ": plant_delay must be in [0, 4096 Ts]");
+    if (o && o->disturbance && o->t_dist < 1) return fail(QSP_ERR_ARG, w + ": t_dist must be >= 1");
     const size_t B = s->o.batch, T = (size_t)n_steps;
     const int Dp = (int)std::ceil(plant_delay / s->o.Ts);   // delay_buff_plant (helper.m:211)
     HIPCHK(hipSetDevice(s->o.device));
@@ -957,10 +1045,13 @@ int qsp_closed_loop_ex(qsp_solver* s, const qsp_closed_loop_opts* o, const doubl
     DevBuf& dS = s->scratch[11];
     DevBuf& dN = s->scratch[3];
     DevBuf& dXs = s->scratch[4];
-    HIPCHK(dX.ensure(B * (T + 1) * 4 * 8));
-    HIPCHK(dU.ensure(B * T * 2 * 8));
-    HIPCHK(dS.ensure(B * T * 4));
-    if (X_sim) HIPCHK(dXs.ensure(B * T * 4 * 8));
+    if (want_traj) {
+        HIPCHK(dX.ensure(B * (T + 1) * 4 * 8));
+        HIPCHK(dU.ensure(B * T * 2 * 8));
+        HIPCHK(dS.ensure(B * T * 4));
+    }
+    if (want_xsim) HIPCHK(dXs.ensure(B * T * 4 * 8));
+    if (want_metrics) HIPCHK(s->cl_metrics.ensure(B * QSP_CL_NMETRICS * 8));
     if (noise) HIPCHK(dN.ensure(T * B * 4 * 8));
     HIPCHK(s->cl_x.ensure(B * 4 * 8));
     HIPCHK(s->ubp.ensure(B * (size_t)(Dp > 0 ? Dp : 1) * 2 * 8));
@@ -980,6 +1071,7 @@ int qsp_closed_loop_ex(qsp_solver* s, const qsp_closed_loop_opts* o, const doubl
     // (NMPC_controller.m:106-110; qsp_set_delay_comp), so a second run continues from the first's
     HIPCHK(hipMemsetAsync(s->warm_valid.p, 0, B, s->stream));
     if (Dp > 0) HIPCHK(hipMemsetAsync(s->ubp.p, 0, B * (size_t)Dp * 2 * 8, s->stream));
+    if (want_metrics) HIPCHK(hipMemsetAsync(s->cl_metrics.p, 0, B * QSP_CL_NMETRICS * 8, s->stream));
     ClosedLoopArgs c = cl_args(s);
     c.n_steps = n_steps;
     c.x = s->cl_x.as<double>();
@@ -991,27 +1083,65 @@ int qsp_closed_loop_ex(qsp_solver* s, const qsp_closed_loop_opts* o, const doubl
     c.ubp = s->ubp.as<double>();
     c.u0 = s->u0.as<double>();
     c.status = s->status.as<int32_t>();
-    c.Xtraj = dX.as<double>();
-    c.Xsim = X_sim ? dXs.as<double>() : nullptr;
-    c.Utraj = dU.as<double>();
-    c.Straj = dS.as<int32_t>();
+    c.Xtraj = want_traj ? dX.as<double>() : nullptr;
+    c.Xsim = want_xsim ? dXs.as<double>() : nullptr;
+    c.Utraj = want_traj ? dU.as<double>() : nullptr;
+    c.Straj = want_traj ? dS.as<int32_t>() : nullptr;
+    if (want_metrics) {
+        c.metrics = s->cl_metrics.as<double>();
+        c.mtraj = s->traj.as<double>();
+        c.mT = s->T;
+        c.mper_lane = s->traj_per_lane ? 1 : 0;
+        c.index0 = s->index_time.as<int32_t>();
+        c.s_lo = s->p.lh[0];
+        c.s_hi = s->p.uh[0];
+    }
     HIPCHK(hipEventRecord(s->ev0, s->stream));
     const SolveArgs a = controller_args(s);
     for (int32_t t = 0; t < n_steps; ++t) {
         HIPCHK(launch_closed_loop_pre(c, t, s->stream));                       // disturbance, noise, delay_buffer_sim
         HIPCHK(launch_controller_step(s, t + s->D));                           // y_ref for index0 + t + D
         HIPCHK(launch_sqp(a, s->S, s->stream, take_kernel_events(s), sqp_split(s)));   // NMPC_controller.solve
-        HIPCHK(launch_plant(c, t, s->stream));                                 // buffers, plant step, logs
+        HIPCHK(launch_plant(c, t, s->stream));                                 // buffers, plant step, logs, metrics
     }
     HIPCHK(hipEventRecord(s->ev1, s->stream));
-    HIPCHK(hipMemcpyAsync(X_traj, dX.p, B * (T + 1) * 4 * 8, hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(hipMemcpyAsync(U_traj, dU.p, B * T * 2 * 8, hipMemcpyDeviceToHost, s->stream));
-    if (X_sim) HIPCHK(hipMemcpyAsync(X_sim, dXs.p, B * T * 4 * 8, hipMemcpyDeviceToHost, s->stream));
-    if (status_traj) HIPCHK(hipMemcpyAsync(status_traj, dS.p, B * T * 4, hipMemcpyDeviceToHost, s->stream));
+    return QSP_OK;
+}
+
+static int closed_loop_done(qsp_solver* s) {
     HIPCHK(hipStreamSynchronize(s->stream));
     HIPCHK(hipEventElapsedTime(&s->last_ms, s->ev0, s->ev1));
     s->solved = true;
     return QSP_OK;
+}
+
+int qsp_closed_loop_ex(qsp_solver* s, const qsp_closed_loop_opts* o, const double* x0, const int32_t* index0,
+                       int32_t n_steps, const double* noise, double* X_traj, double* X_sim, double* U_traj,
+                       int32_t* status_traj) {
+    if (!s || !x0 || !index0 || !X_traj || !U_traj || n_steps < 1)
+        return fail(QSP_ERR_ARG, "qsp_closed_loop: bad argument");
+    const int r = closed_loop_run(s, "qsp_closed_loop", o, x0, index0, n_steps, noise, true, X_sim != nullptr, false);
+    if (r) return r;
+    const size_t B = s->o.batch, T = (size_t)n_steps;
+    HIPCHK(hipMemcpyAsync(X_traj, s->scratch[9].p, B * (T + 1) * 4 * 8, hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(hipMemcpyAsync(U_traj, s->scratch[10].p, B * T * 2 * 8, hipMemcpyDeviceToHost, s->stream));
+    if (X_sim) HIPCHK(hipMemcpyAsync(X_sim, s->scratch[4].p, B * T * 4 * 8, hipMemcpyDeviceToHost, s->stream));
+    if (status_traj) HIPCHK(hipMemcpyAsync(status_traj, s->scratch[11].p, B * T * 4, hipMemcpyDeviceToHost, s->stream));
+    return closed_loop_done(s);
+}
+
+int qsp_closed_loop_metrics(qsp_solver* s, const qsp_closed_loop_opts* o, const double* x0, const int32_t* index0,
+                            int32_t n_steps, const double* noise, double* metrics, double* x_end,
+                            int32_t* status_last) {
+    if (!s || !x0 || !index0 || !metrics || n_steps < 1)
+        return fail(QSP_ERR_ARG, "qsp_closed_loop_metrics: bad argument");
+    const int r = closed_loop_run(s, "qsp_closed_loop_metrics", o, x0, index0, n_steps, noise, false, false, true);
+    if (r) return r;
+    const size_t B = s->o.batch;
+    HIPCHK(hipMemcpyAsync(metrics, s->cl_metrics.p, B * QSP_CL_NMETRICS * 8, hipMemcpyDeviceToHost, s->stream));
+    if (x_end) HIPCHK(hipMemcpyAsync(x_end, s->cl_x.p, B * 4 * 8, hipMemcpyDeviceToHost, s->stream));
+    if (status_last) HIPCHK(hipMemcpyAsync(status_last, s->status.p, B * 4, hipMemcpyDeviceToHost, s->stream));
+    return closed_loop_done(s);
 }
 
 int qsp_closed_loop(qsp_solver* s, const double* x0, const int32_t* index0, int32_t n_steps, const double* noise,

@@ -120,11 +120,28 @@ struct ClosedLoopArgs {
     double* ubp;               // B x Dp x 2 u_buff_plant
     const double* u0;          // B x 2   the solve's u0
     const int32_t* status;     // B
-    double* Xtraj;             // B x (n_steps + 1) x 4
+    double* Xtraj;             // B x (n_steps + 1) x 4 or nullptr (a metrics run)
     double* Xsim;              // B x n_steps x 4 or nullptr
-    double* Utraj;             // B x n_steps x 2
+    double* Utraj;             // B x n_steps x 2 or nullptr (a metrics run)
     int32_t* Straj;            // B x n_steps or nullptr
+    // The plant's own model (qsp_set_plant_*; helper.m passes `plant` beside `controller`): the Euler
+    // step, the delay prediction and the disturbance re-projection read lane i's shape from this table
+    // and c, mu from the overrides.  All nullable: no table -> the controller's shape (shapes / sid
+    // above), no override -> the plant shape's own constant.
+    const ShapeDev* pshapes;
+    int32_t n_pshapes;
+    const int32_t* psid;       // B ids into pshapes (nullptr: plant shape 0); clamped
+    const double* pmu;         // B mu_sp of the plant or nullptr
+    const double* pc;          // B c_ellipse of the plant or nullptr
+    // Per-lane metrics of the run (qsp_closed_loop_metrics), accumulated by plant_kernel; with them
+    // Xtraj and Utraj may be nullptr (nothing of size B x n_steps is kept)
+    double* metrics;           // B x QSP_CL_NMETRICS or nullptr
+    const double* mtraj;       // the reference table as installed: T x 6, or B x T x 6 (mper_lane)
+    int32_t mT, mper_lane;
+    const int32_t* index0;     // B, 1-based column of step 1
+    double s_lo, s_hi;         // the handle's lh[0], uh[0]
 };
+constexpr int CL_NMETRICS = 10;   // QSP_CL_NMETRICS (include/qsp_nmpc.h), columns QSP_CLM_*
 hipError_t launch_closed_loop_pre(const ClosedLoopArgs& a, int t, hipStream_t stream);
 hipError_t launch_plant(const ClosedLoopArgs& a, int t, hipStream_t stream);
 hipError_t launch_delay_sim(const ClosedLoopArgs& a, hipStream_t stream);   // x -> xs (delay_buffer_sim)

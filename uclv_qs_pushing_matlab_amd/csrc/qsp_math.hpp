@@ -132,8 +132,26 @@ __device__ __forceinline__ double blend3(double ist, double a, double isl, doubl
     return qfma(isr, c, qfma(isl, b, ist * a));
 }
 
-template <bool WITH_JAC>
-__device__ __forceinline__ void dynamics(const ShapeDev& sh, double th, double s, double un, double ut, DynOut& o) {
+// dynamics_cm: the core, with the two physical constants that f reads beside the contour -- the
+// limit-surface constant c (c_ellipse) and the pusher-slider friction mu (mu_sp) -- as an argument, so that
+// a closed loop's plant can carry them per lane (qsp_set_plant_params).  They come as a small source object
+// that f asks where it first needs them, after the spline: ShapeCM hands out the shape's own fields, which
+// leaves dynamics<>'s two loads what and where they were, and with them the generated code of every kernel
+// that calls it (a value or a const double& argument moved or retyped the loads and reordered the
+// schedule of the rollout and open-loop kernels); LaneCM holds a lane's values.
+struct ShapeCM {
+    __device__ __forceinline__ double c(const ShapeDev& sh) const { return sh.c; }
+    __device__ __forceinline__ double mu(const ShapeDev& sh) const { return sh.mu; }
+};
+struct LaneCM {
+    double c_, mu_;
+    __device__ __forceinline__ double c(const ShapeDev&) const { return c_; }
+    __device__ __forceinline__ double mu(const ShapeDev&) const { return mu_; }
+};
+
+template <bool WITH_JAC, class CM>
+__device__ __forceinline__ void dynamics_cm(const ShapeDev& sh, const CM& cm, double th, double s, double un, double ut,
+                                            DynOut& o) {
     const double sig = smod_model(s, sh.b);
     SplineEval e;
     spline_eval(sh, sig, e);
@@ -148,7 +166,7 @@ __device__ __forceinline__ void dynamics(const ShapeDev& sh, double th, double s
     const double px = qfma(nx, Px, ny * Py);
     const double py = qfma(tx, Px, ty * Py);
 
-    const double c2 = sh.c * sh.c, mu = sh.mu;
+    const double c2 = cm.c(sh) * cm.c(sh), mu = cm.mu(sh);
     const double pxpy = px * py, px2 = px * px;
     const double q00 = qfma(px, px, c2), q11 = qfma(py, py, c2);
     const double fac = 1.0 / qfma(py, py, q00);                        // :544
@@ -238,6 +256,11 @@ __device__ __forceinline__ void dynamics(const ShapeDev& sh, double th, double s
     o.Jut[3] = isl + isr;
 }
 
+template <bool WITH_JAC>
+__device__ __forceinline__ void dynamics(const ShapeDev& sh, double th, double s, double un, double ut, DynOut& o) {
+    dynamics_cm<WITH_JAC>(sh, ShapeCM{}, th, s, un, ut, o);
+}
+
 // ---------------------------------------------------------------- contact mode
 // The motion cone at the contact point s and the branch of f that the input (un, ut) selects:
 // dynamics<> restated up to and including its three indicators, the same operations in the same
@@ -260,7 +283,9 @@ struct MotionCone {
     int mode;             // QSP_MODE_*
 };
 
-__device__ __forceinline__ MotionCone motion_cone(const ShapeDev& sh, double s, double un, double ut) {
+// motion_cone_cm: the core with the source of c and mu as an argument (dynamics_cm's counterpart)
+template <class CM>
+__device__ __forceinline__ MotionCone motion_cone_cm(const ShapeDev& sh, const CM& cm, double s, double un, double ut) {
     const double sig = smod_model(s, sh.b);
     SplineEval e;
     spline_eval(sh, sig, e);
@@ -273,7 +298,7 @@ __device__ __forceinline__ MotionCone motion_cone(const ShapeDev& sh, double s, 
     const double px = qfma(nx, Px, ny * Py);
     const double py = qfma(tx, Px, ty * Py);
 
-    const double c2 = sh.c * sh.c, mu = sh.mu;
+    const double c2 = cm.c(sh) * cm.c(sh), mu = cm.mu(sh);
     const double pxpy = px * py, px2 = px * px;
     const double q11 = qfma(py, py, c2);
     const double nl = qfma(mu, px2, qfma(mu, c2, -pxpy));
@@ -290,6 +315,10 @@ __device__ __forceinline__ MotionCone motion_cone(const ShapeDev& sh, double s, 
            : (o.rho < o.gr)                       ? QSP_MODE_SR
                                                   : QSP_MODE_NONE;
     return o;
+}
+
+__device__ __forceinline__ MotionCone motion_cone(const ShapeDev& sh, double s, double un, double ut) {
+    return motion_cone_cm(sh, ShapeCM{}, s, un, ut);
 }
 
 // ---------------------------------------------------------------- RK4 + VDE

@@ -2487,10 +2487,26 @@ __device__ double reproject_contact(const ShapeDev& sh, double px, double py, do
     return s;
 }
 
+// With a plant model installed (qsp_set_plant_*) the three kernels below take lane i's shape, c and
+// mu from it (plant_of): the reference simulates, predicts and re-projects with `plant`
+// (helper.m:226-233, :244, :294-307) and keeps the controller's model for solve alone.
+
+// Lane i's plant: the shape and the two constants f reads beside it
+struct PlantModel {
+    const ShapeDev* sh;
+    LaneCM cm;
+};
+__device__ __forceinline__ PlantModel plant_of(const ClosedLoopArgs& a, int i) {
+    const ShapeDev& sh = a.pshapes ? shape_clamped(a.pshapes, a.n_pshapes, a.psid, i)
+                                   : shape_clamped(a.shapes, a.n_shapes, a.sid, i);
+    return PlantModel{&sh, LaneCM{a.pc ? a.pc[i] : sh.c, a.pmu ? a.pmu[i] : sh.mu}};
+}
+
 __global__ void closed_loop_pre_kernel(ClosedLoopArgs a, int t) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.B) return;
-    const ShapeDev& sh = shape_clamped(a.shapes, a.n_shapes, a.sid, i);
+    const PlantModel pm = plant_of(a, i);
+    const ShapeDev& sh = *pm.sh;
     double x[4] = {a.x[(size_t)i * 4], a.x[(size_t)i * 4 + 1], a.x[(size_t)i * 4 + 2], a.x[(size_t)i * 4 + 3]};
     if (a.dist_step > 0 && t + 1 == a.dist_step) {
         // y += amplitude; new contact: the spline point nearest (-xwidth/2, C_y(s) - amplitude),
@@ -2506,13 +2522,13 @@ __global__ void closed_loop_pre_kernel(ClosedLoopArgs a, int t) {
         for (int c = 0; c < 4; ++c) x[c] += a.noise[((size_t)t * a.B + i) * 4 + c];
     for (int c = 0; c < 4; ++c) {
         a.x[(size_t)i * 4 + c] = x[c];
-        a.Xtraj[((size_t)i * (a.n_steps + 1) + t) * 4 + c] = x[c];
+        if (a.Xtraj) a.Xtraj[((size_t)i * (a.n_steps + 1) + t) * 4 + c] = x[c];
     }
     // delay_buffer_sim: D Euler steps with the buffered inputs, oldest (u_buff_contr(:, end)) first
     for (int k = 1; k <= a.D; ++k) {
         const double* u = a.ubc + ((size_t)i * a.D + (a.D - k)) * 2;
         DynOut d;
-        dynamics<false>(sh, x[2], x[3], u[0], u[1], d);
+        dynamics_cm<false>(sh, pm.cm, x[2], x[3], u[0], u[1], d);
         for (int c = 0; c < 4; ++c) x[c] = qfma(a.Ts, d.f[c], x[c]);
     }
     for (int c = 0; c < 4; ++c) a.xs[(size_t)i * 4 + c] = x[c];
@@ -2520,10 +2536,43 @@ __global__ void closed_loop_pre_kernel(ClosedLoopArgs a, int t) {
         for (int c = 0; c < 4; ++c) a.Xsim[((size_t)i * a.n_steps + t) * 4 + c] = x[c];
 }
 
+// Row of lane i's reference table at the 1-based column col, clamped at both ends as get_y_ref clamps
+// (NMPC_controller.m:307-313); the table as installed, without the delay prefix
+__device__ __forceinline__ const double* metrics_ref(const ClosedLoopArgs& a, int i, int col) {
+    col = col > a.mT ? a.mT : col;
+    col = col < 1 ? 1 : col;
+    return a.mtraj + ((size_t)(a.mper_lane ? i : 0) * a.mT + (size_t)(col - 1)) * 6;
+}
+
+// qsp_closed_loop_metrics' accumulators of lane i for step t (0-based): x the logged plant state (after
+// disturbance and noise), xn the state after the plant step, u the commanded and ua the applied input.
+// Plain products and sums in step order (no qfma), so that numpy restates them bit for bit.
+__device__ __forceinline__ void metrics_step(const ClosedLoopArgs& a, const PlantModel& pm, int i, int t,
+                                             const double x[4], const double xn[4], const double u[2],
+                                             const double ua[2]) {
+    double* m = a.metrics + (size_t)i * CL_NMETRICS;
+    const double* r = metrics_ref(a, i, a.index0[i] + t);
+    const double ex = x[0] - r[0], ey = x[1] - r[1], et = x[2] - r[2];
+    const double e2 = ex * ex + ey * ey;
+    m[0] = m[0] + e2;
+    m[1] = e2 > m[1] ? e2 : m[1];
+    m[2] = m[2] + et * et;
+    if (t + 1 == a.n_steps) {
+        const double* re = metrics_ref(a, i, a.index0[i] + a.n_steps);
+        const double fx = xn[0] - re[0], fy = xn[1] - re[1];
+        m[3] = fx * fx + fy * fy;
+    }
+    m[4] = m[4] + (u[0] * u[0] + u[1] * u[1]);
+    if (a.status[i] != 0) m[5] = m[5] + 1.0;
+    const int mode = motion_cone_cm(*pm.sh, pm.cm, x[3], ua[0], ua[1]).mode;
+    if (mode != QSP_MODE_NONE) m[5 + mode] = m[5 + mode] + 1.0;   // 6, 7, 8: ST, SL, SR
+    if (!(x[3] >= a.s_lo && x[3] <= a.s_hi)) m[9] = m[9] + 1.0;
+}
+
 __global__ void plant_kernel(ClosedLoopArgs a, int t) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.B) return;
-    const ShapeDev& sh = shape_clamped(a.shapes, a.n_shapes, a.sid, i);
+    const PlantModel pm = plant_of(a, i);
     double xi[4] = {a.x[(size_t)i * 4], a.x[(size_t)i * 4 + 1], a.x[(size_t)i * 4 + 2], a.x[(size_t)i * 4 + 3]};
     const double u[2] = {a.u0[(size_t)i * 2], a.u0[(size_t)i * 2 + 1]};
     // u_buff_contr = [u, u_buff_contr(:, 1:end-1)]
@@ -2543,27 +2592,31 @@ __global__ void plant_kernel(ClosedLoopArgs a, int t) {
         b[1] = u[1];
     }
     DynOut d;
-    dynamics<false>(sh, xi[2], xi[3], ua[0], ua[1], d);
+    dynamics_cm<false>(*pm.sh, pm.cm, xi[2], xi[3], ua[0], ua[1], d);
+    double xn[4];
     for (int c = 0; c < 4; ++c) {
-        const double v = qfma(a.Ts, d.f[c], xi[c]);
-        a.x[(size_t)i * 4 + c] = v;
-        if (t + 1 == a.n_steps) a.Xtraj[((size_t)i * (a.n_steps + 1) + t + 1) * 4 + c] = v;
+        xn[c] = qfma(a.Ts, d.f[c], xi[c]);
+        a.x[(size_t)i * 4 + c] = xn[c];
+        if (a.Xtraj && t + 1 == a.n_steps) a.Xtraj[((size_t)i * (a.n_steps + 1) + t + 1) * 4 + c] = xn[c];
     }
-    a.Utraj[((size_t)i * a.n_steps + t) * 2] = u[0];
-    a.Utraj[((size_t)i * a.n_steps + t) * 2 + 1] = u[1];
+    if (a.Utraj) {
+        a.Utraj[((size_t)i * a.n_steps + t) * 2] = u[0];
+        a.Utraj[((size_t)i * a.n_steps + t) * 2 + 1] = u[1];
+    }
     if (a.Straj) a.Straj[(size_t)i * a.n_steps + t] = a.status[i];
+    if (a.metrics) metrics_step(a, pm, i, t, xi, xn, u, ua);
 }
 
 // NMPC_controller.delay_buffer_sim alone (qsp_delay_buffer_sim)
 __global__ void delay_sim_kernel(ClosedLoopArgs a) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.B) return;
-    const ShapeDev& sh = shape_clamped(a.shapes, a.n_shapes, a.sid, i);
+    const PlantModel pm = plant_of(a, i);
     double x[4] = {a.x[(size_t)i * 4], a.x[(size_t)i * 4 + 1], a.x[(size_t)i * 4 + 2], a.x[(size_t)i * 4 + 3]};
     for (int k = 1; k <= a.D; ++k) {
         const double* u = a.ubc + ((size_t)i * a.D + (a.D - k)) * 2;
         DynOut d;
-        dynamics<false>(sh, x[2], x[3], u[0], u[1], d);
+        dynamics_cm<false>(*pm.sh, pm.cm, x[2], x[3], u[0], u[1], d);
         for (int c = 0; c < 4; ++c) x[c] = qfma(a.Ts, d.f[c], x[c]);
     }
     for (int c = 0; c < 4; ++c) a.xs[(size_t)i * 4 + c] = x[c];

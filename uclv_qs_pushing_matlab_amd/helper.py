@@ -5,7 +5,10 @@ the disturbance branch (:221-236: y offset, contact re-projected onto the contou
 fminunc restated as a damped Newton iteration), sim_noise (:240-242), the controller's delay
 prediction delay_buffer_sim and its input buffer (NMPC_controller.m:112-120, helper.m:255),
 NMPC_controller.solve, and the plant step with evalModelVariableShape and the plant's own delay
-buffer (:289-307).  Not reproduced: print_ (console output).
+buffer (:289-307).  Not reproduced: print_ (console output).  The loop simulates with `plant` and solves with
+the controller's model, as the reference does: a plant that is not the controller's own object is installed on
+the handle for the call (OcpSolver.set_plant), with per-lane friction / limit-surface overrides for Monte-Carlo
+runs, and closed_loop_metrics reduces such a run to per-lane metrics on the device.
 
 helper.evaluate_cost_function and helper.debug_cost_function (helper.m:356-431), the reference's
 optimality probe, run on the device too (OcpSolver.rollout_cost / cost_landscape): the cost of a control
@@ -20,6 +23,8 @@ modes that the reference plots from mode_vect (convert_str2num, my_plot) come fr
 labels a closed loop's trajectories.  Coding: "ST" 1, "SL" 2, "SR" 3; 0 / "" where u_t / u_n is NaN (both
 inputs zero, as a delayed plant's buffer holds at its start), which the reference's if-chain would call "SR".
 """
+import contextlib
+
 import numpy as np
 
 
@@ -87,11 +92,30 @@ def debug_cost_function(x0, u_n_lb, u_t_lb, u_n_ub, u_t_ub, controller, plant, i
     return r["u_min"], np.ascontiguousarray(r["cost"].transpose(0, 2, 1)), UN, UT
 
 
-def closed_loop_matlab(plant, controller, x0, time_sim, print_=False, sim_noise=False, debug_cost=False,
-                       disturbance_=False, amplitude_dist=0.0, t_dist=0, seed=0):
-    """Returns (x_s, x_sim, y_s, theta_s, S_p_x, S_p_y, u_n, u_t, time_sim_vec, mode_vect, found_sol),
-    each with a leading batch dimension B (helper.m:195-197; x_sim is (B, 2T+1, 4): the reference's
-    4 x (2T+1) with its T+1 leading zero columns); amplitude_dist may be per lane."""
+@contextlib.contextmanager
+def _plant_for_call(plant, controller, plant_mu_sp, plant_c_ellipse):
+    """The handle's plant model for one closed-loop call.  A `plant` that is not the controller's own object
+    is installed as the plant's shape for every lane (the reference simulates with plant, solves with
+    controller: helper.m:226-233, :244, :294-307), per-lane mu_sp / c_ellipse overrides on top; what was
+    installed before comes back on every exit path.  With the controller's own plant object and no
+    overrides nothing is touched."""
+    sv = controller.ocp_solver
+    foreign = plant is not controller.plant
+    if not foreign and plant_mu_sp is None and plant_c_ellipse is None:
+        yield
+        return
+    prev = sv.plant()
+    try:
+        sv.set_plant(shapes=[plant.shape] if foreign else None, mu_sp=plant_mu_sp, c_ellipse=plant_c_ellipse)
+        yield
+    finally:
+        if prev is None:
+            sv.clear_plant()
+        else:
+            sv.set_plant(**prev)
+
+
+def _closed_loop_inputs(controller, x0, time_sim, sim_noise, seed):
     Ts = controller.sample_time
     time_sim_vec = np.arange(0.0, time_sim + 1e-9, Ts)                      # :198
     T = len(time_sim_vec)
@@ -101,9 +125,23 @@ def closed_loop_matlab(plant, controller, x0, time_sim, print_=False, sim_noise=
         rng = np.random.default_rng(seed)
         noise = rng.standard_normal((T, B, 4)) * np.array([1e-5, 1e-5, 1e-3, 1e-4])
     x0 = np.broadcast_to(np.asarray(x0, np.float64).reshape(-1, 4), (B, 4))
-    r = controller.ocp_solver.closed_loop(x0, T, index0=1, noise=noise, plant_delay=plant.time_delay,
-                                          disturbance=bool(disturbance_), t_dist=int(t_dist),
-                                          amplitude=amplitude_dist)
+    return time_sim_vec, T, B, noise, x0
+
+
+def closed_loop_matlab(plant, controller, x0, time_sim, print_=False, sim_noise=False, debug_cost=False,
+                       disturbance_=False, amplitude_dist=0.0, t_dist=0, seed=0, plant_mu_sp=None,
+                       plant_c_ellipse=None):
+    """Returns (x_s, x_sim, y_s, theta_s, S_p_x, S_p_y, u_n, u_t, time_sim_vec, mode_vect, found_sol),
+    each with a leading batch dimension B (helper.m:195-197; x_sim is (B, 2T+1, 4): the reference's
+    4 x (2T+1) with its T+1 leading zero columns); amplitude_dist may be per lane.
+    The loop simulates with `plant` and solves with the controller's model: a plant other than
+    controller.plant is the handle's plant for the call (OcpSolver.set_plant), and plant_mu_sp /
+    plant_c_ellipse (scalars or (B,)) override its friction and limit-surface constant per lane."""
+    time_sim_vec, T, B, noise, x0 = _closed_loop_inputs(controller, x0, time_sim, sim_noise, seed)
+    with _plant_for_call(plant, controller, plant_mu_sp, plant_c_ellipse):
+        r = controller.ocp_solver.closed_loop(x0, T, index0=1, noise=noise, plant_delay=plant.time_delay,
+                                              disturbance=bool(disturbance_), t_dist=int(t_dist),
+                                              amplitude=amplitude_dist)
     X, U = r["X"][:, :T], r["U"]
     found_sol = r["status"] == 0                                            # :253-260
     S_p = plant.SP.FC(X[:, :, 3].ravel()).reshape(B, T, 2)                 # :316-318
@@ -112,6 +150,18 @@ def closed_loop_matlab(plant, controller, x0, time_sim, print_=False, sim_noise=
     x_sim = np.concatenate([np.zeros((B, T + 1, 4)), r["Xsim"]], 1)
     return (X[:, :, 0], x_sim, X[:, :, 1], X[:, :, 2], S_p[..., 0], S_p[..., 1], U[:, :, 0], U[:, :, 1],
             time_sim_vec, mode_vect, found_sol)
+
+
+def closed_loop_metrics(plant, controller, x0, time_sim, print_=False, sim_noise=False, debug_cost=False,
+                        disturbance_=False, amplitude_dist=0.0, t_dist=0, seed=0, plant_mu_sp=None,
+                        plant_c_ellipse=None):
+    """closed_loop_matlab's run with the same arguments, reduced on the device to per-lane metrics
+    (OcpSolver.closed_loop_metrics' dict): no trajectory comes back to the host."""
+    _, T, _, noise, x0 = _closed_loop_inputs(controller, x0, time_sim, sim_noise, seed)
+    with _plant_for_call(plant, controller, plant_mu_sp, plant_c_ellipse):
+        return controller.ocp_solver.closed_loop_metrics(x0, T, index0=1, noise=noise, plant_delay=plant.time_delay,
+                                                         disturbance=bool(disturbance_), t_dist=int(t_dist),
+                                                         amplitude=amplitude_dist)
 
 
 MODE_NUM = {"ST": 1, "SL": 2, "SR": 3, "": 0}      # helper.m:17-23; "" = no indicator set (QSP_MODE_NONE)

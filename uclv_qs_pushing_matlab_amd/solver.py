@@ -74,6 +74,7 @@ class OcpSolver:
         self._refs_staged = False   # the device references are a controller step's, newer than set('cost_y_ref*')
         self.n_shapes = 0
         self.shape_ids = np.zeros(Bn, np.int32)   # host copy of the per-lane shape ids (helper.mode_trace)
+        self._plant = None                        # host copy of the installed plant model (set_plant)
         # timings=True: per-kernel HIP events around every solve, for get('time_lin'/'time_qp_sol')
         self._timings = bool(timings)
         self._last_times = None
@@ -119,6 +120,61 @@ class OcpSolver:
         sid = i32(np.broadcast_to(np.asarray(shape_id, np.int32), (self.B,)))
         check(self._L.qsp_set_shape_ids(self._h, ptr(sid)), "qsp_set_shape_ids")
         self.shape_ids = sid.copy()
+
+    # ------------------------------------------- the plant's own model
+    def _install_plant(self, p):
+        """The handle's plant <- p (a plant() dict or None), from a cleared state."""
+        check(self._L.qsp_clear_plant(self._h), "qsp_clear_plant")
+        self._plant = None
+        if p is None:
+            return
+        if p["shapes"] is not None:
+            arr = (_lib.Shape * len(p["shapes"]))(*p["shapes"])
+            check(self._L.qsp_set_plant_shapes(self._h, arr, len(p["shapes"])), "qsp_set_plant_shapes")
+            if p["shape_id"] is not None:
+                check(self._L.qsp_set_plant_shape_ids(self._h, ptr(p["shape_id"])), "qsp_set_plant_shape_ids")
+        if p["mu_sp"] is not None or p["c_ellipse"] is not None:
+            check(self._L.qsp_set_plant_params(self._h, ptr(p["mu_sp"]), ptr(p["c_ellipse"])), "qsp_set_plant_params")
+        self._plant = p
+
+    def set_plant(self, shapes=None, shape_id=None, mu_sp=None, c_ellipse=None):
+        """The model that closed_loop simulates with, where it is not the controller's (closed_loop_matlab's
+        `plant` argument, helper.m:195-322): the plant step, the delay prediction, the disturbance
+        re-projection and the mode counts of closed_loop_metrics read it; the solve keeps the controller's.
+        shapes: a plant shape table with shape_id (scalar or (B,), default 0) into it; None: the controller's
+        shapes.  mu_sp, c_ellipse: scalar or (B,) overrides of the plant shape's two constants, finite and
+        > 0.  Replaces what was installed; all None is clear_plant().  When the library rejects an argument
+        the plant installed before the call is put back."""
+        if shapes is None and shape_id is not None:
+            raise ValueError("set_plant: shape_id needs a plant shape table (shapes)")
+        lanes = lambda v: None if v is None else f64(np.broadcast_to(np.asarray(v, np.float64), (self.B,)))  # noqa: E731
+        p = dict(shapes=None if shapes is None else list(shapes),
+                 shape_id=None if shape_id is None else i32(np.broadcast_to(np.asarray(shape_id, np.int32), (self.B,))),
+                 mu_sp=lanes(mu_sp), c_ellipse=lanes(c_ellipse))
+        if all(v is None for v in p.values()):
+            p = None
+        prev = self._plant
+        try:
+            self._install_plant(p)
+        except Exception:
+            self._install_plant(prev)
+            raise
+
+    def clear_plant(self):
+        """Back to "the plant is the controller's model", the state of a new solver."""
+        self._install_plant(None)
+
+    def plant(self):
+        """What set_plant installed: None, or dict(shapes, shape_id, mu_sp, c_ellipse) with None for what
+        is left to the controller's model / the plant shape.  set_plant(**p) installs such a dict again."""
+        hs, hp = C.c_int32(), C.c_int32()
+        check(self._L.qsp_get_plant(self._h, C.byref(hs), C.byref(hp)), "qsp_get_plant")
+        p = self._plant
+        want = (0, 0) if p is None else (0 if p["shapes"] is None else len(p["shapes"]),
+                                         (p["mu_sp"] is not None) | 2 * (p["c_ellipse"] is not None))
+        if (hs.value, hp.value) != want:
+            raise _lib.QspError(f"plant(): the handle reports {(hs.value, hp.value)}, this object installed {want}")
+        return None if p is None else dict(p)
 
     # ----------------------------------------------------------------- set
     def _lanes(self, v, width):
@@ -444,12 +500,8 @@ class OcpSolver:
         self._refs_staged = True
         return self.get_u0()
 
-    def closed_loop(self, x0, n_steps, index0=1, noise=None, plant_delay=0.0, disturbance=False, t_dist=0,
-                    amplitude=None):
-        """Device-resident closed loop (helper.m:195-322): returns X (B, n+1, 4) (plant states after
-        disturbance and noise), Xsim (B, n, 4) (the delay-predicted states the solver sees), U (B, n, 2),
-        status (B, n).  noise: (n, B, 4) additive state noise before each solve, or None; plant_delay [s];
-        disturbance at the 1-based step t_dist with per-lane amplitude (y offset + contact re-projection)."""
+    def _closed_loop_args(self, x0, n_steps, index0, noise, plant_delay, disturbance, t_dist, amplitude):
+        """The two closed-loop entries' common arguments; the amplitude array is returned to keep it alive."""
         n = int(n_steps)
         x0 = f64(self._lanes(x0, 4))
         idx = i32(np.broadcast_to(np.asarray(index0, np.int32), (self.B,)))
@@ -458,6 +510,37 @@ class OcpSolver:
         o = _lib.ClosedLoopOpts()
         o.plant_delay, o.disturbance, o.t_dist = float(plant_delay), 1 if disturbance else 0, int(t_dist)
         o.amplitude = None if amp is None else amp.ctypes.data
+        return n, x0, idx, nz, o, amp
+
+    METRICS = ("sum_exy2", "max_exy2", "sum_eth2", "end_exy2", "sum_u2", "n_failed", "n_st", "n_sl", "n_sr",
+               "n_s_out")   # QSP_CLM_* (include/qsp_nmpc.h)
+
+    def closed_loop_metrics(self, x0, n_steps, index0=1, noise=None, plant_delay=0.0, disturbance=False, t_dist=0,
+                            amplitude=None):
+        """closed_loop's run reduced on the device to per-lane metrics (qsp_closed_loop_metrics): no trajectory
+        is kept or copied.  Returns dict(metrics (B, 10), one (B,) column under each name of METRICS, x_end
+        (B, 4) the state after the last plant step, status (B,) the last solve's).  The tracking errors are
+        against the installed reference table at column index0 + i - 1, clamped at its end."""
+        n, x0, idx, nz, o, _amp = self._closed_loop_args(x0, n_steps, index0, noise, plant_delay, disturbance, t_dist,
+                                                         amplitude)
+        m = np.zeros((self.B, len(self.METRICS)))
+        xe = np.zeros((self.B, 4))
+        st = np.zeros(self.B, np.int32)
+        check(self._L.qsp_closed_loop_metrics(self._h, C.byref(o), ptr(x0), ptr(idx), n, ptr(nz), ptr(m), ptr(xe),
+                                              ptr(st)), "qsp_closed_loop_metrics")
+        self._refs_staged = True
+        out = dict(metrics=m, x_end=xe, status=st)
+        out.update({k: m[:, j] for j, k in enumerate(self.METRICS)})
+        return out
+
+    def closed_loop(self, x0, n_steps, index0=1, noise=None, plant_delay=0.0, disturbance=False, t_dist=0,
+                    amplitude=None):
+        """Device-resident closed loop (helper.m:195-322): returns X (B, n+1, 4) (plant states after
+        disturbance and noise), Xsim (B, n, 4) (the delay-predicted states the solver sees), U (B, n, 2),
+        status (B, n).  noise: (n, B, 4) additive state noise before each solve, or None; plant_delay [s];
+        disturbance at the 1-based step t_dist with per-lane amplitude (y offset + contact re-projection)."""
+        n, x0, idx, nz, o, _amp = self._closed_loop_args(x0, n_steps, index0, noise, plant_delay, disturbance, t_dist,
+                                                         amplitude)
         X = np.zeros((self.B, n + 1, 4))
         Xs = np.zeros((self.B, n, 4))
         U = np.zeros((self.B, n, 2))

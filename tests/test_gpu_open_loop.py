@@ -440,3 +440,34 @@ def test_argument_checks_leave_the_handle_usable():
         assert run() == 0 and np.array_equal(xe, first)
     finally:
         s.close()
+
+
+# ------------------------------------------------------------------ device entry equals host entry
+@pytest.mark.parametrize("tile", [0, 1, 4, 8])
+@pytest.mark.parametrize("M", [3, 65])
+def test_open_loop_device_equals_host(M, tile):
+    """B = 5, T = 9 (tiles of 4 and of 8 steps both end on a partial tile), M = 3 (several lanes per workgroup) and
+    65 (one lane per workgroup); clip, a plant delay of two columns, noise, every output; device memory from torch."""
+    import torch
+    from uclv_qs_pushing_matlab_amd._lib import OpenLoopIO
+    B, T = 5, 9
+    s, shapes = _solver(B, N=4)
+    x0, U = _x0(B, 41, shapes), _U(B, M, 42)
+    noise = np.random.default_rng(43).normal(0.0, 1e-4, (T, B, 4))
+    dev0 = torch.device("cuda", 0)
+    try:
+        host = s.open_loop(x0, U, T, noise=noise, plant_delay=2 * TS, clip=True, want=ALL, store_tile=tile)
+        ins = dict(x0=x0, U=U, noise=noise)
+        outs = {k: np.full_like(v, -7) for k, v in host.items()}                  # a value no output holds
+        t = {k: torch.as_tensor(np.ascontiguousarray(v), device=dev0) for k, v in {**ins, **outs}.items()}
+        io = OpenLoopIO()
+        for k, v in t.items():
+            setattr(io, k, v.data_ptr())
+        torch.cuda.synchronize()                            # the tensors are filled before the handle's stream reads them
+        s.open_loop_device(io, T, M, u_steps=1, plant_delay=2 * TS, clip=True, store_tile=tile)
+        s.synchronize()
+        assert set(host) == set(ALL) | {"x_end"}
+        for k in host:
+            assert np.array_equal(host[k], t[k].cpu().numpy()), k
+    finally:
+        s.close()

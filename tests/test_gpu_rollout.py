@@ -387,3 +387,105 @@ def test_argument_checks_leave_the_handle_usable():
     finally:
         s.close()
         f.close()
+
+
+# ------------------------------------------------------------------ 7. device entries equal host entries
+def _dev(a):
+    import torch
+    return torch.as_tensor(np.ascontiguousarray(a), device=torch.device("cuda", 0))
+
+
+def _dev_out(shape, dtype=np.float64):
+    return _dev(np.full(shape, -7, dtype))              # a value no output holds
+
+
+def _rollout_device(s, M, integ, x0, U, yref, ye, sid=None, U_dev=None):
+    """qsp_rollout_cost_device on torch tensors -> (cost, viol, x_end) as numpy."""
+    import torch
+    from uclv_qs_pushing_matlab_amd._lib import RolloutIO
+    B = len(x0)
+    ins = [_dev(x0), U_dev if U_dev is not None else _dev(U), _dev(yref), _dev(ye)]
+    ids = None if sid is None else _dev(np.asarray(sid, np.int32))
+    outs = [_dev_out((B, M)), _dev_out((B, M)), _dev_out((B, M, 4))]
+    io = RolloutIO()
+    io.x0, io.U, io.yref, io.yref_e = (t.data_ptr() for t in ins)
+    io.shape_id = ids.data_ptr() if ids is not None else None
+    io.cost, io.viol, io.x_end = (t.data_ptr() for t in outs)
+    torch.cuda.synchronize()                            # the tensors are filled before the handle's stream reads them
+    s.rollout_cost_device(io, M, integrator=integ)
+    s.synchronize()
+    return tuple(t.cpu().numpy() for t in outs)
+
+
+@pytest.mark.parametrize("integ", ["euler", "rk4"])
+@pytest.mark.parametrize("M", [3, 65])
+def test_rollout_cost_device_equals_host(M, integ):
+    """B = 5, N = 4: M = 3 (several lanes per workgroup) and 65 (one lane per workgroup); io.shape_id other than
+    the handle's against a handle that holds those ids; U 8 bytes past a 16-byte boundary (scalar loads)."""
+    import torch
+    B, N = 5, 4
+    s, shapes = _solver(B, N)
+    s2, _ = _solver(B, N)
+    x0, sid, yref, ye = _data(B, N, 31, shapes)
+    U = _rand_U(np.random.default_rng(100 + M), (B, M, N))
+    ids2 = (np.arange(B) + 1) % 4
+    s2.set_shape_ids(ids2)
+    kw = dict(integrator=integ, yref=yref, yref_e=ye, want_viol=True, want_x_end=True)
+    try:
+        host = s.rollout_cost(x0, U, **kw)
+        dev = _rollout_device(s, M, integ, x0, U, yref, ye)
+        for h, d in zip(host, dev):
+            assert np.array_equal(h, d)
+        host2 = s2.rollout_cost(x0, U, **kw)
+        assert not np.array_equal(host2[0], host[0])                 # the other shapes give other costs
+        for h, d in zip(host2, _rollout_device(s, M, integ, x0, U, yref, ye, sid=ids2)):
+            assert np.array_equal(h, d)
+        buf = torch.zeros(U.size + 1, dtype=torch.float64, device=torch.device("cuda", 0))
+        assert buf.data_ptr() % 16 == 0
+        Uo = buf[1:]
+        Uo.copy_(_dev(U).reshape(-1))
+        assert Uo.data_ptr() % 16 == 8
+        for a, d in zip(dev, _rollout_device(s, M, integ, x0, U, yref, ye, U_dev=Uo)):
+            assert np.array_equal(a, d)
+    finally:
+        s.close()
+        s2.close()
+
+
+@pytest.mark.parametrize("grid", [(3, 5), (9, 8)])
+def test_cost_landscape_device_equals_host(grid):
+    """B = 5, N = 4, grids of 15 and of 72 points (more than one wave); U_tail given, and NULL after a solve (the
+    handle's iterate and staged references); the surface requested, and NULL."""
+    import torch
+    from uclv_qs_pushing_matlab_amd._lib import LandscapeIO
+    B, N = 5, 4
+    s, shapes = _solver(B, N, sqp_iters=3)
+    x0, sid, yref, ye = _data(B, N, 32, shapes)
+    tail = _rand_U(np.random.default_rng(33), (B, N))
+    un, ut = np.linspace(0.0, 0.03, grid[0]), np.linspace(-0.05, 0.05, grid[1])
+    try:
+        s.set_reference_trajectory(straight_traj())
+        s.controller_solve(config2_x0(B, 34), 1)
+        for integ in ("euler", "rk4"):
+            for given in (True, False):
+                for surface in (True, False):
+                    kw = dict(U_tail=tail, yref=yref, yref_e=ye) if given else {}
+                    host = s.cost_landscape(x0, un, ut, integrator=integ, want_surface=surface, **kw)
+                    ins = dict(x0=_dev(x0), un_grid=_dev(un), ut_grid=_dev(ut))
+                    if given:
+                        ins.update(U_tail=_dev(tail), yref=_dev(yref), yref_e=_dev(ye))
+                    outs = dict(u_min=_dev_out((B, 2)), cost_min=_dev_out(B), idx_min=_dev_out(B, np.int32))
+                    if surface:
+                        outs["cost"] = _dev_out((B,) + grid)
+                    io = LandscapeIO()
+                    for k, t in {**ins, **outs}.items():
+                        setattr(io, k, t.data_ptr())
+                    io.n_un, io.n_ut = grid
+                    torch.cuda.synchronize()
+                    s.cost_landscape_device(io, integrator=integ)
+                    s.synchronize()
+                    assert host["cost"] is None if not surface else np.array_equal(host["cost"], outs["cost"].cpu().numpy())
+                    for k in ("u_min", "cost_min", "idx_min"):
+                        assert np.array_equal(host[k], outs[k].cpu().numpy()), (k, integ, given, surface)
+    finally:
+        s.close()

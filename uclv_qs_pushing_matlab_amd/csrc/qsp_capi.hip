@@ -47,6 +47,8 @@ struct DevBuf {
     T* as() const { return static_cast<T*>(p); }
 };
 
+constexpr int STAGE_POOL = 12;   // most host arrays of one call (qsp_cost_landscape, qsp_qp_solve: 10)
+
 struct qsp_solver {
     qsp_options o;
     SolveParams p;
@@ -57,19 +59,19 @@ struct qsp_solver {
     DevBuf shapes, shape_id, x0, yref, yref_e, X, U, PI, Xo, Uo, PIo, u0, status, sqp_iter, qp_iter, qp_capped, qp_stalled, cost;
     DevBuf warm_valid, traj, index_time;
     // delay compensation (set_delay_comp, NMPC_controller.m:106-110): delay_buff_comp columns and the
-    // per-lane controller input buffer u_buff_contr (B x D x 2, column 0 newest); closed-loop state
+    // per-lane controller input buffer u_buff_contr (B x D x 2, column 0 newest); closed-loop state:
+    // the plant's buffer and state, the disturbance amplitudes, the noise (n_steps x B x 4) and the
+    // logs of a run with trajectories (B x n_steps: X_sim, X_traj, U_traj, status_traj)
     int32_t D = 0;
-    DevBuf ubc, ubp, cl_x, cl_xsim, cl_amp;
+    DevBuf ubc, ubp, cl_x, cl_amp, cl_noise, cl_xsim, cl_xtraj, cl_utraj, cl_straj;
     // the plant's own model (qsp_set_plant_*): shape table, ids, per-lane mu_sp / c_ellipse; the closed
     // loop's metric accumulators (qsp_closed_loop_metrics)
     int n_pshapes = 0;
     bool has_pids = false, has_pmu = false, has_pc = false;
     DevBuf pshapes, pshape_id, pmu, pc, cl_metrics;
     DevBuf wX, wU, wx0, wlin, wnlp, wdone, wres, wqp, wperm, wnit, whist, wadj, wadjv;
-    DevBuf scratch[12];
-    DevBuf ro[12];                  // staging of the rollout entry points' host arrays
-    DevBuf ol[10];                  // staging of qsp_eval_modes / qsp_get_modes / qsp_open_loop's host arrays
-    DevBuf ol_ring;                 // qsp_open_loop's plant delay buffer (clipped u_t of the last D steps)
+    DevBuf pool[STAGE_POOL];        // device images of one call's host arrays, handed out by Staging
+    DevBuf ol_ring;                // qsp_open_loop's plant delay buffer (clipped u_t of the last D steps)
     bool solved = false;            // wU holds a solve's iterate (qsp_cost_landscape with U_tail = NULL)
     int32_t T = 0;
     bool have_traj = false;
@@ -247,17 +249,46 @@ static int run_timed(qsp_solver* s, const SolveArgs& a) {
     return QSP_OK;
 }
 
-template <class T>
-static int stage_in(qsp_solver* s, DevBuf& b, const T* src, size_t count) {
-    HIPCHK(b.ensure(count * sizeof(T)));
-    HIPCHK(hipMemcpyAsync(b.p, src, count * sizeof(T), hipMemcpyHostToDevice, s->stream));
-    return QSP_OK;
-}
-template <class T>
-static int stage_out(qsp_solver* s, T* dst, DevBuf& b, size_t count) {
-    HIPCHK(hipMemcpyAsync(dst, b.p, count * sizeof(T), hipMemcpyDeviceToHost, s->stream));
-    return QSP_OK;
-}
+// The device images of one call's host arrays, one object per call: the handle's grow-only pool handed
+// out in call order, all copies on the handle's stream.  in() copies a host array in, out() reserves the
+// image of one that finish() copies back; a null host pointer (an optional array) gives a null device
+// pointer.  The first error stays in err (and in qsp_last_error) and turns every later step into a no-op,
+// so a caller checks once before its launch and returns finish().
+struct Staging {
+    qsp_solver* s;
+    int used = 0, n_out = 0, err = QSP_OK;
+    struct { void* host; const void* dev; size_t bytes; } outs[STAGE_POOL];
+
+    explicit Staging(qsp_solver* s_) : s(s_) {}
+    void check(hipError_t e, const char* what) {
+        if (e != hipSuccess && !err) err = fail(QSP_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+    }
+    void* take(size_t bytes) {
+        if (!err && used == STAGE_POOL) err = fail(QSP_ERR_STATE, "staging pool exhausted: more than STAGE_POOL arrays in one call");
+        if (err) return nullptr;
+        DevBuf& b = s->pool[used++];
+        check(b.ensure(bytes), "staging hipMalloc");
+        return err ? nullptr : b.p;
+    }
+    template <class T>
+    T* in(const T* host, size_t count) {
+        void* d = host ? take(count * sizeof(T)) : nullptr;
+        if (d) check(hipMemcpyAsync(d, host, count * sizeof(T), hipMemcpyHostToDevice, s->stream), "staging copy in");
+        return static_cast<T*>(d);
+    }
+    template <class T>
+    T* out(T* host, size_t count) {
+        void* d = host ? take(count * sizeof(T)) : nullptr;
+        if (d) outs[n_out++] = {host, d, count * sizeof(T)};   // n_out <= used <= STAGE_POOL
+        return static_cast<T*>(d);
+    }
+    int finish() {
+        for (int q = 0; q < n_out && !err; ++q)
+            check(hipMemcpyAsync(outs[q].host, outs[q].dev, outs[q].bytes, hipMemcpyDeviceToHost, s->stream), "staging copy out");
+        if (!err) check(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
+        return err;
+    }
+};
 
 static int check_ids(qsp_solver* s, int32_t n, const int32_t* ids) {
     if (s->n_shapes < 1) return fail(QSP_ERR_STATE, "no shapes set");
@@ -266,38 +297,10 @@ static int check_ids(qsp_solver* s, int32_t n, const int32_t* ids) {
     return QSP_OK;
 }
 
-__global__ void stage_yref_kernel(const double* traj, int T, int per_lane, const int32_t* index_time, int offset,
-                                  int D, int B, int N, double* yref, double* yref_e) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= B) return;
-    if (per_lane) traj += (size_t)i * T * 6;
-    // get_y_ref (NMPC_controller.m:307-313): column index_time+k (1-based) of the table as
-    // set_reference_trajectory (:425-431) builds it -- D = delay_buff_comp zero columns prepended,
-    // their u_t-reference row copied from the first real column -- clamped to the last column
-    for (int k = 0; k < N; ++k) {
-        int idx = index_time[i] + offset + k;
-        if (idx > T + D) idx = T + D;
-        if (idx < 1) idx = 1;
-        double* out = yref + ((size_t)i * N + k) * 6;
-        if (idx <= D) {
-            for (int c = 0; c < 5; ++c) out[c] = 0.0;
-            out[5] = traj[5];
-        } else {
-            for (int c = 0; c < 6; ++c) out[c] = traj[(size_t)(idx - D - 1) * 6 + c];
-        }
-    }
-    // terminal reference = last stage reference (:348)
-    for (int c = 0; c < 4; ++c) yref_e[(size_t)i * 4 + c] = yref[((size_t)i * N + N - 1) * 6 + c];
-}
-
 // y_ref staging for the controller step at index_time + offset
 static hipError_t launch_controller_step(qsp_solver* s, int offset) {
-    const size_t B = s->o.batch;
-    hipLaunchKernelGGL(stage_yref_kernel, dim3((unsigned)((B + 127) / 128)), dim3(128), 0, s->stream,
-                       s->traj.as<double>(), s->T, s->traj_per_lane ? 1 : 0, s->index_time.as<int32_t>(), offset,
-                       s->D, (int)B, s->o.N,
-                       s->yref.as<double>(), s->yref_e.as<double>());
-    return hipGetLastError();
+    return launch_stage_yref(s->traj.as<double>(), s->T, s->traj_per_lane ? 1 : 0, s->index_time.as<int32_t>(), offset,
+                             s->D, s->o.batch, s->o.N, s->yref.as<double>(), s->yref_e.as<double>(), s->stream);
 }
 
 // NMPC_controller.solve arguments: warm buffers updated in place (each instance reads its
@@ -482,7 +485,7 @@ int qsp_create(const qsp_options* o, qsp_solver** out) {
 int qsp_destroy(qsp_solver* s) {
     if (!s) return QSP_OK;
     (void)hipSetDevice(s->o.device);
-    DevBuf* bufs[] = {&s->ubc, &s->ubp, &s->cl_x, &s->cl_xsim, &s->cl_amp,
+    DevBuf* bufs[] = {&s->ubc, &s->ubp, &s->cl_x, &s->cl_amp, &s->cl_noise, &s->cl_xsim, &s->cl_xtraj, &s->cl_utraj, &s->cl_straj,
                       &s->pshapes, &s->pshape_id, &s->pmu, &s->pc, &s->cl_metrics,
                       &s->shapes, &s->shape_id, &s->x0, &s->yref, &s->yref_e, &s->X, &s->U, &s->PI, &s->Xo,
                       &s->Uo, &s->PIo, &s->u0, &s->status, &s->sqp_iter, &s->qp_iter, &s->qp_capped, &s->qp_stalled, &s->cost,
@@ -490,9 +493,7 @@ int qsp_destroy(qsp_solver* s) {
                       &s->traj, &s->index_time, &s->wX, &s->wU, &s->wx0, &s->wlin, &s->wnlp, &s->wdone, &s->wres, &s->wqp, &s->wperm, &s->wnit,
                       &s->whist, &s->wadj, &s->wadjv};
     for (DevBuf* b : bufs) b->release();
-    for (auto& b : s->scratch) b.release();
-    for (auto& b : s->ro) b.release();
-    for (auto& b : s->ol) b.release();
+    for (auto& b : s->pool) b.release();
     s->ol_ring.release();
     for (hipEvent_t e : s->kev) (void)hipEventDestroy(e);
     if (s->ev0) (void)hipEventDestroy(s->ev0);
@@ -898,16 +899,13 @@ int qsp_gen_straight_lines(qsp_solver* s, const double* x0, const double* xf, do
     // MATLAB t0:Ts:tf
     const int32_t T = (int32_t)std::floor((tf - t0) / s->o.Ts + 1e-9) + 1;
     HIPCHK(hipSetDevice(s->o.device));
-    DevBuf& d0 = s->scratch[0];
-    DevBuf& d1 = s->scratch[1];
-    HIPCHK(d0.ensure(B * 3 * 8));
-    HIPCHK(d1.ensure(B * 3 * 8));
-    HIPCHK(hipMemcpyAsync(d0.p, x0, B * 3 * 8, hipMemcpyHostToDevice, s->stream));
-    HIPCHK(hipMemcpyAsync(d1.p, xf, B * 3 * 8, hipMemcpyHostToDevice, s->stream));
+    Staging st(s);
+    const double* d0 = st.in(x0, B * 3);
+    const double* d1 = st.in(xf, B * 3);
+    if (st.err) return st.err;
     HIPCHK(s->traj.ensure(B * (size_t)T * 6 * 8));
-    HIPCHK(launch_straight_lines((int)B, T, d0.as<double>(), d1.as<double>(), t0, tf, s->o.Ts, auto_angle,
-                                 s->traj.as<double>(), s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
+    HIPCHK(launch_straight_lines((int)B, T, d0, d1, t0, tf, s->o.Ts, auto_angle, s->traj.as<double>(), s->stream));
+    if (st.finish()) return st.err;
     s->T = T;
     s->have_traj = true;
     s->traj_per_lane = true;
@@ -989,16 +987,13 @@ int qsp_delay_buffer_sim(qsp_solver* s, const double* x, double* x_sim) {
     if (s->n_shapes < 1) return fail(QSP_ERR_STATE, "qsp_delay_buffer_sim: no shapes set");
     const size_t B = s->o.batch;
     HIPCHK(hipSetDevice(s->o.device));
-    HIPCHK(s->cl_x.ensure(B * 4 * 8));
-    HIPCHK(s->cl_xsim.ensure(B * 4 * 8));
-    HIPCHK(hipMemcpyAsync(s->cl_x.p, x, B * 4 * 8, hipMemcpyHostToDevice, s->stream));
+    Staging st(s);
     ClosedLoopArgs a = cl_args(s);
-    a.x = s->cl_x.as<double>();
-    a.xs = s->cl_xsim.as<double>();
+    a.x = st.in(x, B * 4);
+    a.xs = st.out(x_sim, B * 4);
+    if (st.err) return st.err;
     HIPCHK(launch_delay_sim(a, s->stream));
-    HIPCHK(hipMemcpyAsync(x_sim, s->cl_xsim.p, B * 4 * 8, hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    return QSP_OK;
+    return st.finish();
 }
 
 int qsp_delay_buffer_push(qsp_solver* s, const double* u) {
@@ -1023,7 +1018,7 @@ int qsp_delay_buffer_push(qsp_solver* s, const double* u) {
 static_assert(CL_NMETRICS == QSP_CL_NMETRICS, "metric columns of the kernel and of the header");
 
 // closed_loop_matlab's loop (helper.m:195-322) on the stream, for both front ends: with trajectories
-// (qsp_closed_loop_ex: B x n_steps logs in scratch 9, 10, 11 and 4) or with the per-lane metric
+// (qsp_closed_loop_ex: B x n_steps logs in s->cl_xtraj, cl_utraj, cl_straj and cl_xsim) or with the per-lane metric
 // accumulators alone (qsp_closed_loop_metrics: s->cl_metrics, nothing of size B x n_steps).  The
 // final plant state is left in s->cl_x, the last status in s->status; the caller copies out and
 // synchronises.
@@ -1040,11 +1035,7 @@ static int closed_loop_run(qsp_solver* s, const char* who, const qsp_closed_loop
     const size_t B = s->o.batch, T = (size_t)n_steps;
     const int Dp = (int)std::ceil(plant_delay / s->o.Ts);   // delay_buff_plant (helper.m:211)
     HIPCHK(hipSetDevice(s->o.device));
-    DevBuf& dX = s->scratch[9];
-    DevBuf& dU = s->scratch[10];
-    DevBuf& dS = s->scratch[11];
-    DevBuf& dN = s->scratch[3];
-    DevBuf& dXs = s->scratch[4];
+    DevBuf &dX = s->cl_xtraj, &dU = s->cl_utraj, &dS = s->cl_straj, &dN = s->cl_noise, &dXs = s->cl_xsim;
     if (want_traj) {
         HIPCHK(dX.ensure(B * (T + 1) * 4 * 8));
         HIPCHK(dU.ensure(B * T * 2 * 8));
@@ -1123,10 +1114,10 @@ int qsp_closed_loop_ex(qsp_solver* s, const qsp_closed_loop_opts* o, const doubl
     const int r = closed_loop_run(s, "qsp_closed_loop", o, x0, index0, n_steps, noise, true, X_sim != nullptr, false);
     if (r) return r;
     const size_t B = s->o.batch, T = (size_t)n_steps;
-    HIPCHK(hipMemcpyAsync(X_traj, s->scratch[9].p, B * (T + 1) * 4 * 8, hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(hipMemcpyAsync(U_traj, s->scratch[10].p, B * T * 2 * 8, hipMemcpyDeviceToHost, s->stream));
-    if (X_sim) HIPCHK(hipMemcpyAsync(X_sim, s->scratch[4].p, B * T * 4 * 8, hipMemcpyDeviceToHost, s->stream));
-    if (status_traj) HIPCHK(hipMemcpyAsync(status_traj, s->scratch[11].p, B * T * 4, hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(hipMemcpyAsync(X_traj, s->cl_xtraj.p, B * (T + 1) * 4 * 8, hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(hipMemcpyAsync(U_traj, s->cl_utraj.p, B * T * 2 * 8, hipMemcpyDeviceToHost, s->stream));
+    if (X_sim) HIPCHK(hipMemcpyAsync(X_sim, s->cl_xsim.p, B * T * 4 * 8, hipMemcpyDeviceToHost, s->stream));
+    if (status_traj) HIPCHK(hipMemcpyAsync(status_traj, s->cl_straj.p, B * T * 4, hipMemcpyDeviceToHost, s->stream));
     return closed_loop_done(s);
 }
 
@@ -1155,16 +1146,13 @@ int qsp_reproject_contact(qsp_solver* s, int32_t n, const int32_t* sid, const do
     int r = check_ids(s, n, sid);
     if (r) return r;
     HIPCHK(hipSetDevice(s->o.device));
-    auto& sc = s->scratch;
-    if ((r = stage_in(s, sc[0], sid, n)) || (r = stage_in(s, sc[1], px, n)) || (r = stage_in(s, sc[2], py, n)) ||
-        (r = stage_in(s, sc[5], s0, n)))
-        return r;
-    HIPCHK(sc[6].ensure((size_t)n * 8));
-    HIPCHK(launch_reproject(s->shapes.as<ShapeDev>(), s->n_shapes, sc[0].as<int32_t>(), n, sc[1].as<double>(),
-                            sc[2].as<double>(), sc[5].as<double>(), sc[6].as<double>(), s->stream));
-    if ((r = stage_out(s, s_out, sc[6], (size_t)n))) return r;
-    HIPCHK(hipStreamSynchronize(s->stream));
-    return QSP_OK;
+    Staging st(s);
+    const int32_t* d_sid = st.in(sid, n);
+    const double *d_px = st.in(px, n), *d_py = st.in(py, n), *d_s0 = st.in(s0, n);
+    double* d_s = st.out(s_out, n);
+    if (st.err) return st.err;
+    HIPCHK(launch_reproject(s->shapes.as<ShapeDev>(), s->n_shapes, d_sid, n, d_px, d_py, d_s0, d_s, s->stream));
+    return st.finish();
 }
 
 // ------------------------------------------------------ device fast path
@@ -1276,17 +1264,14 @@ int qsp_eval_spline(qsp_solver* s, int32_t n, const int32_t* sid, const double* 
     int r = check_ids(s, n, sid);
     if (r) return r;
     HIPCHK(hipSetDevice(s->o.device));
-    auto& sc = s->scratch;
-    if ((r = stage_in(s, sc[0], sid, n)) || (r = stage_in(s, sc[1], sig, n))) return r;
-    HIPCHK(sc[2].ensure((size_t)n * 16)); HIPCHK(sc[3].ensure((size_t)n * 16));
-    HIPCHK(sc[4].ensure((size_t)n * 16)); HIPCHK(sc[5].ensure((size_t)n * 8));
-    HIPCHK(launch_spline(s->shapes.as<ShapeDev>(), sc[0].as<int32_t>(), n, sc[1].as<double>(), sc[2].as<double>(),
-                         sc[3].as<double>(), sc[4].as<double>(), sc[5].as<double>(), s->stream));
-    if ((r = stage_out(s, C, sc[2], (size_t)2 * n)) || (r = stage_out(s, D, sc[3], (size_t)2 * n)) ||
-        (r = stage_out(s, Dd, sc[4], (size_t)2 * n)) || (r = stage_out(s, kappa, sc[5], (size_t)n)))
-        return r;
-    HIPCHK(hipStreamSynchronize(s->stream));
-    return QSP_OK;
+    Staging st(s);
+    const int32_t* d_sid = st.in(sid, n);
+    const double* d_sig = st.in(sig, n);
+    double *dC = st.out(C, (size_t)2 * n), *dD = st.out(D, (size_t)2 * n), *dDd = st.out(Dd, (size_t)2 * n);
+    double* dk = st.out(kappa, n);
+    if (st.err) return st.err;
+    HIPCHK(launch_spline(s->shapes.as<ShapeDev>(), d_sid, n, d_sig, dC, dD, dDd, dk, s->stream));
+    return st.finish();
 }
 
 int qsp_eval_dynamics(qsp_solver* s, int32_t n, const int32_t* sid, const double* x, const double* u, double* f,
@@ -1295,16 +1280,13 @@ int qsp_eval_dynamics(qsp_solver* s, int32_t n, const int32_t* sid, const double
     int r = check_ids(s, n, sid);
     if (r) return r;
     HIPCHK(hipSetDevice(s->o.device));
-    auto& sc = s->scratch;
-    if ((r = stage_in(s, sc[0], sid, n)) || (r = stage_in(s, sc[1], x, (size_t)4 * n)) ||
-        (r = stage_in(s, sc[2], u, (size_t)2 * n)))
-        return r;
-    HIPCHK(sc[3].ensure((size_t)n * 32)); HIPCHK(sc[4].ensure((size_t)n * 24 * 8));
-    HIPCHK(launch_dynamics(s->shapes.as<ShapeDev>(), sc[0].as<int32_t>(), n, sc[1].as<double>(), sc[2].as<double>(),
-                           sc[3].as<double>(), sc[4].as<double>(), s->stream));
-    if ((r = stage_out(s, f, sc[3], (size_t)4 * n)) || (r = stage_out(s, J, sc[4], (size_t)24 * n))) return r;
-    HIPCHK(hipStreamSynchronize(s->stream));
-    return QSP_OK;
+    Staging st(s);
+    const int32_t* d_sid = st.in(sid, n);
+    const double *dx = st.in(x, (size_t)4 * n), *du = st.in(u, (size_t)2 * n);
+    double *df = st.out(f, (size_t)4 * n), *dJ = st.out(J, (size_t)24 * n);
+    if (st.err) return st.err;
+    HIPCHK(launch_dynamics(s->shapes.as<ShapeDev>(), d_sid, n, dx, du, df, dJ, s->stream));
+    return st.finish();
 }
 
 int qsp_eval_rk4(qsp_solver* s, int32_t n, const int32_t* sid, double h, const double* x, const double* u, double* xn,
@@ -1313,18 +1295,13 @@ int qsp_eval_rk4(qsp_solver* s, int32_t n, const int32_t* sid, double h, const d
     int r = check_ids(s, n, sid);
     if (r) return r;
     HIPCHK(hipSetDevice(s->o.device));
-    auto& sc = s->scratch;
-    if ((r = stage_in(s, sc[0], sid, n)) || (r = stage_in(s, sc[1], x, (size_t)4 * n)) ||
-        (r = stage_in(s, sc[2], u, (size_t)2 * n)))
-        return r;
-    HIPCHK(sc[3].ensure((size_t)n * 32)); HIPCHK(sc[4].ensure((size_t)n * 128)); HIPCHK(sc[5].ensure((size_t)n * 64));
-    HIPCHK(launch_rk4(s->shapes.as<ShapeDev>(), sc[0].as<int32_t>(), n, h, sc[1].as<double>(), sc[2].as<double>(),
-                      sc[3].as<double>(), sc[4].as<double>(), sc[5].as<double>(), s->stream));
-    if ((r = stage_out(s, xn, sc[3], (size_t)4 * n)) || (r = stage_out(s, A, sc[4], (size_t)16 * n)) ||
-        (r = stage_out(s, B, sc[5], (size_t)8 * n)))
-        return r;
-    HIPCHK(hipStreamSynchronize(s->stream));
-    return QSP_OK;
+    Staging st(s);
+    const int32_t* d_sid = st.in(sid, n);
+    const double *dx = st.in(x, (size_t)4 * n), *du = st.in(u, (size_t)2 * n);
+    double *dxn = st.out(xn, (size_t)4 * n), *dA = st.out(A, (size_t)16 * n), *dB = st.out(B, (size_t)8 * n);
+    if (st.err) return st.err;
+    HIPCHK(launch_rk4(s->shapes.as<ShapeDev>(), d_sid, n, h, dx, du, dxn, dA, dB, s->stream));
+    return st.finish();
 }
 
 int qsp_eval_vbound(qsp_solver* s, int32_t n, const int32_t* sid, const double* sv, double* vb) {
@@ -1332,14 +1309,13 @@ int qsp_eval_vbound(qsp_solver* s, int32_t n, const int32_t* sid, const double* 
     int r = check_ids(s, n, sid);
     if (r) return r;
     HIPCHK(hipSetDevice(s->o.device));
-    auto& sc = s->scratch;
-    if ((r = stage_in(s, sc[0], sid, n)) || (r = stage_in(s, sc[1], sv, n))) return r;
-    HIPCHK(sc[2].ensure((size_t)n * 8));
-    HIPCHK(launch_vbound(s->shapes.as<ShapeDev>(), sc[0].as<int32_t>(), n, s->p.cp, sc[1].as<double>(),
-                         sc[2].as<double>(), s->stream));
-    if ((r = stage_out(s, vb, sc[2], (size_t)n))) return r;
-    HIPCHK(hipStreamSynchronize(s->stream));
-    return QSP_OK;
+    Staging st(s);
+    const int32_t* d_sid = st.in(sid, n);
+    const double* ds = st.in(sv, n);
+    double* dvb = st.out(vb, n);
+    if (st.err) return st.err;
+    HIPCHK(launch_vbound(s->shapes.as<ShapeDev>(), d_sid, n, s->p.cp, ds, dvb, s->stream));
+    return st.finish();
 }
 
 int qsp_qp_solve(qsp_solver* s, int32_t nb, const double* A, const double* B, const double* b, const double* H,
@@ -1397,31 +1373,25 @@ int qsp_qp_solve(qsp_solver* s, int32_t nb, const double* A, const double* B, co
         x0[(size_t)l * 4 + 3] += X[(size_t)l * (N + 1) * 4 + 3];
     }
     HIPCHK(hipSetDevice(s->o.device));
-    auto& sc = s->scratch;
-    int r;
-    if ((r = stage_in(s, sc[0], lin.data(), lin.size())) || (r = stage_in(s, sc[1], X.data(), X.size())) ||
-        (r = stage_in(s, sc[2], U.data(), U.size())) || (r = stage_in(s, sc[3], x0.data(), x0.size())))
-        return r;
-    HIPCHK(sc[4].ensure((size_t)nb * (N + 1) * 32)); HIPCHK(sc[5].ensure((size_t)nb * N * 16));
-    HIPCHK(sc[6].ensure((size_t)nb * N * 32)); HIPCHK(sc[7].ensure((size_t)nb * N * 48));
-    HIPCHK(sc[8].ensure((size_t)nb * 4));
-    HIPCHK(sc[9].ensure((size_t)nb * 4));
+    Staging st(s);
+    std::vector<int32_t> qst((size_t)nb);
     SolveArgs a;
     std::memset(&a, 0, sizeof a);
     a.p = p;
     a.B = nb;
-    a.wlin = sc[0].as<double>(); a.wX = sc[1].as<double>(); a.wU = sc[2].as<double>(); a.wx0 = sc[3].as<double>();
-    a.qp_dx = sc[4].as<double>(); a.qp_du = sc[5].as<double>(); a.PI_out = sc[6].as<double>();
-    a.qp_lam = sc[7].as<double>(); a.qp_iter = sc[8].as<int32_t>();
-    a.qp_capped = sc[9].as<int32_t>();
+    a.wlin = st.in(lin.data(), lin.size());
+    a.wX = st.in(X.data(), X.size());
+    a.wU = st.in(U.data(), U.size());
+    a.wx0 = st.in(x0.data(), x0.size());
+    a.qp_dx = st.out(dx, (size_t)nb * (N + 1) * 4);
+    a.qp_du = st.out(du, (size_t)nb * N * 2);
+    a.PI_out = st.out(pi, (size_t)nb * N * 4);
+    a.qp_lam = st.out(lam, (size_t)nb * N * 6);
+    a.qp_iter = st.out(iters, (size_t)nb);
+    a.qp_capped = st.out(qst.data(), (size_t)nb);
+    if (st.err) return st.err;
     HIPCHK(launch_qp(a, s->S, s->stream));
-    if ((r = stage_out(s, dx, sc[4], (size_t)nb * (N + 1) * 4)) || (r = stage_out(s, du, sc[5], (size_t)nb * N * 2)) ||
-        (r = stage_out(s, pi, sc[6], (size_t)nb * N * 4)) || (r = stage_out(s, lam, sc[7], (size_t)nb * N * 6)) ||
-        (r = stage_out(s, iters, sc[8], (size_t)nb)))
-        return r;
-    std::vector<int32_t> qst(qp_status ? (size_t)nb : 0);
-    if (qp_status && (r = stage_out(s, qst.data(), sc[9], (size_t)nb))) return r;
-    HIPCHK(hipStreamSynchronize(s->stream));
+    if (st.finish()) return st.err;
     if (qp_status) {
         for (int l = 0; l < nb; ++l) {
             bool fin = true;
@@ -1473,150 +1443,133 @@ static int rollout_args(qsp_solver* s, const qsp_rollout_opts* o, const char* wh
     return QSP_OK;
 }
 
+// Each host entry and its _device twin run one function: the checks, io onto the kernel's argument block,
+// the launch.  host: io holds host arrays, which go through the staging pool and are copied back before
+// the return, on the handle's stream; else device arrays, used as they are, asynchronous on `stream`.
+static const char* missing(bool host) { return host ? ": null argument" : ": missing device pointer"; }
+static hipStream_t stream_of(qsp_solver* s, bool host, void* stream) {
+    return (host || !stream) ? s->stream : (hipStream_t)stream;
+}
+
+static int rollout_cost_run(qsp_solver* s, const qsp_rollout_opts* opts, const char* who, bool host, int32_t M,
+                            const qsp_rollout_io* io, void* stream) {
+    RolloutArgs a;
+    const int r = rollout_args(s, opts, who, a);
+    if (r) return r;
+    const std::string w(who);
+    if (!io || !io->x0 || !io->U || !io->cost) return fail(QSP_ERR_ARG, w + missing(host));
+    if (M < 1) return fail(QSP_ERR_ARG, w + ": M must be >= 1");
+    HIPCHK(hipSetDevice(s->o.device));
+    qsp_rollout_io d = *io;
+    Staging st(s);
+    if (host) {
+        const size_t B = s->o.batch, N = s->o.N, BM = B * (size_t)M;
+        d.x0 = st.in(io->x0, B * 4);
+        d.U = st.in(io->U, BM * N * 2);
+        d.yref = st.in(io->yref, B * N * 6);
+        d.yref_e = st.in(io->yref_e, B * 4);
+        d.cost = st.out(io->cost, BM);
+        d.viol = st.out(io->viol, BM);
+        d.x_end = st.out(io->x_end, BM * 4);
+        if (st.err) return st.err;
+    }
+    a.M = M;
+    a.x0 = d.x0;
+    a.U = d.U;
+    if (d.yref) a.yref = d.yref;
+    if (d.yref_e) a.yref_e = d.yref_e;
+    if (d.shape_id) a.shape_id = d.shape_id;
+    a.cost = d.cost;
+    a.viol = d.viol;
+    a.x_end = d.x_end;
+    HIPCHK(launch_rollout_cost(a, stream_of(s, host, stream)));
+    return host ? st.finish() : QSP_OK;
+}
+
 int qsp_rollout_cost(qsp_solver* s, const qsp_rollout_opts* opts, int32_t M, const double* x0, const double* U,
                      const double* yref, const double* yref_e, double* cost, double* viol, double* x_end) {
-    RolloutArgs a;
-    int r = rollout_args(s, opts, "qsp_rollout_cost", a);
-    if (r) return r;
-    if (!x0 || !U || !cost) return fail(QSP_ERR_ARG, "qsp_rollout_cost: null argument");
-    if (M < 1) return fail(QSP_ERR_ARG, "qsp_rollout_cost: M must be >= 1");
-    const size_t B = s->o.batch, N = s->o.N, BM = B * (size_t)M;
-    HIPCHK(hipSetDevice(s->o.device));
-    auto& b = s->ro;
-    if ((r = stage_in(s, b[0], x0, B * 4)) || (r = stage_in(s, b[1], U, BM * N * 2))) return r;
-    if (yref && (r = stage_in(s, b[2], yref, B * N * 6))) return r;
-    if (yref_e && (r = stage_in(s, b[3], yref_e, B * 4))) return r;
-    HIPCHK(b[4].ensure(BM * 8));
-    if (viol) HIPCHK(b[5].ensure(BM * 8));
-    if (x_end) HIPCHK(b[6].ensure(BM * 4 * 8));
-    a.M = M;
-    a.x0 = b[0].as<double>();
-    a.U = b[1].as<double>();
-    if (yref) a.yref = b[2].as<double>();
-    if (yref_e) a.yref_e = b[3].as<double>();
-    a.cost = b[4].as<double>();
-    a.viol = viol ? b[5].as<double>() : nullptr;
-    a.x_end = x_end ? b[6].as<double>() : nullptr;
-    HIPCHK(launch_rollout_cost(a, s->stream));
-    if ((r = stage_out(s, cost, b[4], BM))) return r;
-    if (viol && (r = stage_out(s, viol, b[5], BM))) return r;
-    if (x_end && (r = stage_out(s, x_end, b[6], BM * 4))) return r;
-    HIPCHK(hipStreamSynchronize(s->stream));
-    return QSP_OK;
+    const qsp_rollout_io io = {x0, U, yref, yref_e, nullptr, cost, viol, x_end};
+    return rollout_cost_run(s, opts, "qsp_rollout_cost", true, M, &io, nullptr);
 }
 
 int qsp_rollout_cost_device(qsp_solver* s, const qsp_rollout_opts* opts, int32_t M, const qsp_rollout_io* io,
                             void* stream) {
+    return rollout_cost_run(s, opts, "qsp_rollout_cost_device", false, M, io, stream);
+}
+
+static int cost_landscape_run(qsp_solver* s, const qsp_rollout_opts* opts, const char* who, bool host,
+                              const qsp_landscape_io* io, void* stream) {
     RolloutArgs a;
-    int r = rollout_args(s, opts, "qsp_rollout_cost_device", a);
+    const int r = rollout_args(s, opts, who, a);
     if (r) return r;
-    if (!io || !io->x0 || !io->U || !io->cost) return fail(QSP_ERR_ARG, "qsp_rollout_cost_device: missing device pointer");
-    if (M < 1) return fail(QSP_ERR_ARG, "qsp_rollout_cost_device: M must be >= 1");
+    const std::string w(who);
+    if (!io || !io->x0 || !io->un_grid || !io->ut_grid || !io->u_min || !io->cost_min)
+        return fail(QSP_ERR_ARG, w + missing(host));
+    if (io->n_un < 1 || io->n_ut < 1) return fail(QSP_ERR_ARG, w + ": empty grid");
+    if ((long long)io->n_un * io->n_ut > (1ll << 30)) return fail(QSP_ERR_ARG, w + ": more than 2^30 grid points");
+    if (!io->U_tail && !s->solved)
+        return fail(QSP_ERR_STATE, w + ": U_tail = NULL needs a solve (the last solution's tail)");
     HIPCHK(hipSetDevice(s->o.device));
-    a.M = M;
-    a.x0 = io->x0;
-    a.U = io->U;
-    if (io->yref) a.yref = io->yref;
-    if (io->yref_e) a.yref_e = io->yref_e;
-    if (io->shape_id) a.shape_id = io->shape_id;
-    a.cost = io->cost;
-    a.viol = io->viol;
-    a.x_end = io->x_end;
-    HIPCHK(launch_rollout_cost(a, stream ? (hipStream_t)stream : s->stream));
-    return QSP_OK;
+    qsp_landscape_io d = *io;
+    Staging st(s);
+    if (host) {
+        const size_t B = s->o.batch, N = s->o.N, G = (size_t)io->n_un * io->n_ut;
+        d.x0 = st.in(io->x0, B * 4);
+        d.U_tail = st.in(io->U_tail, B * N * 2);
+        d.un_grid = st.in(io->un_grid, (size_t)io->n_un);
+        d.ut_grid = st.in(io->ut_grid, (size_t)io->n_ut);
+        d.yref = st.in(io->yref, B * N * 6);
+        d.yref_e = st.in(io->yref_e, B * 4);
+        d.cost = st.out(io->cost, B * G);
+        d.u_min = st.out(io->u_min, B * 2);
+        d.cost_min = st.out(io->cost_min, B);
+        d.idx_min = st.out(io->idx_min, B);
+        if (st.err) return st.err;
+    }
+    a.x0 = d.x0;
+    a.U_tail = d.U_tail ? d.U_tail : s->wU.as<double>();   // the iterate epilogue_kernel reads
+    if (d.yref) a.yref = d.yref;
+    if (d.yref_e) a.yref_e = d.yref_e;
+    if (d.shape_id) a.shape_id = d.shape_id;
+    a.n_un = d.n_un;
+    a.n_ut = d.n_ut;
+    a.un_grid = d.un_grid;
+    a.ut_grid = d.ut_grid;
+    a.cost = d.cost;
+    a.u_min = d.u_min;
+    a.cost_min = d.cost_min;
+    a.idx_min = d.idx_min;
+    HIPCHK(launch_cost_landscape(a, stream_of(s, host, stream)));
+    return host ? st.finish() : QSP_OK;
 }
 
 int qsp_cost_landscape(qsp_solver* s, const qsp_rollout_opts* opts, const double* x0, const double* U_tail,
                        int32_t n_un, const double* un_grid, int32_t n_ut, const double* ut_grid, const double* yref,
                        const double* yref_e, double* cost, double* u_min, double* cost_min, int32_t* idx_min) {
-    RolloutArgs a;
-    int r = rollout_args(s, opts, "qsp_cost_landscape", a);
-    if (r) return r;
-    if (!x0 || !un_grid || !ut_grid || !u_min || !cost_min) return fail(QSP_ERR_ARG, "qsp_cost_landscape: null argument");
-    if (n_un < 1 || n_ut < 1) return fail(QSP_ERR_ARG, "qsp_cost_landscape: empty grid");
-    if ((long long)n_un * n_ut > (1ll << 30)) return fail(QSP_ERR_ARG, "qsp_cost_landscape: more than 2^30 grid points");
-    if (!U_tail && !s->solved)
-        return fail(QSP_ERR_STATE, "qsp_cost_landscape: U_tail = NULL needs a solve (the last solution's tail)");
-    const size_t B = s->o.batch, N = s->o.N, G = (size_t)n_un * n_ut;
-    HIPCHK(hipSetDevice(s->o.device));
-    auto& b = s->ro;
-    if ((r = stage_in(s, b[0], x0, B * 4)) || (r = stage_in(s, b[7], un_grid, (size_t)n_un)) ||
-        (r = stage_in(s, b[8], ut_grid, (size_t)n_ut)))
-        return r;
-    if (U_tail && (r = stage_in(s, b[1], U_tail, B * N * 2))) return r;
-    if (yref && (r = stage_in(s, b[2], yref, B * N * 6))) return r;
-    if (yref_e && (r = stage_in(s, b[3], yref_e, B * 4))) return r;
-    if (cost) HIPCHK(b[4].ensure(B * G * 8));
-    HIPCHK(b[9].ensure(B * 2 * 8));
-    HIPCHK(b[10].ensure(B * 8));
-    HIPCHK(b[11].ensure(B * 4));
-    a.x0 = b[0].as<double>();
-    a.U_tail = U_tail ? b[1].as<double>() : s->wU.as<double>();   // the iterate epilogue_kernel reads
-    if (yref) a.yref = b[2].as<double>();
-    if (yref_e) a.yref_e = b[3].as<double>();
-    a.n_un = n_un;
-    a.n_ut = n_ut;
-    a.un_grid = b[7].as<double>();
-    a.ut_grid = b[8].as<double>();
-    a.cost = cost ? b[4].as<double>() : nullptr;
-    a.u_min = b[9].as<double>();
-    a.cost_min = b[10].as<double>();
-    a.idx_min = b[11].as<int32_t>();
-    HIPCHK(launch_cost_landscape(a, s->stream));
-    if (cost && (r = stage_out(s, cost, b[4], B * G))) return r;
-    if ((r = stage_out(s, u_min, b[9], B * 2)) || (r = stage_out(s, cost_min, b[10], B))) return r;
-    if (idx_min && (r = stage_out(s, idx_min, b[11], B))) return r;
-    HIPCHK(hipStreamSynchronize(s->stream));
-    return QSP_OK;
+    const qsp_landscape_io io = {x0, U_tail, un_grid, ut_grid, yref, yref_e, nullptr, cost, u_min, cost_min, idx_min,
+                                 n_un, n_ut};
+    return cost_landscape_run(s, opts, "qsp_cost_landscape", true, &io, nullptr);
 }
 
 int qsp_cost_landscape_device(qsp_solver* s, const qsp_rollout_opts* opts, const qsp_landscape_io* io, void* stream) {
-    RolloutArgs a;
-    int r = rollout_args(s, opts, "qsp_cost_landscape_device", a);
-    if (r) return r;
-    if (!io || !io->x0 || !io->un_grid || !io->ut_grid || !io->u_min || !io->cost_min)
-        return fail(QSP_ERR_ARG, "qsp_cost_landscape_device: missing device pointer");
-    if (io->n_un < 1 || io->n_ut < 1) return fail(QSP_ERR_ARG, "qsp_cost_landscape_device: empty grid");
-    if ((long long)io->n_un * io->n_ut > (1ll << 30))
-        return fail(QSP_ERR_ARG, "qsp_cost_landscape_device: more than 2^30 grid points");
-    if (!io->U_tail && !s->solved)
-        return fail(QSP_ERR_STATE, "qsp_cost_landscape_device: U_tail = NULL needs a solve (the last solution's tail)");
-    HIPCHK(hipSetDevice(s->o.device));
-    a.x0 = io->x0;
-    a.U_tail = io->U_tail ? io->U_tail : s->wU.as<double>();
-    if (io->yref) a.yref = io->yref;
-    if (io->yref_e) a.yref_e = io->yref_e;
-    if (io->shape_id) a.shape_id = io->shape_id;
-    a.n_un = io->n_un;
-    a.n_ut = io->n_ut;
-    a.un_grid = io->un_grid;
-    a.ut_grid = io->ut_grid;
-    a.cost = io->cost;
-    a.u_min = io->u_min;
-    a.cost_min = io->cost_min;
-    a.idx_min = io->idx_min;
-    HIPCHK(launch_cost_landscape(a, stream ? (hipStream_t)stream : s->stream));
-    return QSP_OK;
+    return cost_landscape_run(s, opts, "qsp_cost_landscape_device", false, io, stream);
 }
 
 // ------------------------------------- contact modes and the open-loop simulation
 int qsp_eval_modes(qsp_solver* s, int32_t n, const int32_t* sid, const double* x, const double* u, int32_t* mode,
                    double* cone) {
     if (!s || !sid || !x || !u || !mode || n < 1) return fail(QSP_ERR_ARG, "qsp_eval_modes: bad argument");
-    int r = check_ids(s, n, sid);
+    const int r = check_ids(s, n, sid);
     if (r) return r;
     HIPCHK(hipSetDevice(s->o.device));
-    auto& b = s->ol;
-    if ((r = stage_in(s, b[0], sid, n)) || (r = stage_in(s, b[1], x, (size_t)4 * n)) || (r = stage_in(s, b[2], u, (size_t)2 * n)))
-        return r;
-    HIPCHK(b[3].ensure((size_t)n * 4));
-    if (cone) HIPCHK(b[4].ensure((size_t)n * 3 * 8));
-    HIPCHK(launch_modes(s->shapes.as<ShapeDev>(), s->n_shapes, b[0].as<int32_t>(), n, 1, 1, b[1].as<double>(),
-                        b[2].as<double>(), b[3].as<int32_t>(), cone ? b[4].as<double>() : nullptr, s->stream));
-    if ((r = stage_out(s, mode, b[3], (size_t)n))) return r;
-    if (cone && (r = stage_out(s, cone, b[4], (size_t)3 * n))) return r;
-    HIPCHK(hipStreamSynchronize(s->stream));
-    return QSP_OK;
+    Staging st(s);
+    const int32_t* d_sid = st.in(sid, n);
+    const double *dx = st.in(x, (size_t)4 * n), *du = st.in(u, (size_t)2 * n);
+    int32_t* d_mode = st.out(mode, n);
+    double* d_cone = st.out(cone, (size_t)3 * n);
+    if (st.err) return st.err;
+    HIPCHK(launch_modes(s->shapes.as<ShapeDev>(), s->n_shapes, d_sid, n, 1, 1, dx, du, d_mode, d_cone, s->stream));
+    return st.finish();
 }
 
 int qsp_get_modes(qsp_solver* s, int32_t* mode, double* cone) {
@@ -1624,19 +1577,16 @@ int qsp_get_modes(qsp_solver* s, int32_t* mode, double* cone) {
     if (s->n_shapes < 1) return fail(QSP_ERR_STATE, "qsp_get_modes: no shapes set");
     const size_t n = (size_t)s->o.batch * s->o.N;
     HIPCHK(hipSetDevice(s->o.device));
-    auto& b = s->ol;
-    HIPCHK(b[3].ensure(n * 4));
-    if (cone) HIPCHK(b[4].ensure(n * 3 * 8));
+    Staging st(s);
+    int32_t* d_mode = st.out(mode, n);
+    double* d_cone = st.out(cone, 3 * n);
+    if (st.err) return st.err;
     // the buffers qsp_get_x / qsp_get_u copy out
     const DevBuf& X = s->last_controller ? s->X : s->Xo;
     const DevBuf& U = s->last_controller ? s->U : s->Uo;
     HIPCHK(launch_modes(s->shapes.as<ShapeDev>(), s->n_shapes, s->shape_id.as<int32_t>(), (long long)n, s->o.N, s->o.N + 1,
-                        X.as<double>(), U.as<double>(), b[3].as<int32_t>(), cone ? b[4].as<double>() : nullptr, s->stream));
-    int r;
-    if ((r = stage_out(s, mode, b[3], n))) return r;
-    if (cone && (r = stage_out(s, cone, b[4], 3 * n))) return r;
-    HIPCHK(hipStreamSynchronize(s->stream));
-    return QSP_OK;
+                        X.as<double>(), U.as<double>(), d_mode, d_cone, s->stream));
+    return st.finish();
 }
 
 void qsp_default_open_loop_opts(qsp_open_loop_opts* o) {
@@ -1688,61 +1638,52 @@ static int open_loop_args(qsp_solver* s, const qsp_open_loop_opts* o, const char
     return QSP_OK;
 }
 
+static int open_loop_run(qsp_solver* s, const qsp_open_loop_opts* opts, const char* who, bool host,
+                         const qsp_open_loop_io* io, void* stream) {
+    OpenLoopArgs a;
+    const int r = open_loop_args(s, opts, who, a);
+    if (r) return r;
+    const std::string w(who);
+    if (!io || !io->x0 || !io->U || !io->x_end) return fail(QSP_ERR_ARG, w + missing(host));
+    qsp_open_loop_io d = *io;
+    Staging st(s);
+    if (host) {
+        const size_t B = a.B, T = a.T, BM = B * (size_t)a.M;
+        d.x0 = st.in(io->x0, B * 4);
+        d.U = st.in(io->U, BM * a.u_steps * 2);
+        d.noise = st.in(io->noise, T * B * 4);
+        d.X = st.out(io->X, BM * (T + 1) * 4);
+        d.U_out = st.out(io->U_out, BM * T * 2);
+        d.S_p = st.out(io->S_p, BM * T * 2);
+        d.mode = st.out(io->mode, BM * T);
+        d.mode_steps = st.out(io->mode_steps, BM * 4);
+        d.x_end = st.out(io->x_end, BM * 4);
+        if (st.err) return st.err;
+    }
+    if ((((uintptr_t)d.X | (uintptr_t)d.U_out | (uintptr_t)d.S_p) & 15) != 0)
+        return fail(QSP_ERR_ARG, w + ": X, U_out and S_p must be 16-byte aligned");
+    a.x0 = d.x0;
+    a.U = d.U;
+    a.noise = d.noise;
+    if (d.shape_id) a.shape_id = d.shape_id;
+    a.X = d.X;
+    a.U_out = d.U_out;
+    a.S_p = d.S_p;
+    a.mode = d.mode;
+    a.mode_steps = d.mode_steps;
+    a.x_end = d.x_end;
+    HIPCHK(launch_open_loop(a, stream_of(s, host, stream)));
+    return host ? st.finish() : QSP_OK;
+}
+
 int qsp_open_loop(qsp_solver* s, const qsp_open_loop_opts* opts, const double* x0, const double* U, const double* noise,
                   double* X, double* U_out, double* S_p, int32_t* mode, int32_t* mode_steps, double* x_end) {
-    OpenLoopArgs a;
-    int r = open_loop_args(s, opts, "qsp_open_loop", a);
-    if (r) return r;
-    if (!x0 || !U || !x_end) return fail(QSP_ERR_ARG, "qsp_open_loop: null argument");
-    const size_t B = a.B, T = a.T, BM = B * (size_t)a.M;
-    auto& b = s->ol;
-    if ((r = stage_in(s, b[0], x0, B * 4)) || (r = stage_in(s, b[1], U, BM * a.u_steps * 2))) return r;
-    if (noise && (r = stage_in(s, b[2], noise, T * B * 4))) return r;
-    if (X) HIPCHK(b[5].ensure(BM * (T + 1) * 4 * 8));
-    if (U_out) HIPCHK(b[6].ensure(BM * T * 2 * 8));
-    if (S_p) HIPCHK(b[7].ensure(BM * T * 2 * 8));
-    if (mode) HIPCHK(b[3].ensure(BM * T * 4));
-    if (mode_steps) HIPCHK(b[8].ensure(BM * 4 * 4));
-    HIPCHK(b[9].ensure(BM * 4 * 8));
-    a.x0 = b[0].as<double>();
-    a.U = b[1].as<double>();
-    a.noise = noise ? b[2].as<double>() : nullptr;
-    a.X = X ? b[5].as<double>() : nullptr;
-    a.U_out = U_out ? b[6].as<double>() : nullptr;
-    a.S_p = S_p ? b[7].as<double>() : nullptr;
-    a.mode = mode ? b[3].as<int32_t>() : nullptr;
-    a.mode_steps = mode_steps ? b[8].as<int32_t>() : nullptr;
-    a.x_end = b[9].as<double>();
-    HIPCHK(launch_open_loop(a, s->stream));
-    if (X && (r = stage_out(s, X, b[5], BM * (T + 1) * 4))) return r;
-    if (U_out && (r = stage_out(s, U_out, b[6], BM * T * 2))) return r;
-    if (S_p && (r = stage_out(s, S_p, b[7], BM * T * 2))) return r;
-    if (mode && (r = stage_out(s, mode, b[3], BM * T))) return r;
-    if (mode_steps && (r = stage_out(s, mode_steps, b[8], BM * 4))) return r;
-    if ((r = stage_out(s, x_end, b[9], BM * 4))) return r;
-    HIPCHK(hipStreamSynchronize(s->stream));
-    return QSP_OK;
+    const qsp_open_loop_io io = {x0, U, noise, nullptr, X, U_out, S_p, mode, mode_steps, x_end};
+    return open_loop_run(s, opts, "qsp_open_loop", true, &io, nullptr);
 }
 
 int qsp_open_loop_device(qsp_solver* s, const qsp_open_loop_opts* opts, const qsp_open_loop_io* io, void* stream) {
-    OpenLoopArgs a;
-    int r = open_loop_args(s, opts, "qsp_open_loop_device", a);
-    if (r) return r;
-    if (!io || !io->x0 || !io->U || !io->x_end) return fail(QSP_ERR_ARG, "qsp_open_loop_device: missing device pointer");
-    if ((((uintptr_t)io->X | (uintptr_t)io->U_out | (uintptr_t)io->S_p) & 15) != 0)
-        return fail(QSP_ERR_ARG, "qsp_open_loop_device: X, U_out and S_p must be 16-byte aligned");
-    a.x0 = io->x0;
-    a.U = io->U;
-    a.noise = io->noise;
-    if (io->shape_id) a.shape_id = io->shape_id;
-    a.X = io->X;
-    a.U_out = io->U_out;
-    a.S_p = io->S_p;
-    a.mode = io->mode;
-    a.mode_steps = io->mode_steps;
-    a.x_end = io->x_end;
-    HIPCHK(launch_open_loop(a, stream ? (hipStream_t)stream : s->stream));
-    return QSP_OK;
+    return open_loop_run(s, opts, "qsp_open_loop_device", false, io, stream);
 }
 
 }  // extern "C"

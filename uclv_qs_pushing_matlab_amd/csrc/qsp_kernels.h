@@ -66,9 +66,11 @@ struct SolveArgs {
     double* qp_lam;            // B x N x 6
 };
 
-// Shape of instance i of a kernel's argument block (solver, closed loop, rollout).  The ids are device
-// data that the host cannot validate without a round trip, and the table may have shrunk since they
-// were set, so every kernel clamps them into the table, by shape_clamp.
+// Shape of instance i of a kernel's argument block (solver, closed loop, rollout, open loop, modes).  The
+// ids are device data that the host cannot validate without a round trip, and the table may have shrunk
+// since they were set, so these kernels clamp them into the table, by shape_clamp.  The four
+// building-block kernels (spline_, dynamics_, rk4_, vbound_kernel) do not: they index shapes[sid[i]] with
+// ids that come from the host in the same call, which the entry point has checked (check_ids).
 __device__ __forceinline__ int shape_clamp(int id, int n_shapes) { return id < 0 ? 0 : (id >= n_shapes ? n_shapes - 1 : id); }
 __device__ __forceinline__ const ShapeDev& shape_clamped(const ShapeDev* shapes, int n_shapes, const int32_t* sid, int i) {
     return shapes[shape_clamp(sid ? sid[i] : 0, n_shapes)];
@@ -149,6 +151,9 @@ hipError_t launch_reproject(const ShapeDev* shapes, int n_shapes, const int32_t*
                             const double* py, const double* s0, double* s, hipStream_t stream);
 hipError_t launch_straight_lines(int B, int T, const double* x0, const double* xf, double t0, double tf, double Ts,
                                  int auto_angle, double* traj, hipStream_t stream);
+// y_ref, y_ref_e of the controller step at index_time + offset, from the T x 6 (per_lane: B x T x 6) table
+hipError_t launch_stage_yref(const double* traj, int T, int per_lane, const int32_t* index_time, int offset, int D,
+                             int B, int N, double* yref, double* yref_e, hipStream_t stream);
 hipError_t launch_spline(const ShapeDev* shapes, const int32_t* sid, int n, const double* s, double* C, double* D,
                          double* Dd, double* kappa, hipStream_t stream);
 hipError_t launch_dynamics(const ShapeDev* shapes, const int32_t* sid, int n, const double* x, const double* u,

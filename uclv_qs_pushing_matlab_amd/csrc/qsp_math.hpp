@@ -261,6 +261,21 @@ __device__ __forceinline__ void dynamics(const ShapeDev& sh, double th, double s
     dynamics_cm<WITH_JAC>(sh, ShapeCM{}, th, s, un, ut, o);
 }
 
+// The plant's explicit Euler step x <- x + Ts f(x, u) (helper.m:289-307, NMPC_controller.m:112-120,
+// :357-380): the one step of the prologue's rollout, the closed loop's plant and delay prediction,
+// the rollout costs and the open-loop simulation, whose chains therefore agree bit for bit.
+template <class CM>
+__device__ __forceinline__ void euler_step_cm(const ShapeDev& sh, const CM& cm, double Ts, double x[4], double un, double ut) {
+    DynOut d;
+    dynamics_cm<false>(sh, cm, x[2], x[3], un, ut, d);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) x[c] = qfma(Ts, d.f[c], x[c]);
+}
+
+__device__ __forceinline__ void euler_step(const ShapeDev& sh, double Ts, double x[4], double un, double ut) {
+    euler_step_cm(sh, ShapeCM{}, Ts, x, un, ut);
+}
+
 // ---------------------------------------------------------------- contact mode
 // The motion cone at the contact point s and the branch of f that the input (un, ut) selects:
 // dynamics<> restated up to and including its three indicators, the same operations in the same

@@ -4,14 +4,15 @@
 //                     qsp_math.hpp), for a list of points or for a handle's device-resident trajectories;
 //   open_loop_kernel  helper.open_loop_matlab (helper.m:132-193), one thread per (lane, candidate): per
 //                     step the noise, the tangential clip, the plant's delay buffer, the mode and the
-//                     Euler step x + Ts f(x, u) with the OCP's f (dynamics<false>, plant_kernel's step).
+//                     Euler step x + Ts f(x, u) with the OCP's f (euler_step, qsp_math.hpp: the closed
+//                     loop's plant step).
 //
 // A candidate's arithmetic is the same sequence of IEEE operations at any M, B, lane index, position
 // among the candidates, set of requested outputs and store path: results agree bit for bit, with
 // qsp_rollout_cost's Euler x_end and with the building blocks (qsp_eval_spline, qsp_eval_modes) too.
 //
-// Thread mapping (qsp_rollout.hip's): a lane's candidates are adjacent threads.  With 64 candidates or
-// more a workgroup serves one lane and stages its shape table in LDS (candidates beyond a workgroup's
+// Thread mapping (qsp_candidates.hpp): a lane's candidates are adjacent threads.  With 64 candidates or
+// more a workgroup serves one lane and stages its shape in LDS (candidates beyond a workgroup's
 // size go to further workgroups of the lane); with fewer it serves floor(threads / M) lanes and reads
 // the shapes through the vector cache.
 //
@@ -30,15 +31,12 @@
 
 #include "../../include/qsp_nmpc.h"
 #include "qsp_math.hpp"
-#include "qsp_kernels.h"
+#include "qsp_candidates.hpp"
 
 namespace qsp {
 
 constexpr int OL_BLOCK = 256;        // largest workgroup (K = 0, 1)
 constexpr int OL_TBLOCK = 64;        // workgroup of the tiled paths: K = 8 holds 596 bytes of LDS per thread
-constexpr int OL_ONE_LANE_M = 64;    // candidates per lane from which a workgroup serves one lane
-constexpr int OL_SHAPE_D = (int)(sizeof(ShapeDev) / sizeof(double));
-static_assert(sizeof(ShapeDev) % 16 == 0, "the tile image behind the staged shape stays 16-byte aligned");
 
 // ------------------------------------------------------------------ modes
 __global__ void modes_kernel(const ShapeDev* shapes, int n_shapes, const int32_t* sid, long long n, int per, int xper,
@@ -159,10 +157,7 @@ __device__ __forceinline__ void open_loop_rows(const OpenLoopArgs& A, const Shap
         n2 += mc.mode == QSP_MODE_SL;
         n3 += mc.mode == QSP_MODE_SR;
         log(i, u, sp, mc.mode);
-        DynOut d;
-        dynamics<false>(sh, x[2], x[3], ua[0], ua[1], d);
-#pragma unroll
-        for (int c = 0; c < 4; ++c) x[c] = qfma(A.Ts, d.f[c], x[c]);
+        euler_step(sh, A.Ts, x, ua[0], ua[1]);
     };
 
     if constexpr (K == 0) {
@@ -226,13 +221,15 @@ __global__ void __launch_bounds__(OL_BLOCK) open_loop_kernel(OpenLoopArgs A, int
     extern __shared__ __align__(16) double ol_lds[];
     if (ONE_LANE) {
         const int lane = blockIdx.x;
+        // stage_shape (qsp_candidates.hpp) written out: through the call these four instantiations'
+        // scalar instructions come out in another order (profiles/sim_layer/README.md)
         const double* sg = reinterpret_cast<const double*>(&shape_clamped(A.shapes, A.n_shapes, A.shape_id, lane));
-        for (int q = threadIdx.x; q < OL_SHAPE_D; q += blockDim.x) ol_lds[q] = sg[q];
+        for (int q = threadIdx.x; q < SHAPE_D; q += blockDim.x) ol_lds[q] = sg[q];
         __syncthreads();
         const ShapeDev& sh = *reinterpret_cast<const ShapeDev*>(ol_lds);
         const int m0 = blockIdx.y * blockDim.x, left = A.M - m0;   // left >= 1 by the grid
         open_loop_rows<K>(A, sh, lane, (size_t)lane * A.M + m0, left < (int)blockDim.x ? left : (int)blockDim.x,
-                          ol_lds + OL_SHAPE_D);
+                          ol_lds + SHAPE_D);
     } else {
         const long long lane0 = (long long)blockIdx.x * lpb;
         const long long nl = A.B - lane0 < lpb ? A.B - lane0 : lpb;
@@ -244,17 +241,11 @@ __global__ void __launch_bounds__(OL_BLOCK) open_loop_kernel(OpenLoopArgs A, int
     }
 }
 
-static int ol_wg_threads(long long n, int cap) {   // threads of a workgroup, n items split evenly: whole waves, <= cap
-    const long long passes = (n + cap - 1) / cap;
-    const long long per = (n + passes - 1) / passes;
-    return (int)((per + 63) / 64 * 64);
-}
-
 template <int K>
 static hipError_t launch_ol(const OpenLoopArgs& a, hipStream_t stream) {
     const int cap = K >= 4 ? OL_TBLOCK : OL_BLOCK;
-    if (a.M >= OL_ONE_LANE_M) {
-        const int nt = ol_wg_threads(a.M, cap);
+    if (a.M >= ONE_LANE_M) {
+        const int nt = wg_threads(a.M, cap);
         const long long blocks = ((long long)a.M + nt - 1) / nt;
         if (blocks > 65535) return hipErrorInvalidValue;
         const size_t lds = sizeof(ShapeDev) + (K >= 4 ? Tile<(K >= 4 ? K : 4)>::bytes(nt) : 0);
@@ -272,7 +263,7 @@ static hipError_t launch_ol(const OpenLoopArgs& a, hipStream_t stream) {
 // 65 536 rows of 200 steps (profiles/open_loop/open_loop_rate.txt) -- several lanes per workgroup (M = 1):
 // tiles of 4 steps 1.15 ms, direct 1.28 ms, tiles of 8 steps 1.30 ms; one lane per workgroup (M = 64):
 // direct 0.79 ms, tiles of 4 steps 0.93 ms, of 8 steps 1.28 ms.
-static int ol_default_tile(const OpenLoopArgs& a) { return a.M >= OL_ONE_LANE_M ? 1 : 4; }
+static int ol_default_tile(const OpenLoopArgs& a) { return a.M >= ONE_LANE_M ? 1 : 4; }
 
 hipError_t launch_open_loop(const OpenLoopArgs& a, hipStream_t stream) {
     const bool traj = a.X || a.U_out || a.S_p || a.mode;

@@ -14,12 +14,12 @@
 // Both call rollout_one, so a candidate's arithmetic is the same sequence of IEEE operations in either
 // kernel, at any M, B, lane index or position among the candidates: results agree bit for bit.  The
 // model is the OCP's f (dynamics<false>: PusherSliderModel.m:503-603, what evalModelVariableShape
-// evaluates); the stage sum is epilogue_kernel's chain, the Euler step plant_kernel's, the RK4 step
-// rk4_kernel's xn.
+// evaluates); the stage sum is epilogue_kernel's chain (qsp_solver.hip), the Euler step euler_step
+// (qsp_math.hpp: the closed loop's plant step), the RK4 step rk4_kernel's xn (qsp_sim.hip).
 //
-// Thread mapping: a lane's candidates are adjacent threads.  With 64 candidates or more a workgroup
-// serves one lane and stages what the lane's threads share in LDS -- its shape table, the N x 6
-// references, the terminal reference and (landscape) the tail of U -- and loops over candidates
+// Thread mapping (qsp_candidates.hpp): a lane's candidates are adjacent threads.  With 64 candidates or
+// more a workgroup serves one lane and stages what the lane's threads share in LDS -- its shape, the
+// N x 6 references, the terminal reference and (landscape) the tail of U -- and loops over candidates
 // beyond its size.  With fewer, a 256-thread workgroup serves floor(256 / M) lanes and reads the
 // shared data through the vector cache.  The landscape always runs one lane per workgroup: its
 // reduction stays inside the workgroup (wave shifts, then one LDS slot per wave), without atomics.
@@ -28,14 +28,11 @@
 
 #include "../../include/qsp_nmpc.h"
 #include "qsp_math.hpp"
-#include "qsp_kernels.h"
+#include "qsp_candidates.hpp"
 
 namespace qsp {
 
 constexpr int RO_BLOCK = 256;        // largest workgroup
-constexpr int RO_ONE_LANE_M = 64;    // candidates per lane from which a workgroup serves one lane
-constexpr int RO_SHAPE_D = (int)(sizeof(ShapeDev) / sizeof(double));
-static_assert(sizeof(ShapeDev) % sizeof(double) == 0, "ShapeDev is staged as doubles");
 
 struct RollOut {
     double cost, viol, x[4];
@@ -74,10 +71,7 @@ __device__ __forceinline__ void rollout_one(const RolloutArgs& A, const ShapeDev
 #pragma unroll
             for (int c = 0; c < 4; ++c) x[c] = L.xn[c];
         } else {
-            DynOut d;
-            dynamics<false>(sh, x[2], x[3], u[0], u[1], d);
-#pragma unroll
-            for (int c = 0; c < 4; ++c) x[c] = qfma(A.Ts, d.f[c], x[c]);
+            euler_step(sh, A.Ts, x, u[0], u[1]);
         }
     }
     double s = 0.0;
@@ -91,9 +85,8 @@ __device__ __forceinline__ void rollout_one(const RolloutArgs& A, const ShapeDev
 
 // LDS image of one lane: [shape | yref N x 6 | yref_e 4 | tail N x 2 (landscape)]
 __device__ __forceinline__ void stage_lane(const RolloutArgs& A, int lane, double* lds, bool tail) {
-    const double* sh = reinterpret_cast<const double*>(&shape_clamped(A.shapes, A.n_shapes, A.shape_id, lane));
-    for (int q = threadIdx.x; q < RO_SHAPE_D; q += blockDim.x) lds[q] = sh[q];
-    double* yr = lds + RO_SHAPE_D;
+    stage_shape(shape_clamped(A.shapes, A.n_shapes, A.shape_id, lane), lds);
+    double* yr = lds + SHAPE_D;
     const double* gy = A.yref + (size_t)lane * A.N * 6;
     for (int q = threadIdx.x; q < A.N * 6; q += blockDim.x) yr[q] = gy[q];
     double* ye = yr + A.N * 6;
@@ -149,7 +142,7 @@ __global__ void __launch_bounds__(RO_BLOCK) rollout_cost_kernel(RolloutArgs A, i
         const int lane = blockIdx.x;
         stage_lane(A, lane, ro_lds, false);
         const ShapeDev& sh = *reinterpret_cast<const ShapeDev*>(ro_lds);
-        const double* yr = ro_lds + RO_SHAPE_D;
+        const double* yr = ro_lds + SHAPE_D;
         const double* ye = yr + A.N * 6;
         const double* x0 = A.x0 + (size_t)lane * 4;
         for (int m = threadIdx.x; m < A.M; m += blockDim.x) {
@@ -184,10 +177,10 @@ __global__ void __launch_bounds__(RO_BLOCK) cost_landscape_kernel(RolloutArgs A)
     const int lane = blockIdx.x;
     stage_lane(A, lane, ro_lds, true);
     const ShapeDev& sh = *reinterpret_cast<const ShapeDev*>(ro_lds);
-    const double* yr = ro_lds + RO_SHAPE_D;
+    const double* yr = ro_lds + SHAPE_D;
     const double* ye = yr + A.N * 6;
     const double* tail = ye + 4;
-    double* red_c = ro_lds + RO_SHAPE_D + A.N * 8 + 4;                 // one slot per wave
+    double* red_c = ro_lds + SHAPE_D + A.N * 8 + 4;                 // one slot per wave
     int* red_i = reinterpret_cast<int*>(red_c + RO_BLOCK / 64);
     const double* x0 = A.x0 + (size_t)lane * 4;
     const int G = A.n_un * A.n_ut;
@@ -222,18 +215,12 @@ __global__ void __launch_bounds__(RO_BLOCK) cost_landscape_kernel(RolloutArgs A)
     }
 }
 
-static int wg_threads(long long n) {   // threads of a workgroup that loops over n items: whole waves, <= RO_BLOCK
-    const long long passes = (n + RO_BLOCK - 1) / RO_BLOCK;
-    const long long per = (n + passes - 1) / passes;
-    return (int)((per + 63) / 64 * 64);
-}
-
 hipError_t launch_rollout_cost(const RolloutArgs& a, hipStream_t stream) {
     const int vec = ((uintptr_t)a.U & 15) == 0 ? 1 : 0;
     const bool rk = a.integrator == QSP_ROLLOUT_RK4;
-    if (a.M >= RO_ONE_LANE_M) {
-        const size_t lds = (size_t)(RO_SHAPE_D + a.N * 6 + 4) * sizeof(double);
-        const dim3 grid((unsigned)a.B), block((unsigned)wg_threads(a.M));
+    if (a.M >= ONE_LANE_M) {
+        const size_t lds = (size_t)(SHAPE_D + a.N * 6 + 4) * sizeof(double);
+        const dim3 grid((unsigned)a.B), block((unsigned)wg_threads(a.M, RO_BLOCK));
         if (rk) hipLaunchKernelGGL((rollout_cost_kernel<QSP_ROLLOUT_RK4, true>), grid, block, lds, stream, a, 1, vec);
         else hipLaunchKernelGGL((rollout_cost_kernel<QSP_ROLLOUT_EULER, true>), grid, block, lds, stream, a, 1, vec);
     } else {
@@ -246,8 +233,8 @@ hipError_t launch_rollout_cost(const RolloutArgs& a, hipStream_t stream) {
 }
 
 hipError_t launch_cost_landscape(const RolloutArgs& a, hipStream_t stream) {
-    const size_t lds = (size_t)(RO_SHAPE_D + a.N * 8 + 4 + RO_BLOCK / 64) * sizeof(double) + (RO_BLOCK / 64) * sizeof(int);
-    const dim3 grid((unsigned)a.B), block((unsigned)wg_threads((long long)a.n_un * a.n_ut));
+    const size_t lds = (size_t)(SHAPE_D + a.N * 8 + 4 + RO_BLOCK / 64) * sizeof(double) + (RO_BLOCK / 64) * sizeof(int);
+    const dim3 grid((unsigned)a.B), block((unsigned)wg_threads((long long)a.n_un * a.n_ut, RO_BLOCK));
     if (a.integrator == QSP_ROLLOUT_RK4)
         hipLaunchKernelGGL((cost_landscape_kernel<QSP_ROLLOUT_RK4>), grid, block, lds, stream, a);
     else

@@ -1,0 +1,381 @@
+// qsp_sim.hip — what runs around the solve on gfx950 (FP64): the device closed loop's plant, reference
+// generation and staging, and the building-block kernels.
+//
+//   closed_loop_pre_kernel, plant_kernel   helper.m:195-322 around each NMPC_controller.solve;
+//   delay_sim_kernel, reproject_kernel     NMPC_controller.delay_buffer_sim and the disturbance's
+//                                          re-projection on their own;
+//   straight_lines_kernel                  TrajectoryGenerator.straight_line per lane;
+//   stage_yref_kernel                      get_y_ref: a controller step's references out of the table;
+//   spline_, dynamics_, rk4_, vbound_kernel  one device function each (qsp_math.hpp), for the tests and
+//                                          the oracle comparison.
+//
+// The plant's step is euler_step_cm (qsp_math.hpp), the one the prologue, the rollout and the open-loop
+// simulation take: their chains agree bit for bit.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/qsp_nmpc.h"
+#include "qsp_math.hpp"
+#include "qsp_kernels.h"
+
+namespace qsp {
+
+// ------------------------------------------------------- closed-loop plant
+// helper.m:195-322 (closed_loop_matlab), one thread per lane, around each NMPC_controller.solve:
+//   closed_loop_pre_kernel: the disturbance (:221-236), sim_noise (:240-242), the trajectory log
+//     and the controller's delay prediction delay_buffer_sim (NMPC_controller.m:112-120) into the
+//     solver's x0;
+//   plant_kernel: the controller input buffer push (helper.m:255), the plant x(:,i+1) = x(:,i) +
+//     Ts * evalModelVariableShape(x(:,i), u) with the plant's own delay buffer (:289-307), logs.
+
+// |C(s) - p|^2 with C at the floor-mod of s (evalSpline, bspline_shape.m:192-199)
+__device__ __forceinline__ double contact_phi(const ShapeDev& sh, double s, double px, double py) {
+    SplineEval e;
+    spline_eval(sh, mat_mod(s, sh.b), e);
+    const double ex = e.C[0] - px, ey = e.C[1] - py;
+    return qfma(ey, ey, ex * ex);
+}
+
+// The contact point after a lateral disturbance: argmin_s |C(s) - p|^2 from s0 (fminunc in the
+// reference, helper.m:230; restated as a damped Newton iteration, as the oracle's reproject_contact)
+__device__ double reproject_contact(const ShapeDev& sh, double px, double py, double s0) {
+    double s = s0, phi = contact_phi(sh, s, px, py);
+    for (int it = 0; it < 60; ++it) {
+        SplineEval e;
+        spline_eval(sh, mat_mod(s, sh.b), e);
+        const double ex = e.C[0] - px, ey = e.C[1] - py;
+        const double g = 2.0 * qfma(ey, e.D[1], ex * e.D[0]);
+        const double h = 2.0 * qfma(ey, e.Dd[1], qfma(ex, e.Dd[0], qfma(e.D[1], e.D[1], e.D[0] * e.D[0])));
+        if (fabs(g) < 1e-14) break;
+        double step = h > 0.0 ? -g / h : (g > 0.0 ? -0.05 : 0.05) * sh.b;
+        const double smax = 0.25 * sh.b;
+        step = fmin(fmax(step, -smax), smax);
+        bool ok = false;
+        double sn = s, phin = phi;
+        for (int k = 0; k < 60; ++k) {
+            sn = s + step;
+            phin = contact_phi(sh, sn, px, py);
+            if (phin < phi) { ok = true; break; }
+            step *= 0.5;
+        }
+        if (!ok) break;
+        s = sn;
+        phi = phin;
+        if (fabs(step) < 1e-13 * sh.b) break;
+    }
+    return s;
+}
+
+// With a plant model installed (qsp_set_plant_*) the three kernels below take lane i's shape, c and
+// mu from it (plant_of): the reference simulates, predicts and re-projects with `plant`
+// (helper.m:226-233, :244, :294-307) and keeps the controller's model for solve alone.
+
+// Lane i's plant: the shape and the two constants f reads beside it
+struct PlantModel {
+    const ShapeDev* sh;
+    LaneCM cm;
+};
+__device__ __forceinline__ PlantModel plant_of(const ClosedLoopArgs& a, int i) {
+    const ShapeDev& sh = a.pshapes ? shape_clamped(a.pshapes, a.n_pshapes, a.psid, i)
+                                   : shape_clamped(a.shapes, a.n_shapes, a.sid, i);
+    return PlantModel{&sh, LaneCM{a.pc ? a.pc[i] : sh.c, a.pmu ? a.pmu[i] : sh.mu}};
+}
+
+// delay_buffer_sim (NMPC_controller.m:112-120): D Euler steps of lane i's x with the buffered inputs,
+// oldest (u_buff_contr(:, end)) first
+__device__ __forceinline__ void delay_predict(const ClosedLoopArgs& a, const PlantModel& pm, int i, double x[4]) {
+    for (int k = 1; k <= a.D; ++k) {
+        const double* u = a.ubc + ((size_t)i * a.D + (a.D - k)) * 2;
+        euler_step_cm(*pm.sh, pm.cm, a.Ts, x, u[0], u[1]);
+    }
+}
+
+__global__ void closed_loop_pre_kernel(ClosedLoopArgs a, int t) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.B) return;
+    const PlantModel pm = plant_of(a, i);
+    const ShapeDev& sh = *pm.sh;
+    double x[4] = {a.x[(size_t)i * 4], a.x[(size_t)i * 4 + 1], a.x[(size_t)i * 4 + 2], a.x[(size_t)i * 4 + 3]};
+    if (a.dist_step > 0 && t + 1 == a.dist_step) {
+        // y += amplitude; new contact: the spline point nearest (-xwidth/2, C_y(s) - amplitude),
+        // from s0_spline = 0 (one disturbance per run), wrapped into [-b, b) (:224-234)
+        const double amp = a.dist_amp ? a.dist_amp[i] : 0.0;
+        x[1] += amp;
+        SplineEval e;
+        spline_eval(sh, mat_mod(x[3], sh.b), e);
+        const double sn = reproject_contact(sh, -0.5 * sh.xwidth, e.C[1] - amp, 0.0);
+        x[3] = qfma(-sh.b, sn < 0.0 ? 1.0 : 0.0, mat_mod(sn, sh.b));
+    }
+    if (a.noise)
+        for (int c = 0; c < 4; ++c) x[c] += a.noise[((size_t)t * a.B + i) * 4 + c];
+    for (int c = 0; c < 4; ++c) {
+        a.x[(size_t)i * 4 + c] = x[c];
+        if (a.Xtraj) a.Xtraj[((size_t)i * (a.n_steps + 1) + t) * 4 + c] = x[c];
+    }
+    delay_predict(a, pm, i, x);
+    for (int c = 0; c < 4; ++c) a.xs[(size_t)i * 4 + c] = x[c];
+    if (a.Xsim)
+        for (int c = 0; c < 4; ++c) a.Xsim[((size_t)i * a.n_steps + t) * 4 + c] = x[c];
+}
+
+// Row of lane i's reference table at the 1-based column col, clamped at both ends as get_y_ref clamps
+// (NMPC_controller.m:307-313); the table as installed, without the delay prefix
+__device__ __forceinline__ const double* metrics_ref(const ClosedLoopArgs& a, int i, int col) {
+    col = col > a.mT ? a.mT : col;
+    col = col < 1 ? 1 : col;
+    return a.mtraj + ((size_t)(a.mper_lane ? i : 0) * a.mT + (size_t)(col - 1)) * 6;
+}
+
+// qsp_closed_loop_metrics' accumulators of lane i for step t (0-based): x the logged plant state (after
+// disturbance and noise), xn the state after the plant step, u the commanded and ua the applied input.
+// Plain products and sums in step order (no qfma), so that numpy restates them bit for bit.
+__device__ __forceinline__ void metrics_step(const ClosedLoopArgs& a, const PlantModel& pm, int i, int t,
+                                             const double x[4], const double xn[4], const double u[2],
+                                             const double ua[2]) {
+    double* m = a.metrics + (size_t)i * CL_NMETRICS;
+    const double* r = metrics_ref(a, i, a.index0[i] + t);
+    const double ex = x[0] - r[0], ey = x[1] - r[1], et = x[2] - r[2];
+    const double e2 = ex * ex + ey * ey;
+    m[0] = m[0] + e2;
+    m[1] = e2 > m[1] ? e2 : m[1];
+    m[2] = m[2] + et * et;
+    if (t + 1 == a.n_steps) {
+        const double* re = metrics_ref(a, i, a.index0[i] + a.n_steps);
+        const double fx = xn[0] - re[0], fy = xn[1] - re[1];
+        m[3] = fx * fx + fy * fy;
+    }
+    m[4] = m[4] + (u[0] * u[0] + u[1] * u[1]);
+    if (a.status[i] != 0) m[5] = m[5] + 1.0;
+    const int mode = motion_cone_cm(*pm.sh, pm.cm, x[3], ua[0], ua[1]).mode;
+    if (mode != QSP_MODE_NONE) m[5 + mode] = m[5 + mode] + 1.0;   // 6, 7, 8: ST, SL, SR
+    if (!(x[3] >= a.s_lo && x[3] <= a.s_hi)) m[9] = m[9] + 1.0;
+}
+
+__global__ void plant_kernel(ClosedLoopArgs a, int t) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.B) return;
+    const PlantModel pm = plant_of(a, i);
+    double xi[4] = {a.x[(size_t)i * 4], a.x[(size_t)i * 4 + 1], a.x[(size_t)i * 4 + 2], a.x[(size_t)i * 4 + 3]};
+    const double u[2] = {a.u0[(size_t)i * 2], a.u0[(size_t)i * 2 + 1]};
+    // u_buff_contr = [u, u_buff_contr(:, 1:end-1)]
+    if (a.D > 0) {
+        double* b = a.ubc + (size_t)i * a.D * 2;
+        for (int k = a.D - 1; k >= 1; --k) { b[2 * k] = b[2 * (k - 1)]; b[2 * k + 1] = b[2 * (k - 1) + 1]; }
+        b[0] = u[0];
+        b[1] = u[1];
+    }
+    double ua[2] = {u[0], u[1]};
+    if (a.Dp > 0) {   // the plant applies u_buff_plant(:, end), then pushes u
+        double* b = a.ubp + (size_t)i * a.Dp * 2;
+        ua[0] = b[2 * (a.Dp - 1)];
+        ua[1] = b[2 * (a.Dp - 1) + 1];
+        for (int k = a.Dp - 1; k >= 1; --k) { b[2 * k] = b[2 * (k - 1)]; b[2 * k + 1] = b[2 * (k - 1) + 1]; }
+        b[0] = u[0];
+        b[1] = u[1];
+    }
+    double xn[4] = {xi[0], xi[1], xi[2], xi[3]};   // the metrics read the state before the step too
+    euler_step_cm(*pm.sh, pm.cm, a.Ts, xn, ua[0], ua[1]);
+    for (int c = 0; c < 4; ++c) {
+        a.x[(size_t)i * 4 + c] = xn[c];
+        if (a.Xtraj && t + 1 == a.n_steps) a.Xtraj[((size_t)i * (a.n_steps + 1) + t + 1) * 4 + c] = xn[c];
+    }
+    if (a.Utraj) {
+        a.Utraj[((size_t)i * a.n_steps + t) * 2] = u[0];
+        a.Utraj[((size_t)i * a.n_steps + t) * 2 + 1] = u[1];
+    }
+    if (a.Straj) a.Straj[(size_t)i * a.n_steps + t] = a.status[i];
+    if (a.metrics) metrics_step(a, pm, i, t, xi, xn, u, ua);
+}
+
+// NMPC_controller.delay_buffer_sim alone (qsp_delay_buffer_sim)
+__global__ void delay_sim_kernel(ClosedLoopArgs a) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.B) return;
+    const PlantModel pm = plant_of(a, i);
+    double x[4] = {a.x[(size_t)i * 4], a.x[(size_t)i * 4 + 1], a.x[(size_t)i * 4 + 2], a.x[(size_t)i * 4 + 3]};
+    delay_predict(a, pm, i, x);
+    for (int c = 0; c < 4; ++c) a.xs[(size_t)i * 4 + c] = x[c];
+}
+
+__global__ void reproject_kernel(const ShapeDev* shapes, int n_shapes, const int32_t* sid, int n, const double* px,
+                                 const double* py, const double* s0, double* s) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    s[i] = reproject_contact(shape_clamped(shapes, n_shapes, sid, i), px[i], py[i], s0[i]);
+}
+
+hipError_t launch_closed_loop_pre(const ClosedLoopArgs& a, int t, hipStream_t stream) {
+    hipLaunchKernelGGL(closed_loop_pre_kernel, dim3((a.B + 127) / 128), dim3(128), 0, stream, a, t);
+    return hipGetLastError();
+}
+
+hipError_t launch_plant(const ClosedLoopArgs& a, int t, hipStream_t stream) {
+    hipLaunchKernelGGL(plant_kernel, dim3((a.B + 127) / 128), dim3(128), 0, stream, a, t);
+    return hipGetLastError();
+}
+
+hipError_t launch_delay_sim(const ClosedLoopArgs& a, hipStream_t stream) {
+    hipLaunchKernelGGL(delay_sim_kernel, dim3((a.B + 127) / 128), dim3(128), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_reproject(const ShapeDev* shapes, int n_shapes, const int32_t* sid, int n, const double* px,
+                            const double* py, const double* s0, double* s, hipStream_t stream) {
+    hipLaunchKernelGGL(reproject_kernel, dim3((n + 127) / 128), dim3(128), 0, stream, shapes, n_shapes, sid, n, px, py,
+                       s0, s);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------- reference generation
+// TrajectoryGenerator.straight_line (TrajectoryGenerator.m:39-79), one thread per
+// (lane, sample): quintic time scaling s(t) = 6 tau^5 - 15 tau^4 + 10 tau^3, tau = t / tf
+// (:39-42), x(t) = x0 + s(t) (xf - x0) on (x, y, theta); rows [x y theta 0 0 0] as
+// main.m:165-178 builds y_ref (s_ref = 0, u_ref = 0).  auto_angle: theta follows its own
+// quintic over tf / 2 and then holds its final value (:58-66).
+__device__ __forceinline__ double quintic(double t, double tf) {
+    const double tau = t / tf;
+    return qfma(qfma(6.0, tau, -15.0), tau, 10.0) * tau * tau * tau;
+}
+
+__global__ void straight_lines_kernel(int B, int T, const double* x0, const double* xf, double t0, double tf,
+                                      double Ts, int auto_angle, double* traj) {
+    const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= (size_t)B * T) return;
+    const int i = (int)(g / T), k = (int)(g - (size_t)i * T);
+    const double t = qfma((double)k, Ts, t0);
+    const double* a = x0 + (size_t)i * 3;
+    const double* b = xf + (size_t)i * 3;
+    const double s = quintic(t, tf);
+    double* out = traj + g * 6;
+    out[0] = qfma(s, b[0] - a[0], a[0]);
+    out[1] = qfma(s, b[1] - a[1], a[1]);
+    if (auto_angle) {
+        const double tfa = 0.5 * tf;
+        const int ka = (int)floor((tfa - t0) / Ts + 1e-9);      // last sample of t0:Ts:tf/2
+        const double ta = qfma((double)(k < ka ? k : ka), Ts, t0);
+        out[2] = qfma(quintic(ta, tf), b[2] - a[2], a[2]);
+    } else {
+        out[2] = qfma(s, b[2] - a[2], a[2]);
+    }
+    out[3] = 0.0;
+    out[4] = 0.0;
+    out[5] = 0.0;
+}
+
+hipError_t launch_straight_lines(int B, int T, const double* x0, const double* xf, double t0, double tf, double Ts,
+                                 int auto_angle, double* traj, hipStream_t stream) {
+    const size_t n = (size_t)B * T;
+    hipLaunchKernelGGL(straight_lines_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, B, T, x0, xf,
+                       t0, tf, Ts, auto_angle, traj);
+    return hipGetLastError();
+}
+
+// ----------------------------------------------------- building-block kernels
+// sid[i] indexes the table as it is: the host entries check the ids first (check_ids, qsp_capi.hip)
+__global__ void spline_kernel(const ShapeDev* shapes, const int32_t* sid, int n, const double* s,
+                              double* C, double* D, double* Dd, double* kappa) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const ShapeDev& sh = shapes[sid[i]];
+    SplineEval e;
+    spline_eval(sh, s[i], e);
+    for (int c = 0; c < 2; ++c) { C[2 * i + c] = e.C[c]; D[2 * i + c] = e.D[c]; Dd[2 * i + c] = e.Dd[c]; }
+    kappa[i] = angle_rate_of(e);
+}
+
+__global__ void dynamics_kernel(const ShapeDev* shapes, const int32_t* sid, int n, const double* x, const double* u,
+                                double* f, double* J) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const ShapeDev& sh = shapes[sid[i]];
+    DynOut d;
+    dynamics<true>(sh, x[4 * i + 2], x[4 * i + 3], u[2 * i], u[2 * i + 1], d);
+    for (int r = 0; r < 4; ++r) {
+        f[4 * i + r] = d.f[r];
+        double* Jr = J + (size_t)24 * i + 6 * r;
+        Jr[0] = 0.0; Jr[1] = 0.0;
+        Jr[2] = r < 2 ? d.Jth[r] : 0.0;
+        Jr[3] = d.Js[r]; Jr[4] = d.Jun[r]; Jr[5] = d.Jut[r];
+    }
+}
+
+__global__ void rk4_kernel(const ShapeDev* shapes, const int32_t* sid, int n, double h, const double* x, const double* u,
+                           double* xn, double* Aout, double* Bout) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const ShapeDev& sh = shapes[sid[i]];
+    double xi[4] = {x[4 * i], x[4 * i + 1], x[4 * i + 2], x[4 * i + 3]};
+    double ui[2] = {u[2 * i], u[2 * i + 1]};
+    Lin L;
+    rk4<true>(sh, h, xi, ui, L);
+    double* Ai = Aout + (size_t)16 * i;
+    const double Afull[16] = {1.0, 0.0, L.a[0], L.a[1], 0.0, 1.0, L.a[2], L.a[3],
+                              0.0, 0.0, 1.0, L.a[4], 0.0, 0.0, 0.0, L.a[5]};
+    for (int q = 0; q < 16; ++q) Ai[q] = Afull[q];
+    for (int q = 0; q < 8; ++q) Bout[(size_t)8 * i + q] = L.B[q];
+    for (int q = 0; q < 4; ++q) xn[4 * i + q] = L.xn[q];
+}
+
+__global__ void vbound_kernel(const ShapeDev* shapes, const int32_t* sid, int n, CtrlParams cp, const double* s,
+                              double* vb) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    vb[i] = v_bound(shapes[sid[i]], cp, s[i]);
+}
+
+hipError_t launch_spline(const ShapeDev* shapes, const int32_t* sid, int n, const double* s, double* C, double* D,
+                         double* Dd, double* kappa, hipStream_t stream) {
+    hipLaunchKernelGGL(spline_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, shapes, sid, n, s, C, D, Dd, kappa);
+    return hipGetLastError();
+}
+hipError_t launch_dynamics(const ShapeDev* shapes, const int32_t* sid, int n, const double* x, const double* u,
+                           double* f, double* J, hipStream_t stream) {
+    hipLaunchKernelGGL(dynamics_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, shapes, sid, n, x, u, f, J);
+    return hipGetLastError();
+}
+hipError_t launch_rk4(const ShapeDev* shapes, const int32_t* sid, int n, double h, const double* x, const double* u,
+                      double* xn, double* A, double* B, hipStream_t stream) {
+    hipLaunchKernelGGL(rk4_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, shapes, sid, n, h, x, u, xn, A, B);
+    return hipGetLastError();
+}
+hipError_t launch_vbound(const ShapeDev* shapes, const int32_t* sid, int n, CtrlParams cp, const double* s, double* vb,
+                         hipStream_t stream) {
+    hipLaunchKernelGGL(vbound_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, shapes, sid, n, cp, s, vb);
+    return hipGetLastError();
+}
+
+}  // namespace qsp
+
+// ------------------------------------------------- reference staging
+// get_y_ref (NMPC_controller.m:307-313) for one controller step, one thread per lane.  Outside the
+// namespace: the kernel keeps the name it had beside the C ABI.
+__global__ void stage_yref_kernel(const double* traj, int T, int per_lane, const int32_t* index_time, int offset,
+                                  int D, int B, int N, double* yref, double* yref_e) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B) return;
+    if (per_lane) traj += (size_t)i * T * 6;
+    // column index_time+k (1-based) of the table as set_reference_trajectory (:425-431) builds it --
+    // D = delay_buff_comp zero columns prepended, their u_t-reference row copied from the first real
+    // column -- clamped to the last column
+    for (int k = 0; k < N; ++k) {
+        int idx = index_time[i] + offset + k;
+        if (idx > T + D) idx = T + D;
+        if (idx < 1) idx = 1;
+        double* out = yref + ((size_t)i * N + k) * 6;
+        if (idx <= D) {
+            for (int c = 0; c < 5; ++c) out[c] = 0.0;
+            out[5] = traj[5];
+        } else {
+            for (int c = 0; c < 6; ++c) out[c] = traj[(size_t)(idx - D - 1) * 6 + c];
+        }
+    }
+    // terminal reference = last stage reference (:348)
+    for (int c = 0; c < 4; ++c) yref_e[(size_t)i * 4 + c] = yref[((size_t)i * N + N - 1) * 6 + c];
+}
+
+hipError_t qsp::launch_stage_yref(const double* traj, int T, int per_lane, const int32_t* index_time, int offset, int D,
+                                  int B, int N, double* yref, double* yref_e, hipStream_t stream) {
+    hipLaunchKernelGGL(stage_yref_kernel, dim3((unsigned)((B + 127) / 128)), dim3(128), 0, stream, traj, T, per_lane,
+                       index_time, offset, D, B, N, yref, yref_e);
+    return hipGetLastError();
+}

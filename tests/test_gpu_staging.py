@@ -25,8 +25,8 @@ def _handle():
     return s
 
 
-def _calls(oracle):
-    """[(name, f(handle) -> tuple of arrays)] with fixed inputs."""
+def _calls(oracle, N=N):
+    """[(name, f(handle) -> tuple of arrays)] with fixed inputs, for a handle of horizon N (B lanes)."""
     from oracle.oracle import make_opts
     rng = np.random.default_rng(51)
     x0 = config2_x0(B, 52)

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/qsp_nmpc.h"
+#include "qsp_devbuf.hpp"
 #include "qsp_kernels.h"
 
 using namespace qsp;
@@ -26,52 +27,39 @@ static int fail(int code, const std::string& msg) {
         if (e_ != hipSuccess) return fail(QSP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
     } while (0)
 
-struct DevBuf {
-    void* p = nullptr;
-    size_t n = 0;
-    hipError_t ensure(size_t bytes) {
-        if (bytes <= n) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-        hipError_t e = hipMalloc(&p, bytes);
-        if (e == hipSuccess) n = bytes;
-        return e;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-    }
-    template <class T>
-    T* as() const { return static_cast<T*>(p); }
-};
-
 constexpr int STAGE_POOL = 12;   // most host arrays of one call (qsp_cost_landscape, qsp_qp_solve: 10)
 
-struct qsp_solver {
+// Every device array is a Dev<T> member (qsp_devbuf.hpp): it is freed with the handle, whichever call allocated it.
+struct __attribute__((visibility("hidden"))) qsp_solver {
     qsp_options o;
     SolveParams p;
+    Dims dim;                       // element counts of the handle's arrays (batch, N)
     int S = 1;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     int n_shapes = 0;
-    DevBuf shapes, shape_id, x0, yref, yref_e, X, U, PI, Xo, Uo, PIo, u0, status, sqp_iter, qp_iter, qp_capped, qp_stalled, cost;
-    DevBuf warm_valid, traj, index_time;
+    Dev<ShapeDev> shapes;
+    Dev<int32_t> shape_id, status, sqp_iter, qp_iter, qp_capped, qp_stalled, index_time;
+    Dev<double> x0, yref, yref_e, X, U, PI, Xo, Uo, PIo, u0, cost, traj;
+    Dev<uint8_t> warm_valid;
     // delay compensation (set_delay_comp, NMPC_controller.m:106-110): delay_buff_comp columns and the
     // per-lane controller input buffer u_buff_contr (B x D x 2, column 0 newest); closed-loop state:
     // the plant's buffer and state, the disturbance amplitudes, the noise (n_steps x B x 4) and the
     // logs of a run with trajectories (B x n_steps: X_sim, X_traj, U_traj, status_traj)
     int32_t D = 0;
-    DevBuf ubc, ubp, cl_x, cl_amp, cl_noise, cl_xsim, cl_xtraj, cl_utraj, cl_straj;
+    Dev<double> ubc, ubp, cl_x, cl_amp, cl_noise, cl_xsim, cl_xtraj, cl_utraj;
+    Dev<int32_t> cl_straj;
     // the plant's own model (qsp_set_plant_*): shape table, ids, per-lane mu_sp / c_ellipse; the closed
     // loop's metric accumulators (qsp_closed_loop_metrics)
     int n_pshapes = 0;
     bool has_pids = false, has_pmu = false, has_pc = false;
-    DevBuf pshapes, pshape_id, pmu, pc, cl_metrics;
-    DevBuf wX, wU, wx0, wlin, wnlp, wdone, wres, wqp, wperm, wnit, whist, wadj, wadjv;
-    DevBuf pool[STAGE_POOL];        // device images of one call's host arrays, handed out by Staging
-    DevBuf ol_ring;                // qsp_open_loop's plant delay buffer (clipped u_t of the last D steps)
+    Dev<ShapeDev> pshapes;
+    Dev<int32_t> pshape_id;
+    Dev<double> pmu, pc, cl_metrics;
+    Dev<double> wX, wU, wx0, wlin, wnlp, wres, wqp, wadj;
+    Dev<int32_t> wdone, wperm, wnit, whist, wadjv;
+    Dev<uint8_t> pool[STAGE_POOL];  // device images of one call's host arrays (bytes), handed out by Staging
+    Dev<double> ol_ring;            // qsp_open_loop's plant delay buffer (clipped u_t of the last D steps)
     bool solved = false;            // wU holds a solve's iterate (qsp_cost_landscape with U_tail = NULL)
     int32_t T = 0;
     bool have_traj = false;
@@ -92,6 +80,20 @@ struct qsp_solver {
     bool mfw = true;               // QSP_MFMA_WALK=0: the lane walk wherever the matrix cores would factorise
                                    // (developer A/B; rounds differently: the oracle twin reads the same variable)
     int cus = 256;                 // compute units of the device (hipDeviceProp multiProcessorCount)
+
+    // streams and events here, on the handle's device; the buffers free themselves after this body
+    ~qsp_solver() {
+        (void)hipSetDevice(o.device);
+        for (hipEvent_t e : kev) (void)hipEventDestroy(e);
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+        if (split.fork) (void)hipEventDestroy(split.fork);
+        for (int q = 0; q < SQP_MAX_PARTS - 1; ++q) {
+            if (split.join[q]) (void)hipEventDestroy(split.join[q]);
+            if (split.aux[q]) (void)hipStreamDestroy(split.aux[q]);
+        }
+        if (stream) (void)hipStreamDestroy(stream);
+    }
 };
 
 // --------------------------------------------------------------- helpers
@@ -184,17 +186,42 @@ static int read_ply_xy(const char* path, std::vector<float>& xy) {
     return QSP_OK;
 }
 
-static int h2d(qsp_solver* s, DevBuf& b, const void* src, size_t bytes) {
+// host array -> buffer / buffer -> host array, `count` elements, on the handle's stream, synchronised
+template <class T>
+static int h2d(qsp_solver* s, const Dev<T>& b, const T* src, size_t count) {
     HIPCHK(hipSetDevice(s->o.device));
-    HIPCHK(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, s->stream));
+    HIPCHK(b.upload(s->stream, src, count));
     HIPCHK(hipStreamSynchronize(s->stream));
     return QSP_OK;
 }
-static int d2h(qsp_solver* s, void* dst, const DevBuf& b, size_t bytes) {
+template <class T>
+static int h2d_grow(qsp_solver* s, Dev<T>& b, const T* src, size_t count) {   // ... into a buffer grown to `count` first
     HIPCHK(hipSetDevice(s->o.device));
-    HIPCHK(hipMemcpyAsync(dst, b.p, bytes, hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(b.ensure(count));
+    return h2d(s, b, src, count);
+}
+template <class T>
+static int d2h(qsp_solver* s, T* dst, const Dev<T>& b, size_t count) {
+    HIPCHK(hipSetDevice(s->o.device));
+    HIPCHK(b.download(s->stream, dst, count));
     HIPCHK(hipStreamSynchronize(s->stream));
     return QSP_OK;
+}
+
+// The setters and getters of one whole array: the entry's name, its null test ("<who>: null argument"),
+// the handle's buffer and its count from Dims.  ctl: the buffer that holds the array after a controller
+// solve (the shifted warm start), where that is another one.
+using DimsCount = size_t (Dims::*)() const;
+template <class T>
+static int set_array(qsp_solver* s, const char* who, const T* host, Dev<T> qsp_solver::*buf, DimsCount count) {
+    if (!s || !host) return fail(QSP_ERR_ARG, std::string(who) + ": null argument");
+    return h2d(s, s->*buf, host, (s->dim.*count)());
+}
+template <class T>
+static int get_array(qsp_solver* s, const char* who, T* host, Dev<T> qsp_solver::*buf, DimsCount count,
+                     Dev<T> qsp_solver::*ctl = nullptr) {
+    if (!s || !host) return fail(QSP_ERR_ARG, std::string(who) + ": null argument");
+    return d2h(s, host, s->*(ctl && s->last_controller ? ctl : buf), (s->dim.*count)());
 }
 
 static SolveArgs make_args(qsp_solver* s) {
@@ -202,40 +229,40 @@ static SolveArgs make_args(qsp_solver* s) {
     std::memset(&a, 0, sizeof a);
     a.p = s->p;
     a.B = s->o.batch;
-    a.shapes = s->shapes.as<ShapeDev>();
+    a.shapes = s->shapes.data();
     a.n_shapes = s->n_shapes;
-    a.shape_id = s->shape_id.as<int32_t>();
-    a.x0 = s->x0.as<double>();
-    a.yref = s->yref.as<double>();
-    a.yref_e = s->yref_e.as<double>();
-    a.X_in = s->X.as<double>();
-    a.U_in = s->U.as<double>();
-    a.u0 = s->u0.as<double>();
-    a.X_out = s->Xo.as<double>();
-    a.U_out = s->Uo.as<double>();
-    a.PI_out = s->PIo.as<double>();
+    a.shape_id = s->shape_id.data();
+    a.x0 = s->x0.data();
+    a.yref = s->yref.data();
+    a.yref_e = s->yref_e.data();
+    a.X_in = s->X.data();
+    a.U_in = s->U.data();
+    a.u0 = s->u0.data();
+    a.X_out = s->Xo.data();
+    a.U_out = s->Uo.data();
+    a.PI_out = s->PIo.data();
     s->last_controller = false;
-    a.status = s->status.as<int32_t>();
-    a.sqp_iter = s->sqp_iter.as<int32_t>();
-    a.qp_iter = s->qp_iter.as<int32_t>();
-    a.qp_capped = s->qp_capped.as<int32_t>();
-    a.qp_stalled = s->qp_stalled.as<int32_t>();
-    a.cost = s->cost.as<double>();
-    a.wX = s->wX.as<double>();
-    a.wU = s->wU.as<double>();
-    a.wx0 = s->wx0.as<double>();
-    a.wlin = s->wlin.as<double>();
-    a.wnlp = s->wnlp.as<double>();
-    a.wdone = s->wdone.as<int32_t>();
-    a.wres = s->wres.as<double>();
-    a.wqp = s->wqp.as<double>();
-    a.wperm = s->nopack ? nullptr : s->wperm.as<int32_t>();
+    a.status = s->status.data();
+    a.sqp_iter = s->sqp_iter.data();
+    a.qp_iter = s->qp_iter.data();
+    a.qp_capped = s->qp_capped.data();
+    a.qp_stalled = s->qp_stalled.data();
+    a.cost = s->cost.data();
+    a.wX = s->wX.data();
+    a.wU = s->wU.data();
+    a.wx0 = s->wx0.data();
+    a.wlin = s->wlin.data();
+    a.wnlp = s->wnlp.data();
+    a.wdone = s->wdone.data();
+    a.wres = s->wres.data();
+    a.wqp = s->wqp.data();
+    a.wperm = s->nopack ? nullptr : s->wperm.data();
     if (s->poison) a.flags |= QSP_FLAG_POISON;
-    a.wnit = s->wnit.as<int32_t>();
-    a.whist = s->whist.as<int32_t>();
-    a.wadj = s->wadj.as<double>();
-    a.wadjv = s->wadjv.as<int32_t>();
-    a.PI_in = s->PI.as<double>();   // 'init_pi' (solve) / shifted warm start (controller)
+    a.wnit = s->wnit.data();
+    a.whist = s->whist.data();
+    a.wadj = s->wadj.data();
+    a.wadjv = s->wadjv.data();
+    a.PI_in = s->PI.data();   // 'init_pi' (solve) / shifted warm start (controller)
     return a;
 }
 
@@ -266,9 +293,9 @@ struct Staging {
     void* take(size_t bytes) {
         if (!err && used == STAGE_POOL) err = fail(QSP_ERR_STATE, "staging pool exhausted: more than STAGE_POOL arrays in one call");
         if (err) return nullptr;
-        DevBuf& b = s->pool[used++];
+        Dev<uint8_t>& b = s->pool[used++];
         check(b.ensure(bytes), "staging hipMalloc");
-        return err ? nullptr : b.p;
+        return err ? nullptr : b.data();
     }
     template <class T>
     T* in(const T* host, size_t count) {
@@ -299,8 +326,8 @@ static int check_ids(qsp_solver* s, int32_t n, const int32_t* ids) {
 
 // y_ref staging for the controller step at index_time + offset
 static hipError_t launch_controller_step(qsp_solver* s, int offset) {
-    return launch_stage_yref(s->traj.as<double>(), s->T, s->traj_per_lane ? 1 : 0, s->index_time.as<int32_t>(), offset,
-                             s->D, s->o.batch, s->o.N, s->yref.as<double>(), s->yref_e.as<double>(), s->stream);
+    return launch_stage_yref(s->traj.data(), s->T, s->traj_per_lane ? 1 : 0, s->index_time.data(), offset,
+                             s->D, s->o.batch, s->o.N, s->yref.data(), s->yref_e.data(), s->stream);
 }
 
 // NMPC_controller.solve arguments: warm buffers updated in place (each instance reads its
@@ -308,10 +335,10 @@ static hipError_t launch_controller_step(qsp_solver* s, int offset) {
 static SolveArgs controller_args(qsp_solver* s) {
     SolveArgs a = make_args(s);
     a.flags |= QSP_FLAG_CONTROLLER | QSP_FLAG_SHIFT;
-    a.warm_valid = s->warm_valid.as<uint8_t>();
-    a.X_out = s->X.as<double>();
-    a.U_out = s->U.as<double>();
-    a.PI_out = s->PI.as<double>();
+    a.warm_valid = s->warm_valid.data();
+    a.X_out = s->X.data();
+    a.U_out = s->U.data();
+    a.PI_out = s->PI.data();
     s->last_controller = true;
     return a;
 }
@@ -406,53 +433,6 @@ int qsp_create(const qsp_options* o, qsp_solver** out) {
         if (e == hipSuccess) e = hipStreamCreateWithFlags(&s->split.aux[q], hipStreamNonBlocking);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&s->split.join[q], hipEventDisableTiming);
     }
-    const size_t B = o->batch, N = o->N;
-    auto al = [&](DevBuf& b, size_t bytes) { if (e == hipSuccess) e = b.ensure(bytes); };
-    al(s->shape_id, B * 4);
-    al(s->x0, B * 4 * 8);
-    al(s->yref, B * N * 6 * 8);
-    al(s->yref_e, B * 4 * 8);
-    al(s->X, B * (N + 1) * 4 * 8);
-    al(s->U, B * N * 2 * 8);
-    al(s->PI, B * N * 4 * 8);
-    al(s->Xo, B * (N + 1) * 4 * 8);
-    al(s->Uo, B * N * 2 * 8);
-    al(s->PIo, B * N * 4 * 8);
-    al(s->u0, B * 2 * 8);
-    al(s->status, B * 4);
-    al(s->sqp_iter, B * 4);
-    al(s->qp_iter, B * 4);
-    al(s->qp_capped, B * 4);
-    al(s->qp_stalled, B * 4);
-    al(s->cost, B * 8);
-    al(s->warm_valid, B);
-    al(s->wX, B * (N + 1) * 4 * 8);
-    al(s->wU, B * N * 2 * 8);
-    al(s->wx0, B * 4 * 8);
-    al(s->wperm, B * 4);
-    al(s->wnit, B * 4);
-    al(s->whist, SQP_MAX_PARTS * 4 * 1024 * 4);   // per part of the SQP loop; qsp_solver.hip PACK_KEYS_MAX
-    al(s->wdone, B * 4);
-    if (o->nlp_mode == QSP_NLP_SQP_MERIT) {
-        // stage data in HBM only for the line search (defect and gradient at the iterate); the
-        // fixed-K path linearises inside the QP kernel, and qsp_qp_solve stages its own
-        al(s->wlin, B * (N + 1) * 24 * 8);
-        al(s->wnlp, B * (N + 1) * 20 * 8);
-        al(s->wqp, B * (N + 1) * 16 * 8);
-        al(s->wres, B * 4 * 8);
-    } else {
-        // fixed-K path: the adjoint record of each instance's last successful QP; the dynamics
-        // multipliers are computed from it once per solve (epilogue_kernel)
-        al(s->wadj, B * N * 11 * 8);
-        al(s->wadjv, B * 4);
-    }
-    if (e == hipSuccess) e = hipMemsetAsync(s->shape_id.p, 0, B * 4, s->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(s->warm_valid.p, 0, B, s->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(s->X.p, 0, B * (N + 1) * 4 * 8, s->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(s->U.p, 0, B * N * 2 * 8, s->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(s->PI.p, 0, B * N * 4 * 8, s->stream);
-    // debug: every workspace byte starts as a NaN pattern, so a kernel that reads a word it
-    // never wrote shows up as NaN (tests/test_gpu_errors.py)
     if (const char* fl = std::getenv("QSP_FUSED_LOOP")) s->fused_req = (fl[0] == '1') ? 1 : (fl[0] == '0' ? 0 : -1);
     if (const char* pk = std::getenv("QSP_PACKING")) s->nopack = pk[0] == '0';
     if (const char* mw = std::getenv("QSP_MFMA_WALK")) s->mfw = mw[0] != '0';
@@ -460,22 +440,55 @@ int qsp_create(const qsp_options* o, qsp_solver** out) {
     mfw_prepare(s->p);
     const char* pz = std::getenv("QSP_DEBUG_POISON");
     s->poison = pz && pz[0] == '1';
-    if (s->poison) {
-        DevBuf* ws[] = {&s->wX, &s->wU, &s->wx0, &s->wlin, &s->wnlp, &s->wdone, &s->wres, &s->wqp, &s->wperm, &s->wnit,
-                        &s->wadj, &s->wadjv, &s->X, &s->U, &s->PI, &s->Xo, &s->Uo, &s->PIo, &s->u0, &s->cost, &s->yref, &s->yref_e};
-        for (DevBuf* b : ws)
-            if (e == hipSuccess && b->p) e = hipMemsetAsync(b->p, 0xff, b->n, s->stream);
-        // ... except what a caller legitimately relies on being zero: the initial guess and warm state
-        if (e == hipSuccess) e = hipMemsetAsync(s->X.p, 0, B * (N + 1) * 4 * 8, s->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(s->U.p, 0, B * N * 2 * 8, s->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(s->PI.p, 0, B * N * 4 * 8, s->stream);
+    s->dim = Dims{(size_t)o->batch, (size_t)o->N};
+    const Dims& d = s->dim;
+    // POISON (debug, QSP_DEBUG_POISON=1): every byte of the buffer starts as a NaN pattern, so a kernel that
+    // reads a word it never wrote shows up as NaN (tests/test_gpu_errors.py)
+    enum Mark { PLAIN, POISON };
+    auto al = [&](auto& b, size_t count, Mark mark = PLAIN) {
+        if (e == hipSuccess) e = b.ensure(count);
+        if (e == hipSuccess && mark == POISON && s->poison) e = b.fill(s->stream, 0xff, count);
+    };
+    auto zero = [&](auto& b, size_t count) { if (e == hipSuccess) e = b.fill(s->stream, 0, count); };
+    al(s->shape_id, d.lane());
+    al(s->x0, d.x0());
+    al(s->yref, d.yref(), POISON);
+    al(s->yref_e, d.yref_e(), POISON);
+    for (auto* b : {&s->X, &s->Xo, &s->wX}) al(*b, d.X(), POISON);
+    for (auto* b : {&s->U, &s->Uo, &s->wU}) al(*b, d.U(), POISON);
+    for (auto* b : {&s->PI, &s->PIo}) al(*b, d.PI(), POISON);
+    al(s->u0, d.u0(), POISON);
+    for (auto* b : {&s->status, &s->sqp_iter, &s->qp_iter, &s->qp_capped, &s->qp_stalled}) al(*b, d.lane());
+    al(s->cost, d.lane(), POISON);
+    al(s->warm_valid, d.lane());
+    al(s->wx0, d.x0(), POISON);
+    for (auto* b : {&s->wperm, &s->wnit, &s->wdone}) al(*b, d.lane(), POISON);
+    al(s->whist, Dims::hist());   // per part of the SQP loop
+    if (o->nlp_mode == QSP_NLP_SQP_MERIT) {
+        // stage data in HBM only for the line search (defect and gradient at the iterate); the
+        // fixed-K path linearises inside the QP kernel, and qsp_qp_solve stages its own
+        al(s->wlin, d.lin(), POISON);
+        al(s->wnlp, d.nlp(), POISON);
+        al(s->wqp, d.qp(), POISON);
+        al(s->wres, d.res(), POISON);
+    } else {
+        // fixed-K path: the adjoint record of each instance's last successful QP; the dynamics
+        // multipliers are computed from it once per solve (epilogue_kernel)
+        al(s->wadj, d.adj(), POISON);
+        al(s->wadjv, d.lane(), POISON);
     }
+    // what a caller legitimately relies on being zero, poisoned or not: the ids, the initial guess and warm state
+    zero(s->shape_id, d.lane());
+    zero(s->warm_valid, d.lane());
+    zero(s->X, d.X());
+    zero(s->U, d.U());
+    zero(s->PI, d.PI());
     // qsp_get_residuals before the first solve returns zeros (header contract)
-    if (e == hipSuccess && s->wres.p) e = hipMemsetAsync(s->wres.p, 0, B * 4 * 8, s->stream);
+    if (s->wres.data()) zero(s->wres, d.res());
     if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
     if (e != hipSuccess) {
         std::string m = std::string("qsp_create: ") + hipGetErrorString(e);
-        qsp_destroy(s);
+        delete s;
         return fail(QSP_ERR_HIP, m);
     }
     *out = s;
@@ -483,28 +496,7 @@ int qsp_create(const qsp_options* o, qsp_solver** out) {
 }
 
 int qsp_destroy(qsp_solver* s) {
-    if (!s) return QSP_OK;
-    (void)hipSetDevice(s->o.device);
-    DevBuf* bufs[] = {&s->ubc, &s->ubp, &s->cl_x, &s->cl_amp, &s->cl_noise, &s->cl_xsim, &s->cl_xtraj, &s->cl_utraj, &s->cl_straj,
-                      &s->pshapes, &s->pshape_id, &s->pmu, &s->pc, &s->cl_metrics,
-                      &s->shapes, &s->shape_id, &s->x0, &s->yref, &s->yref_e, &s->X, &s->U, &s->PI, &s->Xo,
-                      &s->Uo, &s->PIo, &s->u0, &s->status, &s->sqp_iter, &s->qp_iter, &s->qp_capped, &s->qp_stalled, &s->cost,
-                      &s->warm_valid,
-                      &s->traj, &s->index_time, &s->wX, &s->wU, &s->wx0, &s->wlin, &s->wnlp, &s->wdone, &s->wres, &s->wqp, &s->wperm, &s->wnit,
-                      &s->whist, &s->wadj, &s->wadjv};
-    for (DevBuf* b : bufs) b->release();
-    for (auto& b : s->pool) b.release();
-    s->ol_ring.release();
-    for (hipEvent_t e : s->kev) (void)hipEventDestroy(e);
-    if (s->ev0) (void)hipEventDestroy(s->ev0);
-    if (s->ev1) (void)hipEventDestroy(s->ev1);
-    if (s->split.fork) (void)hipEventDestroy(s->split.fork);
-    for (int q = 0; q < SQP_MAX_PARTS - 1; ++q) {
-        if (s->split.join[q]) (void)hipEventDestroy(s->split.join[q]);
-        if (s->split.aux[q]) (void)hipStreamDestroy(s->split.aux[q]);
-    }
-    if (s->stream) (void)hipStreamDestroy(s->stream);
-    delete s;
+    delete s;   // ~qsp_solver selects the handle's device
     return QSP_OK;
 }
 
@@ -582,7 +574,8 @@ int qsp_shape_from_ply(const char* path, int32_t flip, double mu_sg, double mu_s
 }
 
 // qsp_shape table -> device ShapeDev table in the handle's `table` (qsp_set_shapes, qsp_set_plant_shapes)
-static int upload_shapes(qsp_solver* s, const char* who, const qsp_shape* shapes, int32_t n, DevBuf qsp_solver::*table) {
+static int upload_shapes(qsp_solver* s, const char* who, const qsp_shape* shapes, int32_t n,
+                         Dev<ShapeDev> qsp_solver::*table) {
     const std::string w(who);
     if (!s || !shapes || n < 1) return fail(QSP_ERR_ARG, w + ": bad argument");
     std::vector<ShapeDev> h((size_t)n);
@@ -615,12 +608,7 @@ static int upload_shapes(qsp_solver* s, const char* who, const qsp_shape* shapes
                 d.ddctrl[2 * i + c] = den != 0.0 ? 2.0 * ((d.dctrl[2 * i + c] - d.dctrl[2 * (i - 1) + c]) / den) : 0.0;
         }
     }
-    HIPCHK(hipSetDevice(s->o.device));
-    DevBuf& dst = s->*table;
-    HIPCHK(dst.ensure(sizeof(ShapeDev) * n));
-    HIPCHK(hipMemcpyAsync(dst.p, h.data(), sizeof(ShapeDev) * n, hipMemcpyHostToDevice, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    return QSP_OK;
+    return h2d_grow(s, s->*table, h.data(), h.size());
 }
 
 int qsp_set_shapes(qsp_solver* s, const qsp_shape* shapes, int32_t n) {
@@ -634,9 +622,7 @@ int qsp_set_shape_ids(qsp_solver* s, const int32_t* ids) {
     if (!s || !ids) return fail(QSP_ERR_ARG, "qsp_set_shape_ids: null argument");
     for (int i = 0; i < s->o.batch; ++i)
         if (ids[i] < 0 || ids[i] >= s->n_shapes) return fail(QSP_ERR_ARG, "qsp_set_shape_ids: id out of range");
-    HIPCHK(hipSetDevice(s->o.device));
-    HIPCHK(hipMemcpy(s->shape_id.p, ids, (size_t)s->o.batch * 4, hipMemcpyHostToDevice));
-    return QSP_OK;
+    return h2d(s, s->shape_id, ids, s->dim.lane());
 }
 
 // ------------------------------------------------- the plant's own model
@@ -651,12 +637,10 @@ int qsp_set_plant_shapes(qsp_solver* s, const qsp_shape* shapes, int32_t n) {
 int qsp_set_plant_shape_ids(qsp_solver* s, const int32_t* ids) {
     if (!s || !ids) return fail(QSP_ERR_ARG, "qsp_set_plant_shape_ids: null argument");
     if (s->n_pshapes < 1) return fail(QSP_ERR_STATE, "qsp_set_plant_shape_ids: no plant shapes set");
-    const size_t B = s->o.batch;
+    const size_t B = s->dim.lane();
     for (size_t i = 0; i < B; ++i)
         if (ids[i] < 0 || ids[i] >= s->n_pshapes) return fail(QSP_ERR_ARG, "qsp_set_plant_shape_ids: id out of range");
-    HIPCHK(hipSetDevice(s->o.device));
-    HIPCHK(s->pshape_id.ensure(B * 4));
-    const int r = h2d(s, s->pshape_id, ids, B * 4);
+    const int r = h2d_grow(s, s->pshape_id, ids, B);
     if (r) return r;
     s->has_pids = true;
     return QSP_OK;
@@ -664,21 +648,14 @@ int qsp_set_plant_shape_ids(qsp_solver* s, const int32_t* ids) {
 
 int qsp_set_plant_params(qsp_solver* s, const double* mu_sp, const double* c_ellipse) {
     if (!s) return fail(QSP_ERR_ARG, "qsp_set_plant_params: null handle");
-    const size_t B = s->o.batch;
+    const size_t B = s->dim.lane();
     for (const double* v : {mu_sp, c_ellipse})
         for (size_t i = 0; v && i < B; ++i)
             if (!(std::isfinite(v[i]) && v[i] > 0.0))
                 return fail(QSP_ERR_ARG, "qsp_set_plant_params: mu_sp and c_ellipse must be finite and > 0");
-    HIPCHK(hipSetDevice(s->o.device));
     int r;
-    if (mu_sp) {
-        HIPCHK(s->pmu.ensure(B * 8));
-        if ((r = h2d(s, s->pmu, mu_sp, B * 8))) return r;
-    }
-    if (c_ellipse) {
-        HIPCHK(s->pc.ensure(B * 8));
-        if ((r = h2d(s, s->pc, c_ellipse, B * 8))) return r;
-    }
+    if (mu_sp && (r = h2d_grow(s, s->pmu, mu_sp, B))) return r;
+    if (c_ellipse && (r = h2d_grow(s, s->pc, c_ellipse, B))) return r;
     s->has_pmu = mu_sp != nullptr;
     s->has_pc = c_ellipse != nullptr;
     return QSP_OK;
@@ -723,24 +700,19 @@ int qsp_set_ctrl_params(qsp_solver* s, double v_alpha, double d_v, double t_angl
 }
 
 // --------------------------------------------------------- acados level
-int qsp_set_x0(qsp_solver* s, const double* x0) {
-    if (!s || !x0) return fail(QSP_ERR_ARG, "qsp_set_x0: null argument");
-    return h2d(s, s->x0, x0, (size_t)s->o.batch * 4 * 8);
-}
+int qsp_set_x0(qsp_solver* s, const double* x0) { return set_array(s, "qsp_set_x0", x0, &qsp_solver::x0, &Dims::x0); }
 
 int qsp_set_yref(qsp_solver* s, const double* yref, const double* yref_e) {
     if (!s || !yref || !yref_e) return fail(QSP_ERR_ARG, "qsp_set_yref: null argument");
-    int r = h2d(s, s->yref, yref, (size_t)s->o.batch * s->o.N * 6 * 8);
-    if (r) return r;
-    return h2d(s, s->yref_e, yref_e, (size_t)s->o.batch * 4 * 8);
+    const int r = h2d(s, s->yref, yref, s->dim.yref());
+    return r ? r : h2d(s, s->yref_e, yref_e, s->dim.yref_e());
 }
 
 int qsp_set_init(qsp_solver* s, const double* X, const double* U, const double* PI) {
     if (!s || !X || !U) return fail(QSP_ERR_ARG, "qsp_set_init: null argument");
-    const size_t B = s->o.batch, N = s->o.N;
-    int r = h2d(s, s->X, X, B * (N + 1) * 4 * 8);
-    if (!r) r = h2d(s, s->U, U, B * N * 2 * 8);
-    if (!r && PI) r = h2d(s, s->PI, PI, B * N * 4 * 8);
+    int r = h2d(s, s->X, X, s->dim.X());
+    if (!r) r = h2d(s, s->U, U, s->dim.U());
+    if (!r && PI) r = h2d(s, s->PI, PI, s->dim.PI());
     return r;
 }
 
@@ -752,51 +724,22 @@ int qsp_solve(qsp_solver* s) {
     return run_timed(s, a);
 }
 
-int qsp_get_u0(qsp_solver* s, double* u0) {
-    if (!s || !u0) return fail(QSP_ERR_ARG, "qsp_get_u0: null argument");
-    return d2h(s, u0, s->u0, (size_t)s->o.batch * 2 * 8);
-}
-int qsp_get_x(qsp_solver* s, double* X) {
-    if (!s || !X) return fail(QSP_ERR_ARG, "qsp_get_x: null argument");
-    return d2h(s, X, s->last_controller ? s->X : s->Xo, (size_t)s->o.batch * (s->o.N + 1) * 4 * 8);
-}
-int qsp_get_u(qsp_solver* s, double* U) {
-    if (!s || !U) return fail(QSP_ERR_ARG, "qsp_get_u: null argument");
-    return d2h(s, U, s->last_controller ? s->U : s->Uo, (size_t)s->o.batch * s->o.N * 2 * 8);
-}
-int qsp_get_pi(qsp_solver* s, double* PI) {
-    if (!s || !PI) return fail(QSP_ERR_ARG, "qsp_get_pi: null argument");
-    return d2h(s, PI, s->last_controller ? s->PI : s->PIo, (size_t)s->o.batch * s->o.N * 4 * 8);
-}
-int qsp_get_cost(qsp_solver* s, double* c) {
-    if (!s || !c) return fail(QSP_ERR_ARG, "qsp_get_cost: null argument");
-    return d2h(s, c, s->cost, (size_t)s->o.batch * 8);
-}
-int qsp_get_status(qsp_solver* s, int32_t* st) {
-    if (!s || !st) return fail(QSP_ERR_ARG, "qsp_get_status: null argument");
-    return d2h(s, st, s->status, (size_t)s->o.batch * 4);
-}
-int qsp_get_sqp_iter(qsp_solver* s, int32_t* it) {
-    if (!s || !it) return fail(QSP_ERR_ARG, "qsp_get_sqp_iter: null argument");
-    return d2h(s, it, s->sqp_iter, (size_t)s->o.batch * 4);
-}
-int qsp_get_qp_iter(qsp_solver* s, int32_t* it) {
-    if (!s || !it) return fail(QSP_ERR_ARG, "qsp_get_qp_iter: null argument");
-    return d2h(s, it, s->qp_iter, (size_t)s->o.batch * 4);
-}
-int qsp_get_qp_capped(qsp_solver* s, int32_t* c) {
-    if (!s || !c) return fail(QSP_ERR_ARG, "qsp_get_qp_capped: null argument");
-    return d2h(s, c, s->qp_capped, (size_t)s->o.batch * 4);
-}
-
-int qsp_get_qp_stalled(qsp_solver* s, int32_t* c) {
-    if (!s || !c) return fail(QSP_ERR_ARG, "qsp_get_qp_stalled: null argument");
-    return d2h(s, c, s->qp_stalled, (size_t)s->o.batch * 4);
-}
+int qsp_get_u0(qsp_solver* s, double* u0) { return get_array(s, "qsp_get_u0", u0, &qsp_solver::u0, &Dims::u0); }
+// X, U, PI: after a controller solve the shifted warm start
+int qsp_get_x(qsp_solver* s, double* X) { return get_array(s, "qsp_get_x", X, &qsp_solver::Xo, &Dims::X, &qsp_solver::X); }
+int qsp_get_u(qsp_solver* s, double* U) { return get_array(s, "qsp_get_u", U, &qsp_solver::Uo, &Dims::U, &qsp_solver::U); }
+int qsp_get_pi(qsp_solver* s, double* PI) { return get_array(s, "qsp_get_pi", PI, &qsp_solver::PIo, &Dims::PI, &qsp_solver::PI); }
+int qsp_get_cost(qsp_solver* s, double* c) { return get_array(s, "qsp_get_cost", c, &qsp_solver::cost, &Dims::lane); }
+int qsp_get_status(qsp_solver* s, int32_t* st) { return get_array(s, "qsp_get_status", st, &qsp_solver::status, &Dims::lane); }
+int qsp_get_sqp_iter(qsp_solver* s, int32_t* it) { return get_array(s, "qsp_get_sqp_iter", it, &qsp_solver::sqp_iter, &Dims::lane); }
+int qsp_get_qp_iter(qsp_solver* s, int32_t* it) { return get_array(s, "qsp_get_qp_iter", it, &qsp_solver::qp_iter, &Dims::lane); }
+int qsp_get_qp_capped(qsp_solver* s, int32_t* c) { return get_array(s, "qsp_get_qp_capped", c, &qsp_solver::qp_capped, &Dims::lane); }
+int qsp_get_qp_stalled(qsp_solver* s, int32_t* c) { return get_array(s, "qsp_get_qp_stalled", c, &qsp_solver::qp_stalled, &Dims::lane); }
 int qsp_get_residuals(qsp_solver* s, double* res) {
     if (!s || !res) return fail(QSP_ERR_ARG, "qsp_get_residuals: null argument");
-    if (s->o.nlp_mode != QSP_NLP_SQP_MERIT || !s->wres.p) return fail(QSP_ERR_STATE, "qsp_get_residuals: nlp_mode 1 (SQP) only");
-    return d2h(s, res, s->wres, (size_t)s->o.batch * 4 * 8);
+    if (s->o.nlp_mode != QSP_NLP_SQP_MERIT || !s->wres.data())
+        return fail(QSP_ERR_STATE, "qsp_get_residuals: nlp_mode 1 (SQP) only");
+    return get_array(s, "qsp_get_residuals", res, &qsp_solver::wres, &Dims::res);
 }
 int qsp_get_time_tot(qsp_solver* s, double* ms) {
     if (!s || !ms) return fail(QSP_ERR_ARG, "qsp_get_time_tot: null argument");
@@ -816,29 +759,18 @@ int qsp_set_yref_stage(qsp_solver* s, int32_t k, const double* y) {
     if (k < 0 || k >= s->o.N) return fail(QSP_ERR_ARG, "qsp_set_yref_stage: stage out of range 0..N-1");
     HIPCHK(hipSetDevice(s->o.device));
     // column k of every lane's N x 6 block: a strided copy (B rows of 6 doubles)
-    HIPCHK(hipMemcpy2DAsync(s->yref.as<double>() + (size_t)k * 6, (size_t)s->o.N * 6 * 8, y, 6 * 8, 6 * 8,
-                            (size_t)s->o.batch, hipMemcpyHostToDevice, s->stream));
+    const size_t row = 6 * sizeof(double);
+    HIPCHK(hipMemcpy2DAsync(s->yref.data() + (size_t)k * 6, s->dim.N * row, y, row, row, s->dim.B,
+                            hipMemcpyHostToDevice, s->stream));
     HIPCHK(hipStreamSynchronize(s->stream));
     return QSP_OK;
 }
 
-int qsp_set_yref_e(qsp_solver* s, const double* y_e) {
-    if (!s || !y_e) return fail(QSP_ERR_ARG, "qsp_set_yref_e: null argument");
-    return h2d(s, s->yref_e, y_e, (size_t)s->o.batch * 4 * 8);
-}
+int qsp_set_yref_e(qsp_solver* s, const double* y_e) { return set_array(s, "qsp_set_yref_e", y_e, &qsp_solver::yref_e, &Dims::yref_e); }
 
-int qsp_set_init_x(qsp_solver* s, const double* X) {
-    if (!s || !X) return fail(QSP_ERR_ARG, "qsp_set_init_x: null argument");
-    return h2d(s, s->X, X, (size_t)s->o.batch * (s->o.N + 1) * 4 * 8);
-}
-int qsp_set_init_u(qsp_solver* s, const double* U) {
-    if (!s || !U) return fail(QSP_ERR_ARG, "qsp_set_init_u: null argument");
-    return h2d(s, s->U, U, (size_t)s->o.batch * s->o.N * 2 * 8);
-}
-int qsp_set_init_pi(qsp_solver* s, const double* PI) {
-    if (!s || !PI) return fail(QSP_ERR_ARG, "qsp_set_init_pi: null argument");
-    return h2d(s, s->PI, PI, (size_t)s->o.batch * s->o.N * 4 * 8);
-}
+int qsp_set_init_x(qsp_solver* s, const double* X) { return set_array(s, "qsp_set_init_x", X, &qsp_solver::X, &Dims::X); }
+int qsp_set_init_u(qsp_solver* s, const double* U) { return set_array(s, "qsp_set_init_u", U, &qsp_solver::U, &Dims::U); }
+int qsp_set_init_pi(qsp_solver* s, const double* PI) { return set_array(s, "qsp_set_init_pi", PI, &qsp_solver::PI, &Dims::PI); }
 
 int qsp_set_timing(qsp_solver* s, int32_t on) {
     if (!s) return fail(QSP_ERR_ARG, "qsp_set_timing: null handle");
@@ -867,29 +799,23 @@ int qsp_get_timings(qsp_solver* s, double* time_tot, double* time_lin, double* t
 }
 
 // ------------------------------------------------------ controller level
-int qsp_set_reference_trajectory(qsp_solver* s, const double* traj, int32_t T) {
-    if (!s || !traj || T < 1) return fail(QSP_ERR_ARG, "qsp_set_reference_trajectory: bad argument");
-    HIPCHK(hipSetDevice(s->o.device));
-    HIPCHK(s->traj.ensure((size_t)T * 6 * 8));
-    HIPCHK(hipMemcpyAsync(s->traj.p, traj, (size_t)T * 6 * 8, hipMemcpyHostToDevice, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
+// the reference table of T rows, shared (T x 6) or one per lane (B x T x 6)
+static int set_traj(qsp_solver* s, const char* who, const double* traj, int32_t T, bool per_lane) {
+    if (!s || !traj || T < 1) return fail(QSP_ERR_ARG, std::string(who) + ": bad argument");
+    const int r = h2d_grow(s, s->traj, traj, per_lane ? s->dim.traj_lanes(T) : Dims::traj(T));
+    if (r) return r;
     s->T = T;
     s->have_traj = true;
-    s->traj_per_lane = false;
+    s->traj_per_lane = per_lane;
     return QSP_OK;
 }
 
+int qsp_set_reference_trajectory(qsp_solver* s, const double* traj, int32_t T) {
+    return set_traj(s, "qsp_set_reference_trajectory", traj, T, false);
+}
+
 int qsp_set_reference_trajectories(qsp_solver* s, const double* traj, int32_t T) {
-    if (!s || !traj || T < 1) return fail(QSP_ERR_ARG, "qsp_set_reference_trajectories: bad argument");
-    const size_t bytes = (size_t)s->o.batch * T * 6 * 8;
-    HIPCHK(hipSetDevice(s->o.device));
-    HIPCHK(s->traj.ensure(bytes));
-    HIPCHK(hipMemcpyAsync(s->traj.p, traj, bytes, hipMemcpyHostToDevice, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    s->T = T;
-    s->have_traj = true;
-    s->traj_per_lane = true;
-    return QSP_OK;
+    return set_traj(s, "qsp_set_reference_trajectories", traj, T, true);
 }
 
 int qsp_gen_straight_lines(qsp_solver* s, const double* x0, const double* xf, double t0, double tf,
@@ -903,8 +829,8 @@ int qsp_gen_straight_lines(qsp_solver* s, const double* x0, const double* xf, do
     const double* d0 = st.in(x0, B * 3);
     const double* d1 = st.in(xf, B * 3);
     if (st.err) return st.err;
-    HIPCHK(s->traj.ensure(B * (size_t)T * 6 * 8));
-    HIPCHK(launch_straight_lines((int)B, T, d0, d1, t0, tf, s->o.Ts, auto_angle, s->traj.as<double>(), s->stream));
+    HIPCHK(s->traj.ensure(s->dim.traj_lanes(T)));
+    HIPCHK(launch_straight_lines((int)B, T, d0, d1, t0, tf, s->o.Ts, auto_angle, s->traj.data(), s->stream));
     if (st.finish()) return st.err;
     s->T = T;
     s->have_traj = true;
@@ -916,14 +842,13 @@ int qsp_gen_straight_lines(qsp_solver* s, const double* x0, const double* xf, do
 int qsp_get_reference_trajectories(qsp_solver* s, double* traj) {
     if (!s || !traj) return fail(QSP_ERR_ARG, "qsp_get_reference_trajectories: null argument");
     if (!s->have_traj) return fail(QSP_ERR_STATE, "qsp_get_reference_trajectories: no reference trajectory");
-    const size_t n = (s->traj_per_lane ? (size_t)s->o.batch : 1) * s->T * 6 * 8;
-    return d2h(s, traj, s->traj, n);
+    return d2h(s, traj, s->traj, s->traj_per_lane ? s->dim.traj_lanes(s->T) : Dims::traj(s->T));
 }
 
 int qsp_controller_reset(qsp_solver* s) {
     if (!s) return fail(QSP_ERR_ARG, "qsp_controller_reset: null handle");
     HIPCHK(hipSetDevice(s->o.device));
-    HIPCHK(hipMemsetAsync(s->warm_valid.p, 0, (size_t)s->o.batch, s->stream));
+    HIPCHK(s->warm_valid.fill(s->stream, 0, s->dim.lane()));
     HIPCHK(hipStreamSynchronize(s->stream));
     return QSP_OK;
 }
@@ -932,11 +857,10 @@ int qsp_controller_solve(qsp_solver* s, const double* x0, const int32_t* index_t
     if (!s || !x0 || !index_time) return fail(QSP_ERR_ARG, "qsp_controller_solve: null argument");
     if (!s->have_traj) return fail(QSP_ERR_STATE, "qsp_controller_solve: no reference trajectory");
     if (s->n_shapes < 1) return fail(QSP_ERR_STATE, "qsp_controller_solve: no shapes set");
-    const size_t B = s->o.batch;
     HIPCHK(hipSetDevice(s->o.device));
-    HIPCHK(s->index_time.ensure(B * 4));
-    HIPCHK(hipMemcpyAsync(s->x0.p, x0, B * 4 * 8, hipMemcpyHostToDevice, s->stream));
-    HIPCHK(hipMemcpyAsync(s->index_time.p, index_time, B * 4, hipMemcpyHostToDevice, s->stream));
+    HIPCHK(s->index_time.ensure(s->dim.lane()));
+    HIPCHK(s->x0.upload(s->stream, x0, s->dim.x0()));
+    HIPCHK(s->index_time.upload(s->stream, index_time, s->dim.lane()));
     HIPCHK(launch_controller_step(s, 0));
     return run_timed(s, controller_args(s));
 }
@@ -948,9 +872,9 @@ int qsp_set_delay_comp(qsp_solver* s, double delay) {
     if (cols > 4096.0) return fail(QSP_ERR_ARG, "qsp_set_delay_comp: more than 4096 delay samples");
     HIPCHK(hipSetDevice(s->o.device));
     s->D = (int32_t)cols;
-    const size_t bytes = (size_t)s->o.batch * (size_t)(s->D > 0 ? s->D : 1) * 2 * 8;
-    HIPCHK(s->ubc.ensure(bytes));
-    HIPCHK(hipMemsetAsync(s->ubc.p, 0, bytes, s->stream));   // u_buff_contr = zeros (:109)
+    const size_t n = s->dim.delay(s->D > 0 ? s->D : 1);
+    HIPCHK(s->ubc.ensure(n));
+    HIPCHK(s->ubc.fill(s->stream, 0, n));   // u_buff_contr = zeros (:109)
     HIPCHK(hipStreamSynchronize(s->stream));
     return QSP_OK;
 }
@@ -964,33 +888,32 @@ int qsp_get_delay_comp(qsp_solver* s, int32_t* cols) {
 static ClosedLoopArgs cl_args(qsp_solver* s) {
     ClosedLoopArgs a;
     std::memset(&a, 0, sizeof a);
-    a.shapes = s->shapes.as<ShapeDev>();
+    a.shapes = s->shapes.data();
     a.n_shapes = s->n_shapes;
-    a.sid = s->shape_id.as<int32_t>();
+    a.sid = s->shape_id.data();
     a.B = s->o.batch;
     a.Ts = s->o.Ts;
     a.D = s->D;
-    a.ubc = s->ubc.as<double>();
+    a.ubc = s->ubc.data();
     // the plant's own model, where one is installed (else nullptr: the controller's)
     if (s->n_pshapes > 0) {
-        a.pshapes = s->pshapes.as<ShapeDev>();
+        a.pshapes = s->pshapes.data();
         a.n_pshapes = s->n_pshapes;
-        a.psid = s->has_pids ? s->pshape_id.as<int32_t>() : nullptr;
+        a.psid = s->has_pids ? s->pshape_id.data() : nullptr;
     }
-    a.pmu = s->has_pmu ? s->pmu.as<double>() : nullptr;
-    a.pc = s->has_pc ? s->pc.as<double>() : nullptr;
+    a.pmu = s->has_pmu ? s->pmu.data() : nullptr;
+    a.pc = s->has_pc ? s->pc.data() : nullptr;
     return a;
 }
 
 int qsp_delay_buffer_sim(qsp_solver* s, const double* x, double* x_sim) {
     if (!s || !x || !x_sim) return fail(QSP_ERR_ARG, "qsp_delay_buffer_sim: null argument");
     if (s->n_shapes < 1) return fail(QSP_ERR_STATE, "qsp_delay_buffer_sim: no shapes set");
-    const size_t B = s->o.batch;
     HIPCHK(hipSetDevice(s->o.device));
     Staging st(s);
     ClosedLoopArgs a = cl_args(s);
-    a.x = st.in(x, B * 4);
-    a.xs = st.out(x_sim, B * 4);
+    a.x = st.in(x, s->dim.x0());
+    a.xs = st.out(x_sim, s->dim.x0());
     if (st.err) return st.err;
     HIPCHK(launch_delay_sim(a, s->stream));
     return st.finish();
@@ -1000,19 +923,16 @@ int qsp_delay_buffer_push(qsp_solver* s, const double* u) {
     if (!s || !u) return fail(QSP_ERR_ARG, "qsp_delay_buffer_push: null argument");
     if (s->D == 0) return QSP_OK;
     const size_t B = s->o.batch, D = (size_t)s->D;
-    std::vector<double> h(B * D * 2);
-    HIPCHK(hipSetDevice(s->o.device));
-    HIPCHK(hipMemcpyAsync(h.data(), s->ubc.p, h.size() * 8, hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
+    std::vector<double> h(s->dim.delay(D));
+    int r = d2h(s, h.data(), s->ubc, h.size());
+    if (r) return r;
     for (size_t i = 0; i < B; ++i) {   // u_buff_contr = [u, u_buff_contr(:, 1:end-1)]  (helper.m:255)
         double* b = h.data() + i * D * 2;
-        std::memmove(b + 2, b, (D - 1) * 2 * 8);
+        std::memmove(b + 2, b, (D - 1) * 2 * sizeof(double));
         b[0] = u[2 * i];
         b[1] = u[2 * i + 1];
     }
-    HIPCHK(hipMemcpyAsync(s->ubc.p, h.data(), h.size() * 8, hipMemcpyHostToDevice, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    return QSP_OK;
+    return h2d(s, s->ubc, h.data(), h.size());
 }
 
 static_assert(CL_NMETRICS == QSP_CL_NMETRICS, "metric columns of the kernel and of the header");
@@ -1032,58 +952,58 @@ static int closed_loop_run(qsp_solver* s, const char* who, const qsp_closed_loop
     if (!(plant_delay >= 0.0) || std::ceil(plant_delay / s->o.Ts) > 4096.0)
         return fail(QSP_ERR_ARG, w + ": plant_delay must be in [0, 4096 Ts]");
     if (o && o->disturbance && o->t_dist < 1) return fail(QSP_ERR_ARG, w + ": t_dist must be >= 1");
-    const size_t B = s->o.batch, T = (size_t)n_steps;
+    const Dims& d = s->dim;
+    const size_t T = (size_t)n_steps;
     const int Dp = (int)std::ceil(plant_delay / s->o.Ts);   // delay_buff_plant (helper.m:211)
     HIPCHK(hipSetDevice(s->o.device));
-    DevBuf &dX = s->cl_xtraj, &dU = s->cl_utraj, &dS = s->cl_straj, &dN = s->cl_noise, &dXs = s->cl_xsim;
     if (want_traj) {
-        HIPCHK(dX.ensure(B * (T + 1) * 4 * 8));
-        HIPCHK(dU.ensure(B * T * 2 * 8));
-        HIPCHK(dS.ensure(B * T * 4));
+        HIPCHK(s->cl_xtraj.ensure(d.cl_X(T)));
+        HIPCHK(s->cl_utraj.ensure(d.cl_U(T)));
+        HIPCHK(s->cl_straj.ensure(d.cl_status(T)));
     }
-    if (want_xsim) HIPCHK(dXs.ensure(B * T * 4 * 8));
-    if (want_metrics) HIPCHK(s->cl_metrics.ensure(B * QSP_CL_NMETRICS * 8));
-    if (noise) HIPCHK(dN.ensure(T * B * 4 * 8));
-    HIPCHK(s->cl_x.ensure(B * 4 * 8));
-    HIPCHK(s->ubp.ensure(B * (size_t)(Dp > 0 ? Dp : 1) * 2 * 8));
-    if (s->D > 0) HIPCHK(s->ubc.ensure(B * (size_t)s->D * 2 * 8));
-    HIPCHK(s->index_time.ensure(B * 4));
-    HIPCHK(hipMemcpyAsync(s->cl_x.p, x0, B * 4 * 8, hipMemcpyHostToDevice, s->stream));
-    HIPCHK(hipMemcpyAsync(s->index_time.p, index0, B * 4, hipMemcpyHostToDevice, s->stream));
-    if (noise) HIPCHK(hipMemcpyAsync(dN.p, noise, T * B * 4 * 8, hipMemcpyHostToDevice, s->stream));
+    if (want_xsim) HIPCHK(s->cl_xsim.ensure(d.cl_Xsim(T)));
+    if (want_metrics) HIPCHK(s->cl_metrics.ensure(d.metrics()));
+    if (noise) HIPCHK(s->cl_noise.ensure(d.cl_noise(T)));
+    HIPCHK(s->cl_x.ensure(d.x0()));
+    HIPCHK(s->ubp.ensure(d.delay(Dp > 0 ? Dp : 1)));
+    if (s->D > 0) HIPCHK(s->ubc.ensure(d.delay(s->D)));
+    HIPCHK(s->index_time.ensure(d.lane()));
+    HIPCHK(s->cl_x.upload(s->stream, x0, d.x0()));
+    HIPCHK(s->index_time.upload(s->stream, index0, d.lane()));
+    if (noise) HIPCHK(s->cl_noise.upload(s->stream, noise, d.cl_noise(T)));
     const bool dist = o && o->disturbance;
     if (dist && o->amplitude) {
-        HIPCHK(s->cl_amp.ensure(B * 8));
-        HIPCHK(hipMemcpyAsync(s->cl_amp.p, o->amplitude, B * 8, hipMemcpyHostToDevice, s->stream));
+        HIPCHK(s->cl_amp.ensure(d.lane()));
+        HIPCHK(s->cl_amp.upload(s->stream, o->amplitude, d.lane()));
     }
     // initial_condition_update -> clear_variables: the first solve is a cold start (main.m:79);
     // the plant's buffer starts at zero (closed_loop_matlab's u_buff_plant, helper.m:211-212); the
     // controller's u_buff_contr is left as it is: the reference zeroes it only in set_delay_comp
     // (NMPC_controller.m:106-110; qsp_set_delay_comp), so a second run continues from the first's
-    HIPCHK(hipMemsetAsync(s->warm_valid.p, 0, B, s->stream));
-    if (Dp > 0) HIPCHK(hipMemsetAsync(s->ubp.p, 0, B * (size_t)Dp * 2 * 8, s->stream));
-    if (want_metrics) HIPCHK(hipMemsetAsync(s->cl_metrics.p, 0, B * QSP_CL_NMETRICS * 8, s->stream));
+    HIPCHK(s->warm_valid.fill(s->stream, 0, d.lane()));
+    if (Dp > 0) HIPCHK(s->ubp.fill(s->stream, 0, d.delay(Dp)));
+    if (want_metrics) HIPCHK(s->cl_metrics.fill(s->stream, 0, d.metrics()));
     ClosedLoopArgs c = cl_args(s);
     c.n_steps = n_steps;
-    c.x = s->cl_x.as<double>();
-    c.xs = s->x0.as<double>();                 // the solver's x0 (constr_x0)
-    c.noise = noise ? dN.as<double>() : nullptr;
+    c.x = s->cl_x.data();
+    c.xs = s->x0.data();                 // the solver's x0 (constr_x0)
+    c.noise = noise ? s->cl_noise.data() : nullptr;
     c.dist_step = dist ? o->t_dist : 0;
-    c.dist_amp = (dist && o->amplitude) ? s->cl_amp.as<double>() : nullptr;
+    c.dist_amp = (dist && o->amplitude) ? s->cl_amp.data() : nullptr;
     c.Dp = Dp;
-    c.ubp = s->ubp.as<double>();
-    c.u0 = s->u0.as<double>();
-    c.status = s->status.as<int32_t>();
-    c.Xtraj = want_traj ? dX.as<double>() : nullptr;
-    c.Xsim = want_xsim ? dXs.as<double>() : nullptr;
-    c.Utraj = want_traj ? dU.as<double>() : nullptr;
-    c.Straj = want_traj ? dS.as<int32_t>() : nullptr;
+    c.ubp = s->ubp.data();
+    c.u0 = s->u0.data();
+    c.status = s->status.data();
+    c.Xtraj = want_traj ? s->cl_xtraj.data() : nullptr;
+    c.Xsim = want_xsim ? s->cl_xsim.data() : nullptr;
+    c.Utraj = want_traj ? s->cl_utraj.data() : nullptr;
+    c.Straj = want_traj ? s->cl_straj.data() : nullptr;
     if (want_metrics) {
-        c.metrics = s->cl_metrics.as<double>();
-        c.mtraj = s->traj.as<double>();
+        c.metrics = s->cl_metrics.data();
+        c.mtraj = s->traj.data();
         c.mT = s->T;
         c.mper_lane = s->traj_per_lane ? 1 : 0;
-        c.index0 = s->index_time.as<int32_t>();
+        c.index0 = s->index_time.data();
         c.s_lo = s->p.lh[0];
         c.s_hi = s->p.uh[0];
     }
@@ -1113,11 +1033,11 @@ int qsp_closed_loop_ex(qsp_solver* s, const qsp_closed_loop_opts* o, const doubl
         return fail(QSP_ERR_ARG, "qsp_closed_loop: bad argument");
     const int r = closed_loop_run(s, "qsp_closed_loop", o, x0, index0, n_steps, noise, true, X_sim != nullptr, false);
     if (r) return r;
-    const size_t B = s->o.batch, T = (size_t)n_steps;
-    HIPCHK(hipMemcpyAsync(X_traj, s->cl_xtraj.p, B * (T + 1) * 4 * 8, hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(hipMemcpyAsync(U_traj, s->cl_utraj.p, B * T * 2 * 8, hipMemcpyDeviceToHost, s->stream));
-    if (X_sim) HIPCHK(hipMemcpyAsync(X_sim, s->cl_xsim.p, B * T * 4 * 8, hipMemcpyDeviceToHost, s->stream));
-    if (status_traj) HIPCHK(hipMemcpyAsync(status_traj, s->cl_straj.p, B * T * 4, hipMemcpyDeviceToHost, s->stream));
+    const size_t T = (size_t)n_steps;
+    HIPCHK(s->cl_xtraj.download(s->stream, X_traj, s->dim.cl_X(T)));
+    HIPCHK(s->cl_utraj.download(s->stream, U_traj, s->dim.cl_U(T)));
+    if (X_sim) HIPCHK(s->cl_xsim.download(s->stream, X_sim, s->dim.cl_Xsim(T)));
+    if (status_traj) HIPCHK(s->cl_straj.download(s->stream, status_traj, s->dim.cl_status(T)));
     return closed_loop_done(s);
 }
 
@@ -1128,10 +1048,9 @@ int qsp_closed_loop_metrics(qsp_solver* s, const qsp_closed_loop_opts* o, const 
         return fail(QSP_ERR_ARG, "qsp_closed_loop_metrics: bad argument");
     const int r = closed_loop_run(s, "qsp_closed_loop_metrics", o, x0, index0, n_steps, noise, false, false, true);
     if (r) return r;
-    const size_t B = s->o.batch;
-    HIPCHK(hipMemcpyAsync(metrics, s->cl_metrics.p, B * QSP_CL_NMETRICS * 8, hipMemcpyDeviceToHost, s->stream));
-    if (x_end) HIPCHK(hipMemcpyAsync(x_end, s->cl_x.p, B * 4 * 8, hipMemcpyDeviceToHost, s->stream));
-    if (status_last) HIPCHK(hipMemcpyAsync(status_last, s->status.p, B * 4, hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(s->cl_metrics.download(s->stream, metrics, s->dim.metrics()));
+    if (x_end) HIPCHK(s->cl_x.download(s->stream, x_end, s->dim.x0()));
+    if (status_last) HIPCHK(s->status.download(s->stream, status_last, s->dim.lane()));
     return closed_loop_done(s);
 }
 
@@ -1151,7 +1070,7 @@ int qsp_reproject_contact(qsp_solver* s, int32_t n, const int32_t* sid, const do
     const double *d_px = st.in(px, n), *d_py = st.in(py, n), *d_s0 = st.in(s0, n);
     double* d_s = st.out(s_out, n);
     if (st.err) return st.err;
-    HIPCHK(launch_reproject(s->shapes.as<ShapeDev>(), s->n_shapes, d_sid, n, d_px, d_py, d_s0, d_s, s->stream));
+    HIPCHK(launch_reproject(s->shapes.data(), s->n_shapes, d_sid, n, d_px, d_py, d_s0, d_s, s->stream));
     return st.finish();
 }
 
@@ -1170,7 +1089,7 @@ int qsp_solve_device(qsp_solver* s, const qsp_device_io* io, void* stream) {
     a.X_in = io->X_in;
     a.U_in = io->U_in;
     a.PI_in = io->PI_in;
-    a.shape_id = io->shape_id ? io->shape_id : s->shape_id.as<int32_t>();
+    a.shape_id = io->shape_id ? io->shape_id : s->shape_id.data();
     a.u0 = io->u0;
     a.X_out = io->X_out;
     a.U_out = io->U_out;
@@ -1270,7 +1189,7 @@ int qsp_eval_spline(qsp_solver* s, int32_t n, const int32_t* sid, const double* 
     double *dC = st.out(C, (size_t)2 * n), *dD = st.out(D, (size_t)2 * n), *dDd = st.out(Dd, (size_t)2 * n);
     double* dk = st.out(kappa, n);
     if (st.err) return st.err;
-    HIPCHK(launch_spline(s->shapes.as<ShapeDev>(), d_sid, n, d_sig, dC, dD, dDd, dk, s->stream));
+    HIPCHK(launch_spline(s->shapes.data(), d_sid, n, d_sig, dC, dD, dDd, dk, s->stream));
     return st.finish();
 }
 
@@ -1285,7 +1204,7 @@ int qsp_eval_dynamics(qsp_solver* s, int32_t n, const int32_t* sid, const double
     const double *dx = st.in(x, (size_t)4 * n), *du = st.in(u, (size_t)2 * n);
     double *df = st.out(f, (size_t)4 * n), *dJ = st.out(J, (size_t)24 * n);
     if (st.err) return st.err;
-    HIPCHK(launch_dynamics(s->shapes.as<ShapeDev>(), d_sid, n, dx, du, df, dJ, s->stream));
+    HIPCHK(launch_dynamics(s->shapes.data(), d_sid, n, dx, du, df, dJ, s->stream));
     return st.finish();
 }
 
@@ -1300,7 +1219,7 @@ int qsp_eval_rk4(qsp_solver* s, int32_t n, const int32_t* sid, double h, const d
     const double *dx = st.in(x, (size_t)4 * n), *du = st.in(u, (size_t)2 * n);
     double *dxn = st.out(xn, (size_t)4 * n), *dA = st.out(A, (size_t)16 * n), *dB = st.out(B, (size_t)8 * n);
     if (st.err) return st.err;
-    HIPCHK(launch_rk4(s->shapes.as<ShapeDev>(), d_sid, n, h, dx, du, dxn, dA, dB, s->stream));
+    HIPCHK(launch_rk4(s->shapes.data(), d_sid, n, h, dx, du, dxn, dA, dB, s->stream));
     return st.finish();
 }
 
@@ -1314,7 +1233,7 @@ int qsp_eval_vbound(qsp_solver* s, int32_t n, const int32_t* sid, const double* 
     const double* ds = st.in(sv, n);
     double* dvb = st.out(vb, n);
     if (st.err) return st.err;
-    HIPCHK(launch_vbound(s->shapes.as<ShapeDev>(), d_sid, n, s->p.cp, ds, dvb, s->stream));
+    HIPCHK(launch_vbound(s->shapes.data(), d_sid, n, s->p.cp, ds, dvb, s->stream));
     return st.finish();
 }
 
@@ -1350,23 +1269,24 @@ int qsp_qp_solve(qsp_solver* s, int32_t nb, const double* A, const double* B, co
                 return fail(QSP_ERR_ARG, "qsp_qp_solve: terminal Hessian must be equal on every lane");
     }
     // pack the workspace on the host: stage data SoA, v = -lo through X/U, x0 - X_0 = dx0
-    const size_t tot = (size_t)nb * (N + 1);
-    std::vector<double> lin(tot * 24, 0.0), X(tot * 4, 0.0), U((size_t)nb * N * 2, 0.0), x0(dx0, dx0 + (size_t)nb * 4);
+    const Dims qd{(size_t)nb, (size_t)N};   // the QPs' own batch
+    const size_t tot = qd.stages();
+    std::vector<double> lin(qd.lin(), 0.0), X(qd.X(), 0.0), U(qd.U(), 0.0), x0(dx0, dx0 + qd.x0());
     for (int l = 0; l < nb; ++l) {
         for (int k = 0; k <= N; ++k) {
             const size_t gi = (size_t)l * (N + 1) + k;
             if (k < N) {
                 const double* Ak = A + ((size_t)l * N + k) * 16;
                 const double av[6] = {Ak[2], Ak[3], Ak[6], Ak[7], Ak[11], Ak[15]};
-                for (int q = 0; q < 6; ++q) lin[(0 + q) * tot + gi] = av[q];
-                for (int q = 0; q < 8; ++q) lin[(6 + q) * tot + gi] = B[((size_t)l * N + k) * 8 + q];
-                for (int q = 0; q < 4; ++q) lin[(14 + q) * tot + gi] = b[((size_t)l * N + k) * 4 + q];
-                for (int q = 0; q < 6; ++q) lin[(18 + q) * tot + gi] = g[(size_t)l * (6 * N + 4) + 6 * k + q];
+                for (int f = 0; f < 6; ++f) lin[(L_A + f) * tot + gi] = av[f];
+                for (int f = 0; f < 8; ++f) lin[(L_B + f) * tot + gi] = B[((size_t)l * N + k) * 8 + f];
+                for (int f = 0; f < 4; ++f) lin[(L_BB + f) * tot + gi] = b[((size_t)l * N + k) * 4 + f];
+                for (int f = 0; f < 6; ++f) lin[(L_G + f) * tot + gi] = g[(size_t)l * (6 * N + 4) + 6 * k + f];
                 X[gi * 4 + 3] = -lo[((size_t)l * N + k) * 3 + 0];
                 U[((size_t)l * N + k) * 2 + 0] = -lo[((size_t)l * N + k) * 3 + 1];
                 U[((size_t)l * N + k) * 2 + 1] = -lo[((size_t)l * N + k) * 3 + 2];
             } else {
-                for (int q = 0; q < 4; ++q) lin[(18 + q) * tot + gi] = g[(size_t)l * (6 * N + 4) + 6 * N + q];
+                for (int f = 0; f < 4; ++f) lin[(L_G + f) * tot + gi] = g[(size_t)l * (6 * N + 4) + 6 * N + f];
             }
         }
         // dx0 = wx0 - X_0 with X_0 = (0, 0, 0, -lo_s(0))  ->  wx0 = dx0 + X_0
@@ -1383,12 +1303,12 @@ int qsp_qp_solve(qsp_solver* s, int32_t nb, const double* A, const double* B, co
     a.wX = st.in(X.data(), X.size());
     a.wU = st.in(U.data(), U.size());
     a.wx0 = st.in(x0.data(), x0.size());
-    a.qp_dx = st.out(dx, (size_t)nb * (N + 1) * 4);
-    a.qp_du = st.out(du, (size_t)nb * N * 2);
-    a.PI_out = st.out(pi, (size_t)nb * N * 4);
-    a.qp_lam = st.out(lam, (size_t)nb * N * 6);
-    a.qp_iter = st.out(iters, (size_t)nb);
-    a.qp_capped = st.out(qst.data(), (size_t)nb);
+    a.qp_dx = st.out(dx, qd.X());
+    a.qp_du = st.out(du, qd.U());
+    a.PI_out = st.out(pi, qd.PI());
+    a.qp_lam = st.out(lam, qd.lam());
+    a.qp_iter = st.out(iters, qd.lane());
+    a.qp_capped = st.out(qst.data(), qd.lane());
     if (st.err) return st.err;
     HIPCHK(launch_qp(a, s->S, s->stream));
     if (st.finish()) return st.err;
@@ -1435,11 +1355,11 @@ static int rollout_args(qsp_solver* s, const qsp_rollout_opts* o, const char* wh
     std::memcpy(a.We, s->p.We, sizeof a.We);
     std::memcpy(a.lh, s->p.lh, sizeof a.lh);
     std::memcpy(a.uh, s->p.uh, sizeof a.uh);
-    a.shapes = s->shapes.as<ShapeDev>();
+    a.shapes = s->shapes.data();
     a.n_shapes = s->n_shapes;
-    a.shape_id = s->shape_id.as<int32_t>();
-    a.yref = s->yref.as<double>();
-    a.yref_e = s->yref_e.as<double>();
+    a.shape_id = s->shape_id.data();
+    a.yref = s->yref.data();
+    a.yref_e = s->yref_e.data();
     return QSP_OK;
 }
 
@@ -1463,11 +1383,11 @@ static int rollout_cost_run(qsp_solver* s, const qsp_rollout_opts* opts, const c
     qsp_rollout_io d = *io;
     Staging st(s);
     if (host) {
-        const size_t B = s->o.batch, N = s->o.N, BM = B * (size_t)M;
-        d.x0 = st.in(io->x0, B * 4);
+        const size_t N = s->dim.N, BM = s->dim.B * (size_t)M;
+        d.x0 = st.in(io->x0, s->dim.x0());
         d.U = st.in(io->U, BM * N * 2);
-        d.yref = st.in(io->yref, B * N * 6);
-        d.yref_e = st.in(io->yref_e, B * 4);
+        d.yref = st.in(io->yref, s->dim.yref());
+        d.yref_e = st.in(io->yref_e, s->dim.yref_e());
         d.cost = st.out(io->cost, BM);
         d.viol = st.out(io->viol, BM);
         d.x_end = st.out(io->x_end, BM * 4);
@@ -1513,21 +1433,21 @@ static int cost_landscape_run(qsp_solver* s, const qsp_rollout_opts* opts, const
     qsp_landscape_io d = *io;
     Staging st(s);
     if (host) {
-        const size_t B = s->o.batch, N = s->o.N, G = (size_t)io->n_un * io->n_ut;
-        d.x0 = st.in(io->x0, B * 4);
-        d.U_tail = st.in(io->U_tail, B * N * 2);
+        const size_t B = s->dim.B, G = (size_t)io->n_un * io->n_ut;
+        d.x0 = st.in(io->x0, s->dim.x0());
+        d.U_tail = st.in(io->U_tail, s->dim.U());
         d.un_grid = st.in(io->un_grid, (size_t)io->n_un);
         d.ut_grid = st.in(io->ut_grid, (size_t)io->n_ut);
-        d.yref = st.in(io->yref, B * N * 6);
-        d.yref_e = st.in(io->yref_e, B * 4);
+        d.yref = st.in(io->yref, s->dim.yref());
+        d.yref_e = st.in(io->yref_e, s->dim.yref_e());
         d.cost = st.out(io->cost, B * G);
-        d.u_min = st.out(io->u_min, B * 2);
+        d.u_min = st.out(io->u_min, s->dim.u0());
         d.cost_min = st.out(io->cost_min, B);
         d.idx_min = st.out(io->idx_min, B);
         if (st.err) return st.err;
     }
     a.x0 = d.x0;
-    a.U_tail = d.U_tail ? d.U_tail : s->wU.as<double>();   // the iterate epilogue_kernel reads
+    a.U_tail = d.U_tail ? d.U_tail : s->wU.data();   // the iterate epilogue_kernel reads
     if (d.yref) a.yref = d.yref;
     if (d.yref_e) a.yref_e = d.yref_e;
     if (d.shape_id) a.shape_id = d.shape_id;
@@ -1568,7 +1488,7 @@ int qsp_eval_modes(qsp_solver* s, int32_t n, const int32_t* sid, const double* x
     int32_t* d_mode = st.out(mode, n);
     double* d_cone = st.out(cone, (size_t)3 * n);
     if (st.err) return st.err;
-    HIPCHK(launch_modes(s->shapes.as<ShapeDev>(), s->n_shapes, d_sid, n, 1, 1, dx, du, d_mode, d_cone, s->stream));
+    HIPCHK(launch_modes(s->shapes.data(), s->n_shapes, d_sid, n, 1, 1, dx, du, d_mode, d_cone, s->stream));
     return st.finish();
 }
 
@@ -1582,10 +1502,10 @@ int qsp_get_modes(qsp_solver* s, int32_t* mode, double* cone) {
     double* d_cone = st.out(cone, 3 * n);
     if (st.err) return st.err;
     // the buffers qsp_get_x / qsp_get_u copy out
-    const DevBuf& X = s->last_controller ? s->X : s->Xo;
-    const DevBuf& U = s->last_controller ? s->U : s->Uo;
-    HIPCHK(launch_modes(s->shapes.as<ShapeDev>(), s->n_shapes, s->shape_id.as<int32_t>(), (long long)n, s->o.N, s->o.N + 1,
-                        X.as<double>(), U.as<double>(), d_mode, d_cone, s->stream));
+    const Dev<double>& X = s->last_controller ? s->X : s->Xo;
+    const Dev<double>& U = s->last_controller ? s->U : s->Uo;
+    HIPCHK(launch_modes(s->shapes.data(), s->n_shapes, s->shape_id.data(), (long long)n, s->o.N, s->o.N + 1,
+                        X.data(), U.data(), d_mode, d_cone, s->stream));
     return st.finish();
 }
 
@@ -1627,13 +1547,13 @@ static int open_loop_args(qsp_solver* s, const qsp_open_loop_opts* o, const char
     a.tile = o->store_tile;
     a.Ts = Ts;
     a.v_alpha = o->v_alpha;
-    a.shapes = s->shapes.as<ShapeDev>();
+    a.shapes = s->shapes.data();
     a.n_shapes = s->n_shapes;
-    a.shape_id = s->shape_id.as<int32_t>();
+    a.shape_id = s->shape_id.data();
     HIPCHK(hipSetDevice(s->o.device));
     if (a.clip && a.D > 0) {
-        HIPCHK(s->ol_ring.ensure((size_t)a.D * a.B * a.M * 8));
-        a.ring = s->ol_ring.as<double>();
+        HIPCHK(s->ol_ring.ensure(s->dim.ring(a.D, a.M)));
+        a.ring = s->ol_ring.data();
     }
     return QSP_OK;
 }

@@ -12,6 +12,16 @@
 
 namespace qsp {
 
+// Layout of SolveArgs' workspace, for the kernels that index it (qsp_solver.hip) and the host that sizes and
+// packs it (qsp_devbuf.hpp, qsp_capi.hip).  wlin, wnlp and wqp are SoA over (instance, stage): field f of
+// stage k of instance i at f * B(N+1) + i(N+1) + k.
+enum LinField : int { L_A = 0, L_B = 6, L_BB = 14, L_G = 18, L_COUNT = 24 };               // wlin
+enum NlpField : int { W_PI = 0, W_LAM = 4, W_NU = 10, W_ETA = 14, W_COUNT = 20 };          // wnlp (nlp_mode 1)
+enum QpField : int { Q_DX = 0, Q_DU = 4, Q_PI = 6, Q_LAM = 10, Q_COUNT = 16 };             // wqp (nlp_mode 1)
+constexpr int ADJ_REC = 11;                         // wadj: doubles per stage 1..N of the adjoint record
+constexpr int PACK_KEYS_MAX = 1024;                 // whist: (maxkey + 1)^2 wave-packing keys
+constexpr int WHIST_PER_PART = 4 * PACK_KEYS_MAX;   // whist of one part of the SQP loop (launch_sqp)
+
 struct SolveArgs {
     SolveParams p;
     int32_t B;
@@ -44,8 +54,8 @@ struct SolveArgs {
     double* wX;                // B x (N+1) x 4   SQP iterate
     double* wU;                // B x N x 2
     double* wx0;               // B x 4           x0 after the controller's s pre-wrap
-    double* wlin;              // 24 x B(N+1)     stage data (A, B, defect, gradient), SoA
-    double* wnlp;              // 20 x B(N+1)     nlp_mode 1: PI(4), LAM(6), merit weights NU(4), ETA(6), SoA
+    double* wlin;              // 24 x B(N+1)     stage data (A, B, defect, gradient), SoA (LinField)
+    double* wnlp;              // 20 x B(N+1)     nlp_mode 1: PI(4), LAM(6), merit weights NU(4), ETA(6), SoA (NlpField)
     int32_t* wdone;            // B               nlp_mode 1: converged (KKT tolerances met)
     double* wres;              // B x 4           nlp_mode 1: the last KKT test's residuals (stat, eq, ineq, comp;
                                //                 nullptr: not recorded).  At max_iter (status 2) that is the test
@@ -57,7 +67,7 @@ struct SolveArgs {
     int32_t* whist;            // 4 x 1024        per parity of the SQP iteration: histogram of the wave-packing
                                //                 keys (accumulated by the QP kernel) and running scatter offsets
     double* wadj;              // B x N x 11      nlp_mode 0: adjoint record of the instance's last successful QP
-                               //                 (ADJ_REC doubles per stage 1..N, instance-major; qsp_solver.hip)
+                               //                 (ADJ_REC doubles per stage 1..N, instance-major)
     int32_t* wadjv;            // B               nlp_mode 0: the record is valid (a QP of this solve wrote it)
     // QP-level interface only (qsp_qp_solve): when qp_dx != nullptr the QP kernel
     // reports the QP solution instead of updating the iterate

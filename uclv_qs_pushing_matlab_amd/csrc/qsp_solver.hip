@@ -157,7 +157,7 @@ __device__ __forceinline__ int sidx(int i, int j) {
 // ties by c2.  Over 50 SQP iterations of 3 072 bench lanes (3 instances per wave) waves then
 // run 1.060x the mean iteration count, against 1.065x ordering by (c1, c2), 1.094x by c1 alone
 // and 1.244x unsorted (perfect prediction: 1.001x).
-constexpr int PACK_KEYS_MAX = 1024;   // (maxkey + 1)^2 keys
+// PACK_KEYS_MAX = (maxkey + 1)^2 keys (qsp_kernels.h).
 // key levels: IPM counts above 31 share the last level (qp_iters up to 50 and more: the
 // acados default cap; such QPs are rare, ~0.1 % of the bench workload's)
 __host__ __device__ __forceinline__ int pack_maxkey(int qp_iters) { return qp_iters < 31 ? qp_iters : 31; }
@@ -1566,7 +1566,6 @@ __device__ __forceinline__ void qp_adjoint_store(const Ctx& c, const SolveParams
 // adjoint_step in its order, so PI keeps its bits.
 //   stage 1 <= k < N, at (k - 1) ADJ_REC: c_i = tau W_i dx_k,i + g_k,i (4), a_k (6), (lam_hi - lam_lo)_s
 //   stage N, at (N - 1) ADJ_REC:          pi_{N-1} = We dx_N + g_N (4)
-constexpr int ADJ_REC = 11;
 
 template <int S>
 __device__ __forceinline__ void qp_adjoint_record(const Ctx& c, const SolveParams& p, const Stage<S>& st, double* rec) {
@@ -1619,16 +1618,12 @@ __device__ __forceinline__ void adjoint_from_record(int N, const double* rec, do
 
 // ------------------------------------------------------------------ kernels
 // One solve = prologue, K x (linearize, qp), epilogue; all on one stream.
-// Workspace (SolveArgs::w*): SQP iterate X/U, wrapped x0, stage data in SoA.
-enum LinField : int { L_A = 0, L_B = 6, L_BB = 14, L_G = 18, L_COUNT = 24 };
+// Workspace (SolveArgs::w*): SQP iterate X/U, wrapped x0, stage data in SoA (LinField, qsp_kernels.h).
 
 __device__ __forceinline__ const ShapeDev& shape_of(const SolveArgs& A, int i) {
     const int id = A.shape_id ? A.shape_id[i] : 0;
     return A.shapes[shape_clamp(id, A.n_shapes)];
 }
-
-// nlp_mode 1 workspace (SoA over (instance, stage), like wlin)
-enum NlpField : int { W_PI = 0, W_LAM = 4, W_NU = 10, W_ETA = 14, W_COUNT = 20 };
 
 // NLP multipliers and merit weights at the start of a solve (oracle sqp_solve: PI from the
 // initial guess, LAM and the weights zero).
@@ -1772,7 +1767,7 @@ __device__ __forceinline__ double merit_stage(const SolveParams& p, int k, const
 // merit_ls_kernel (merit weights from the QP multipliers, Armijo backtracking on the l1
 // merit function, damped multiplier update).  One stage per lane: lane k of a group owns
 // stage k, every per-stage term is lane-parallel, horizon sums/maxima are group reductions.
-enum QpField : int { Q_DX = 0, Q_DU = 4, Q_PI = 6, Q_LAM = 10, Q_COUNT = 16 };
+// Workspaces: NlpField, QpField (qsp_kernels.h), SoA over (instance, stage) like wlin.
 
 // KKT residuals of the NLP at the current iterate against tol_* (max norms over the
 // horizon); `nlp` points at this lane's stage in the W_* SoA (stride tot).  res (the instance's
@@ -2589,7 +2584,7 @@ hipError_t launch_sqp(const SolveArgs& a, int S, hipStream_t stream, hipEvent_t*
         hipLaunchKernelGGL(iota_kernel, dim3(gb), dim3(128), 0, stream, a.B, a.wperm);
         e = hipGetLastError();
         if (e == hipSuccess)
-            e = hipMemsetAsync(a.whist, 0, P * 4 * PACK_KEYS_MAX * sizeof(int32_t), stream);
+            e = hipMemsetAsync(a.whist, 0, P * WHIST_PER_PART * sizeof(int32_t), stream);
     }
     if (e == hipSuccess) e = mark();
     if (fused) {
@@ -2610,7 +2605,7 @@ hipError_t launch_sqp(const SolveArgs& a, int S, hipStream_t stream, hipEvent_t*
             ap[q] = as;
             ap[q].i0 = w0 * G;
             ap[q].nI = (q + 1 < P ? w1 * G : a.B) - w0 * G;
-            if (sorted) ap[q].whist = a.whist + q * 4 * PACK_KEYS_MAX;
+            if (sorted) ap[q].whist = a.whist + q * WHIST_PER_PART;
             sp[q] = q == 0 ? stream : split->aux[q - 1];
         }
         if (e == hipSuccess) e = hipEventRecord(split->fork, stream);

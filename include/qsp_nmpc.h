@@ -39,12 +39,14 @@ extern "C" {
 #define QSP_NY_E 4
 #define QSP_NH 3          /* h = [s; u_n; u_t]      (NMPC_controller.m:237) */
 #define QSP_MAX_CTRL 64   /* spline control points per shape */
-#define QSP_ABI_VERSION 7 /* 2: struct_size fields, qp_mu_max, qsp_get_qp_stalled, QP-failure exits;
+#define QSP_ABI_VERSION 8 /* 2: struct_size fields, qp_mu_max, qsp_get_qp_stalled, QP-failure exits;
                              3: qsp_options.factor_scan; 4: qsp_get_factor_walk;
                              5: qsp_rollout_cost, qsp_rollout_cost_device, qsp_cost_landscape;
                              6: qsp_eval_modes, qsp_get_modes, qsp_open_loop, qsp_open_loop_device;
                              7: qsp_set_plant_shapes, qsp_set_plant_shape_ids, qsp_set_plant_params,
-                                qsp_clear_plant, qsp_get_plant, qsp_closed_loop_metrics */
+                                qsp_clear_plant, qsp_get_plant, qsp_closed_loop_metrics;
+                             8: qsp_default_sim_noise, qsp_set_sim_noise, qsp_clear_sim_noise, qsp_get_sim_noise,
+                                qsp_gen_sim_noise */
 
 #define QSP_OK 0
 #define QSP_ERR_ARG (-1)
@@ -247,7 +249,8 @@ int qsp_controller_reset(qsp_solver* s);                                        
 /* Closed-loop simulation on the device (helper.m:195-322, closed_loop_matlab): cold start of the
  * solver's warm start (X, U, PI), then for t = 0..n_steps-1: x += noise[t] (sim_noise, optional), u = solve(x, index0 + t),
  * x += Ts * f(x, u) (evalModelVariableShape + Euler, :292-307).  x0: B x 4; index0: B (1-based);
- * noise: n_steps x B x 4 or NULL; X_traj: B x (n_steps+1) x 4; U_traj: B x n_steps x 2;
+ * noise: n_steps x B x 4 or NULL (NULL with a generator installed, qsp_set_sim_noise below: drawn on the
+ * device); X_traj: B x (n_steps+1) x 4; U_traj: B x n_steps x 2;
  * status_traj: B x n_steps (found_sol = status == 0) or NULL. */
 int qsp_closed_loop(qsp_solver* s, const double* x0, const int32_t* index0, int32_t n_steps, const double* noise,
                     double* X_traj, double* U_traj, int32_t* status_traj);
@@ -516,7 +519,8 @@ typedef struct {
     double plant_delay;       /* plant.time_delay [s]: ceil(delay / Ts) buffer columns, as qsp_closed_loop_opts' */
 } qsp_open_loop_opts;
 void qsp_default_open_loop_opts(qsp_open_loop_opts* opts);   /* n_steps 1, M 1, u_steps 1, clip on, v_alpha 1 */
-/* x0: B x 4; U: B x M x u_steps x 2; noise: n_steps x B x 4 or NULL (shared by a lane's candidates);
+/* x0: B x 4; U: B x M x u_steps x 2; noise: n_steps x B x 4 or NULL (shared by a lane's candidates; NULL with a
+ * generator installed, qsp_set_sim_noise below: drawn in the kernel);
  * shapes per lane as qsp_set_shape_ids.  Outputs, each optional except x_end:
  *   X          B x M x (n_steps + 1) x 4   the states, row n_steps the final one
  *   U_out      B x M x n_steps x 2         the commanded input after the clip (the reference's returned u)
@@ -543,6 +547,46 @@ typedef struct {
     double* x_end;           /* B x M x 4 */
 } qsp_open_loop_io;
 int qsp_open_loop_device(qsp_solver* s, const qsp_open_loop_opts* opts, const qsp_open_loop_io* io, void* hip_stream);
+
+/* ------------------------------------------- sim_noise generated on the device */
+/* The reference's sim_noise branch (helper.m:240-242; open loop :154-156) adds four normals per lane and step,
+ * x += [1e-5; 1e-5; 1e-3; 1e-4] .* randn(4, 1).  The entries above take them as a host table, noise: n_steps x B
+ * x 4.  A generator installed on the handle draws them inside the kernels instead: no table is built, staged
+ * or held, and the noise of (lane, step) is a pure function of the fields below, so every shard (lane_offset)
+ * and every chunk (step_offset) of a run draws the numbers of the whole run.
+ *   bits      Philox4x32-10 (Random123), one call per (lane, step), step = step_offset + t for the 0-based
+ *             step t of the entry call:
+ *                 counter = (uint32(lane_offset + lane), step low 32 bits, step high 32 bits, stream)
+ *                 key     = (seed low 32 bits, seed high 32 bits)
+ *   uniforms  u_j = (w_j + 0.5) * 2^-32 of the four output words w_0..w_3
+ *   normals   z_0 = r cos(2 pi u_1), z_1 = r sin(2 pi u_1), r = sqrt(-2 log u_0); z_2, z_3 from (u_2, u_3)
+ *             alike; |z| <= 6.76, always finite
+ *   noise     x_c += (sigma[c] * lane_scale[lane]) * z_c
+ * With a generator installed and noise == NULL (io->noise == NULL for qsp_open_loop_device), qsp_closed_loop,
+ * qsp_closed_loop_ex, qsp_closed_loop_metrics, qsp_open_loop and qsp_open_loop_device draw the step's noise
+ * where they add the table's: after the disturbance, before the log and the delay prediction; in the open
+ * loop shared by a lane's M candidates.  The results are bit for bit those of the same call with the table
+ * that qsp_gen_sim_noise writes.  A table passed while a generator is installed is ambiguous: QSP_ERR_ARG.
+ * With nothing installed every result is bit-identical to a library without these entries. */
+typedef struct {
+    int32_t struct_size;       /* sizeof(qsp_sim_noise) (qsp_default_sim_noise sets it; checked) */
+    uint32_t stream;           /* realisation index: counter word 3 */
+    uint64_t seed;
+    int64_t step_offset;       /* >= 0: step t of a call draws at step_offset + t */
+    int64_t lane_offset;       /* >= 0, lane_offset + B <= 2^32: lane i draws as global lane lane_offset + i */
+    double sigma[4];           /* finite, >= 0; default 1e-5, 1e-5, 1e-3, 1e-4 (helper.m:241) */
+    const double* lane_scale;  /* B host doubles, finite, >= 0, copied; NULL: 1 */
+} qsp_sim_noise;
+void qsp_default_sim_noise(qsp_sim_noise* gen);   /* seed 0, stream 0, no offsets, the reference's sigma, no scale */
+/* install (replacing what was installed); QSP_ERR_ARG leaves what was installed */
+int qsp_set_sim_noise(qsp_solver* s, const qsp_sim_noise* gen);
+int qsp_clear_sim_noise(qsp_solver* s);
+/* what is installed: out (lane_scale NULL; the defaults when none is), installed 0 / 1, has_scale 0 / 1.  Each
+ * of the three pointers may be NULL. */
+int qsp_get_sim_noise(qsp_solver* s, qsp_sim_noise* out, int32_t* installed, int32_t* has_scale);
+/* the table the loops draw over n_steps steps from step_offset, noise: n_steps x B x 4 (host), for inspection
+ * and replay; QSP_ERR_STATE if no generator is installed */
+int qsp_gen_sim_noise(qsp_solver* s, int32_t n_steps, double* noise);
 
 #ifdef __cplusplus
 }

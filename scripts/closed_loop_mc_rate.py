@@ -6,17 +6,24 @@ straight-line reference, no noise, no delay), four shapes mixed per lane, x0 fro
   (a) qsp_closed_loop_ex of a library built from the parent commit (--parent-lib; without it the row is left out);
   (b) qsp_closed_loop_ex of this tree with no plant installed;
   (c) the same with per-lane mu_sp / c_ellipse (qsp_set_plant_params: +-20 % around each lane's shape);
-  (d) qsp_closed_loop_metrics with the same plant.
+  (d) qsp_closed_loop_metrics with the same plant;
+  (e) qsp_closed_loop_metrics, no plant, sim_noise from a host table (n_steps x B x 4 doubles: 421 MB at this size),
+      here the table that qsp_gen_sim_noise writes; the time numpy takes to draw the equivalent table on the host
+      (helper.py's default path) is reported on its own;
+  (f) the same run with the generator installed (qsp_set_sim_noise) and noise = NULL: the same noise values drawn
+      in closed_loop_pre_kernel, no table anywhere.
 Both libraries are driven through the C ABI alone (ctypes), so that the parent's older ABI loads, and each runs in
 a process of its own, started afresh for every repetition (with both handles alive in one process the two
 libraries did not time alike although their kernels are the same code: profiles/plant_model/README.md).  The legs
-are interleaved, repetition by repetition: (a), then (b), (c), (d) on one handle, after a warm-up of three steps.
+are interleaved, repetition by repetition: (a), then (b) to (f) on one handle, after a warm-up of three steps.
 Per row: the loop's own HIP-event time (qsp_get_time_tot: all kernels of the 201 steps, no copy) as median,
 minimum and maximum, lane-steps/s from the median, and the median wall time of the call, which adds the host
-copies (about 0.7 GB of trajectories for (a)-(c), 5 MB of metrics for (d)).  (b) against (a) is the regression
-check: (b)'s median must lie within (a)'s own minimum-to-maximum spread.
+copies (about 0.7 GB of trajectories for (a)-(c), 5 MB of metrics for (d) and (f), the 421 MB table for (e)).  (b)
+against (a) is the regression check: (b)'s median must lie within (a)'s own minimum-to-maximum spread.  (f) against
+(e): the same noise, so the same solver work (x_end and status equal); (f)'s median within or below (e)'s spread.
 
-  python scripts/closed_loop_mc_rate.py [--batch 65536] [--steps 201] [--reps 7] [--parent-lib FILE] [--out FILE]
+  python scripts/closed_loop_mc_rate.py [--batch 65536] [--steps 201] [--reps 7] [--parent-lib FILE] [--legs bcdef]
+                                        [--out FILE]
 """
 import argparse
 import ctypes as C
@@ -32,7 +39,8 @@ sys.path.insert(0, ROOT)
 NAMES = ("santal", "balea", "montana", "pulirapid")
 USED = ("qsp_default_options", "qsp_create", "qsp_destroy", "qsp_set_shapes", "qsp_set_shape_ids",
         "qsp_set_reference_trajectory", "qsp_closed_loop_ex", "qsp_get_time_tot", "qsp_last_error")
-NEW = ("qsp_set_plant_params", "qsp_clear_plant", "qsp_closed_loop_metrics")
+NEW = ("qsp_set_plant_params", "qsp_clear_plant", "qsp_closed_loop_metrics", "qsp_default_sim_noise",
+       "qsp_set_sim_noise", "qsp_clear_sim_noise", "qsp_gen_sim_noise")
 METRICS = ("sum_exy2", "max_exy2", "sum_eth2", "end_exy2", "sum_u2", "n_failed", "n_st", "n_sl", "n_sr", "n_s_out")
 
 
@@ -58,7 +66,7 @@ class Handle:
         for name in USED + (NEW if new_abi else ()):
             fn = getattr(self.L, name)
             fn.argtypes = _lib._SIGS[name]
-            fn.restype = None if name == "qsp_default_options" else C.c_char_p if name == "qsp_last_error" else C.c_int
+            fn.restype = None if name in _lib._VOID else C.c_char_p if name == "qsp_last_error" else C.c_int
         o = _lib.Options()
         self.L.qsp_default_options(C.byref(o))
         o.N, o.batch, o.sqp_iters, o.qp_iters, o.nlp_mode = 10, B, 30, 50, 1
@@ -104,14 +112,47 @@ def worker(a):
     def loop(n):
         hd.ok(hd.L.qsp_closed_loop_ex(hd.h, None, p(x0), p(idx), n, None, p(X), None, p(U), p(S)))
 
-    def metrics(n):
-        hd.ok(hd.L.qsp_closed_loop_metrics(hd.h, None, p(x0), p(idx), n, None, p(met), p(xe), p(st)))
+    def metrics(n, noise=None):
+        hd.ok(hd.L.qsp_closed_loop_metrics(hd.h, None, p(x0), p(idx), n, None if noise is None else p(noise), p(met),
+                                           p(xe), p(st)))
+
+    def generator(on):
+        if on:
+            g = _lib.SimNoise()
+            hd.L.qsp_default_sim_noise(C.byref(g))
+            g.seed = 20250303
+            hd.ok(hd.L.qsp_set_sim_noise(hd.h, C.byref(g)))
+        else:
+            hd.ok(hd.L.qsp_clear_sim_noise(hd.h))
 
     loop(3)                                        # warm-up: code objects, allocations, host pages
-    if "d" in a.rows:
+    if set("def") & set(a.rows):
         metrics(3)
+    table, e_end = None, None
+    if "e" in a.rows:                              # the table of (f)'s generator, and numpy's draw of such a table
+        table = np.zeros((T, B, 4))
+        generator(True)
+        hd.ok(hd.L.qsp_gen_sim_noise(hd.h, T, p(table)))
+        generator(False)
+        metrics(3, table)                          # warm-up of the table's device buffer
+        t0 = time.perf_counter()
+        np.random.default_rng(0).standard_normal((T, B, 4)) * np.array([1e-5, 1e-5, 1e-3, 1e-4])
+        draw = (time.perf_counter() - t0) * 1e3
     X[:], U[:], S[:] = 0.0, 0.0, 0
     for row in a.rows:
+        if row in "ef":
+            generator(row == "f")
+            t0 = time.perf_counter()
+            metrics(T, table if row == "e" else None)
+            wall = (time.perf_counter() - t0) * 1e3
+            ms = hd.time_tot()
+            generator(False)
+            h = hashlib.sha256(xe.tobytes() + st.tobytes() + met.tobytes()).hexdigest()[:16]
+            note = f"sha {h} " + (f"numpy_draw_ms {draw:.1f}" if row == "e" else
+                                  f"is_e {int(e_end is not None and h == e_end)}")
+            e_end = h if row == "e" else e_end
+            print(f"ROW {row} {ms:.3f} {wall:.3f} {note}", flush=True)
+            continue
         if row in "cd":
             hd.ok(hd.L.qsp_set_plant_params(hd.h, p(mu), p(ce)))
         t0 = time.perf_counter()
@@ -131,7 +172,8 @@ def worker(a):
 
 
 LABEL = {"a": "(a) closed_loop_ex, parent commit", "b": "(b) closed_loop_ex, no plant installed",
-         "c": "(c) closed_loop_ex, per-lane mu_sp / c_ellipse", "d": "(d) closed_loop_metrics, the same plant"}
+         "c": "(c) closed_loop_ex, per-lane mu_sp / c_ellipse", "d": "(d) closed_loop_metrics, the same plant",
+         "e": "(e) closed_loop_metrics, noise from a host table", "f": "(f) closed_loop_metrics, noise drawn on device"}
 
 
 def main():
@@ -140,6 +182,7 @@ def main():
     ap.add_argument("--steps", type=int, default=201)
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--parent-lib", default=None, help="libqsp_nmpc.so built from the parent commit, for row (a)")
+    ap.add_argument("--legs", default="bcdef", help="rows of this tree to run, e.g. bef (b is always needed with --parent-lib)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--rows", default=None, help=argparse.SUPPRESS)   # worker: the rows of one library
     a = ap.parse_args()
@@ -147,7 +190,7 @@ def main():
         return worker(a)
     import subprocess
     B, T = a.batch, a.steps
-    legs = ([("a", ["--parent-lib", a.parent_lib])] if a.parent_lib else []) + [("bcd", [])]
+    legs = ([("a", ["--parent-lib", a.parent_lib])] if a.parent_lib else []) + [(a.legs, [])]
     ms, wall, notes = {}, {}, {}
     for _ in range(a.reps):                        # interleaved: one repetition of every row in turn
         for rows, extra in legs:
@@ -174,10 +217,18 @@ def main():
         same = len(set(n.split()[1] for n in notes["a"] + notes["b"])) == 1
         lines.append(f"(b) median within (a)'s min..max: {inside}; (a) and (b) bit-identical in X, U, status "
                      f"(sha-256 of every repetition): {same}")
-    lines.append(f"(c): {notes['c'][-1]}; (b): {notes['b'][-1]}")
-    d = notes["d"][-1].split()
-    lines.append(f"(d) x_end == (c) X[:, -1]: {bool(int(d[1]))}; status: {bool(int(d[3]))}; medians over lanes of the ten "
-                 f"metrics ({', '.join(METRICS)}): {' '.join(d[4:])}")
+    if "c" in notes:
+        lines.append(f"(c): {notes['c'][-1]}; (b): {notes['b'][-1]}")
+    if "d" in notes:
+        d = notes["d"][-1].split()
+        lines.append(f"(d) x_end == (c) X[:, -1]: {bool(int(d[1]))}; status: {bool(int(d[3]))}; medians over lanes of the "
+                     f"ten metrics ({', '.join(METRICS)}): {' '.join(d[4:])}")
+    if "e" in ms and "f" in ms:
+        same = all(n.split()[3] == "1" for n in notes["f"])
+        fm = float(np.median(ms["f"]))
+        lines.append(f"(f) metrics, x_end and status bit-identical to (e)'s on every repetition: {same}; (f) median within or "
+                     f"below (e)'s min..max: {fm <= float(np.max(ms['e']))}; numpy's draw of a {T} x {B} x 4 table on the "
+                     f"host (not part of (e)'s times): median {float(np.median([float(n.split()[3]) for n in notes['e']])):.1f} ms")
     print("\n".join(lines))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)

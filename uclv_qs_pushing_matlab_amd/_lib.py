@@ -12,7 +12,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 # QSP_LIB_PATH: developer override (A/B runs of differently compiled libraries)
 LIB_PATH = os.environ.get("QSP_LIB_PATH") or os.path.join(_PKG, "libqsp_nmpc.so")
 MAX_CTRL = 64
-ABI_VERSION = 7   # include/qsp_nmpc.h QSP_ABI_VERSION
+ABI_VERSION = 8   # include/qsp_nmpc.h QSP_ABI_VERSION
 
 _lib = None
 
@@ -84,6 +84,11 @@ class OpenLoopOpts(C.Structure):
 class OpenLoopIO(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in
                 ("x0", "U", "noise", "shape_id", "X", "U_out", "S_p", "mode", "mode_steps", "x_end")]
+
+
+class SimNoise(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("stream", C.c_uint32), ("seed", C.c_uint64), ("step_offset", C.c_int64),
+                ("lane_offset", C.c_int64), ("sigma", C.c_double * 4), ("lane_scale", C.c_void_p)]
 
 
 _P = C.c_void_p
@@ -168,9 +173,14 @@ _SIGS = {
     "qsp_default_open_loop_opts": [C.POINTER(OpenLoopOpts)],
     "qsp_open_loop": [_P, C.POINTER(OpenLoopOpts), _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "qsp_open_loop_device": [_P, C.POINTER(OpenLoopOpts), C.POINTER(OpenLoopIO), _P],
+    "qsp_default_sim_noise": [C.POINTER(SimNoise)],
+    "qsp_set_sim_noise": [_P, C.POINTER(SimNoise)],
+    "qsp_clear_sim_noise": [_P],
+    "qsp_get_sim_noise": [_P, C.POINTER(SimNoise), C.POINTER(_I), C.POINTER(_I)],
+    "qsp_gen_sim_noise": [_P, _I, _P],
     "qsp_last_error": [],
 }
-_VOID = {"qsp_default_options", "qsp_default_rollout_opts", "qsp_default_open_loop_opts"}
+_VOID = {"qsp_default_options", "qsp_default_rollout_opts", "qsp_default_open_loop_opts", "qsp_default_sim_noise"}
 EXPORTED = tuple(_SIGS)
 
 

@@ -44,7 +44,8 @@ struct __attribute__((visibility("hidden"))) qsp_solver {
     Dev<uint8_t> warm_valid;
     // delay compensation (set_delay_comp, NMPC_controller.m:106-110): delay_buff_comp columns and the
     // per-lane controller input buffer u_buff_contr (B x D x 2, column 0 newest); closed-loop state:
-    // the plant's buffer and state, the disturbance amplitudes, the noise (n_steps x B x 4) and the
+    // the plant's buffer and state, the disturbance amplitudes, the noise table (n_steps x B x 4; not
+    // allocated when the generator below draws the noise) and the
     // logs of a run with trajectories (B x n_steps: X_sim, X_traj, U_traj, status_traj)
     int32_t D = 0;
     Dev<double> ubc, ubp, cl_x, cl_amp, cl_noise, cl_xsim, cl_xtraj, cl_utraj;
@@ -56,6 +57,11 @@ struct __attribute__((visibility("hidden"))) qsp_solver {
     Dev<ShapeDev> pshapes;
     Dev<int32_t> pshape_id;
     Dev<double> pmu, pc, cl_metrics;
+    // sim_noise drawn in the kernels (qsp_set_sim_noise): the generator as installed (lane_scale NULL) and the
+    // device copy of its per-lane scale
+    bool sn_on = false, sn_has_scale = false;
+    qsp_sim_noise sn = {};
+    Dev<double> sn_scale;
     Dev<double> wX, wU, wx0, wlin, wnlp, wres, wqp, wadj;
     Dev<int32_t> wdone, wperm, wnit, whist, wadjv;
     Dev<uint8_t> pool[STAGE_POOL];  // device images of one call's host arrays (bytes), handed out by Staging
@@ -906,6 +912,24 @@ static ClosedLoopArgs cl_args(qsp_solver* s) {
     return a;
 }
 
+// The installed generator as the kernels take it (gen.on = 0 without one), and its per-lane scale
+static SimNoiseGen noise_gen(const qsp_solver* s) {
+    SimNoiseGen g;
+    std::memset(&g, 0, sizeof g);
+    if (!s->sn_on) return g;
+    g.on = 1;
+    g.stream = s->sn.stream;
+    g.key0 = (uint32_t)s->sn.seed;
+    g.key1 = (uint32_t)(s->sn.seed >> 32);
+    g.lane0 = (uint32_t)s->sn.lane_offset;
+    g.step0 = (uint64_t)s->sn.step_offset;
+    std::memcpy(g.sigma, s->sn.sigma, sizeof g.sigma);
+    return g;
+}
+static const double* noise_scale(const qsp_solver* s) { return s->sn_on && s->sn_has_scale ? s->sn_scale.data() : nullptr; }
+static const char* const NOISE_TWICE = ": a noise table while a sim_noise generator is installed is ambiguous "
+                                       "(pass noise = NULL, or qsp_clear_sim_noise first)";
+
 int qsp_delay_buffer_sim(qsp_solver* s, const double* x, double* x_sim) {
     if (!s || !x || !x_sim) return fail(QSP_ERR_ARG, "qsp_delay_buffer_sim: null argument");
     if (s->n_shapes < 1) return fail(QSP_ERR_STATE, "qsp_delay_buffer_sim: no shapes set");
@@ -946,6 +970,7 @@ static int closed_loop_run(qsp_solver* s, const char* who, const qsp_closed_loop
                            const int32_t* index0, int32_t n_steps, const double* noise, bool want_traj,
                            bool want_xsim, bool want_metrics) {
     const std::string w(who);
+    if (noise && s->sn_on) return fail(QSP_ERR_ARG, w + NOISE_TWICE);
     if (!s->have_traj) return fail(QSP_ERR_STATE, w + ": no reference trajectory");
     if (s->n_shapes < 1) return fail(QSP_ERR_STATE, w + ": no shapes set");
     const double plant_delay = o ? o->plant_delay : 0.0;
@@ -988,6 +1013,8 @@ static int closed_loop_run(qsp_solver* s, const char* who, const qsp_closed_loop
     c.x = s->cl_x.data();
     c.xs = s->x0.data();                 // the solver's x0 (constr_x0)
     c.noise = noise ? s->cl_noise.data() : nullptr;
+    c.gen = noise_gen(s);                // drawn in closed_loop_pre_kernel: cl_noise is not touched
+    c.lane_scale = noise_scale(s);
     c.dist_step = dist ? o->t_dist : 0;
     c.dist_amp = (dist && o->amplitude) ? s->cl_amp.data() : nullptr;
     c.Dp = Dp;
@@ -1565,6 +1592,7 @@ static int open_loop_run(qsp_solver* s, const qsp_open_loop_opts* opts, const ch
     if (r) return r;
     const std::string w(who);
     if (!io || !io->x0 || !io->U || !io->x_end) return fail(QSP_ERR_ARG, w + missing(host));
+    if (io->noise && s->sn_on) return fail(QSP_ERR_ARG, w + NOISE_TWICE);
     qsp_open_loop_io d = *io;
     Staging st(s);
     if (host) {
@@ -1585,6 +1613,8 @@ static int open_loop_run(qsp_solver* s, const qsp_open_loop_opts* opts, const ch
     a.x0 = d.x0;
     a.U = d.U;
     a.noise = d.noise;
+    a.gen = noise_gen(s);
+    a.lane_scale = noise_scale(s);
     if (d.shape_id) a.shape_id = d.shape_id;
     a.X = d.X;
     a.U_out = d.U_out;
@@ -1604,6 +1634,68 @@ int qsp_open_loop(qsp_solver* s, const qsp_open_loop_opts* opts, const double* x
 
 int qsp_open_loop_device(qsp_solver* s, const qsp_open_loop_opts* opts, const qsp_open_loop_io* io, void* stream) {
     return open_loop_run(s, opts, "qsp_open_loop_device", false, io, stream);
+}
+
+// ------------------------------------------- sim_noise generated on the device
+void qsp_default_sim_noise(qsp_sim_noise* g) {
+    std::memset(g, 0, sizeof(*g));
+    g->struct_size = (int32_t)sizeof(qsp_sim_noise);
+    const double sigma[4] = {1e-5, 1e-5, 1e-3, 1e-4};   // helper.m:241
+    std::memcpy(g->sigma, sigma, sizeof sigma);
+}
+
+int qsp_set_sim_noise(qsp_solver* s, const qsp_sim_noise* g) {
+    if (!s || !g) return fail(QSP_ERR_ARG, "qsp_set_sim_noise: null argument");
+    if (g->struct_size != (int32_t)sizeof(qsp_sim_noise))
+        return fail(QSP_ERR_ARG, "qsp_set_sim_noise: qsp_sim_noise.struct_size != sizeof(qsp_sim_noise) (stale layout?)");
+    for (int c = 0; c < 4; ++c)
+        if (!(std::isfinite(g->sigma[c]) && g->sigma[c] >= 0.0))
+            return fail(QSP_ERR_ARG, "qsp_set_sim_noise: sigma must be finite and >= 0");
+    const size_t B = s->dim.lane();
+    if (g->step_offset < 0 || g->lane_offset < 0 || g->lane_offset > (1ll << 32) - (long long)B)
+        return fail(QSP_ERR_ARG, "qsp_set_sim_noise: need step_offset >= 0, lane_offset >= 0 and lane_offset + B <= 2^32");
+    for (size_t i = 0; g->lane_scale && i < B; ++i)
+        if (!(std::isfinite(g->lane_scale[i]) && g->lane_scale[i] >= 0.0))
+            return fail(QSP_ERR_ARG, "qsp_set_sim_noise: lane_scale must be finite and >= 0");
+    // a failed copy (QSP_ERR_HIP) leaves the generator installed before, without a scale
+    if (g->lane_scale) {
+        s->sn_has_scale = false;
+        const int r = h2d_grow(s, s->sn_scale, g->lane_scale, B);
+        if (r) return r;
+    }
+    s->sn = *g;
+    s->sn.lane_scale = nullptr;
+    s->sn_has_scale = g->lane_scale != nullptr;
+    s->sn_on = true;
+    return QSP_OK;
+}
+
+int qsp_clear_sim_noise(qsp_solver* s) {
+    if (!s) return fail(QSP_ERR_ARG, "qsp_clear_sim_noise: null handle");
+    s->sn_on = s->sn_has_scale = false;
+    return QSP_OK;
+}
+
+int qsp_get_sim_noise(qsp_solver* s, qsp_sim_noise* out, int32_t* installed, int32_t* has_scale) {
+    if (!s) return fail(QSP_ERR_ARG, "qsp_get_sim_noise: null handle");
+    if (out) {
+        if (s->sn_on) *out = s->sn;
+        else qsp_default_sim_noise(out);
+    }
+    if (installed) *installed = s->sn_on ? 1 : 0;
+    if (has_scale) *has_scale = s->sn_on && s->sn_has_scale ? 1 : 0;
+    return QSP_OK;
+}
+
+int qsp_gen_sim_noise(qsp_solver* s, int32_t n_steps, double* noise) {
+    if (!s || !noise || n_steps < 1) return fail(QSP_ERR_ARG, "qsp_gen_sim_noise: bad argument");
+    if (!s->sn_on) return fail(QSP_ERR_STATE, "qsp_gen_sim_noise: no sim_noise generator installed (qsp_set_sim_noise)");
+    HIPCHK(hipSetDevice(s->o.device));
+    Staging st(s);
+    double* d = st.out(noise, s->dim.cl_noise((size_t)n_steps));
+    if (st.err) return st.err;
+    HIPCHK(launch_sim_noise(noise_gen(s), noise_scale(s), s->o.batch, n_steps, d, s->stream));
+    return st.finish();
 }
 
 }  // extern "C"

@@ -36,7 +36,7 @@ struct Dims {
     size_t cl_Xsim(size_t T) const { return B * T * 4; }
     size_t cl_U(size_t T) const { return B * T * 2; }
     size_t cl_status(size_t T) const { return B * T; }
-    size_t cl_noise(size_t T) const { return T * B * 4; }
+    size_t cl_noise(size_t T) const { return T * B * 4; }   // a noise table: the caller's, or qsp_gen_sim_noise's
     size_t metrics() const { return B * CL_NMETRICS; }
     size_t delay(size_t D) const { return B * D * 2; }
     // reference table of T rows: shared, or one per lane

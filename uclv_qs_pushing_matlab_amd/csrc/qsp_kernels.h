@@ -115,6 +115,16 @@ hipError_t launch_sqp(const SolveArgs& a, int S, hipStream_t stream, hipEvent_t*
 int sqp_parts_auto(int B, int N, int S, int cus);
 int sqp_fused_auto(int B, int N, int S, int nlp_mode, int cus);
 hipError_t launch_qp(const SolveArgs& a, int S, hipStream_t stream);   // one QP step on prepared workspace
+// sim_noise drawn in the kernels (qsp_noise.hpp; helper.m:240-242, :154-156): the handle's generator
+// (qsp_set_sim_noise) by value.  The noise of (lane, step) is a pure function of these words.
+struct SimNoiseGen {
+    int32_t on;                // 0: no generator (every other field unread)
+    uint32_t stream;           // Philox counter word 3
+    uint32_t key0, key1;       // seed, low and high word
+    uint32_t lane0;            // lane i draws as global lane lane0 + i (lane_offset + B <= 2^32)
+    uint64_t step0;            // step t of a call draws at step0 + t
+    double sigma[4];
+};
 // Device closed loop (helper.m:195-322): buffers and logs of qsp_closed_loop, one thread per lane.
 struct ClosedLoopArgs {
     const ShapeDev* shapes;
@@ -125,6 +135,8 @@ struct ClosedLoopArgs {
     double* x;                 // B x 4   plant state
     double* xs;                // B x 4   state handed to the solver (after the delay prediction)
     const double* noise;       // n_steps x B x 4 (sim_noise) or nullptr
+    SimNoiseGen gen;           // gen.on (then noise == nullptr): the step's noise is drawn in closed_loop_pre_kernel
+    const double* lane_scale;  // B, the generator's per-lane factor of sigma, or nullptr (1)
     int32_t dist_step;         // 1-based step of the disturbance (0: none)
     const double* dist_amp;    // B amplitude_dist (nullptr: 0)
     int32_t D, Dp;             // controller delay_buff_comp, plant delay_buff_plant
@@ -157,6 +169,9 @@ constexpr int CL_NMETRICS = 10;   // QSP_CL_NMETRICS (include/qsp_nmpc.h), colum
 hipError_t launch_closed_loop_pre(const ClosedLoopArgs& a, int t, hipStream_t stream);
 hipError_t launch_plant(const ClosedLoopArgs& a, int t, hipStream_t stream);
 hipError_t launch_delay_sim(const ClosedLoopArgs& a, hipStream_t stream);   // x -> xs (delay_buffer_sim)
+// the table the loops would draw with g: noise[(t * B + i) * 4 + c], t < n_steps (qsp_gen_sim_noise)
+hipError_t launch_sim_noise(const SimNoiseGen& g, const double* lane_scale, int B, int n_steps, double* noise,
+                            hipStream_t stream);
 hipError_t launch_reproject(const ShapeDev* shapes, int n_shapes, const int32_t* sid, int n, const double* px,
                             const double* py, const double* s0, double* s, hipStream_t stream);
 hipError_t launch_straight_lines(int B, int T, const double* x0, const double* xf, double t0, double tf, double Ts,
@@ -231,6 +246,9 @@ struct OpenLoopArgs {
     int32_t* mode;             // B x M x T or nullptr
     int32_t* mode_steps;       // B x M x 4 or nullptr
     double* x_end;             // B x M x 4
+    // last, so that the kernels without a generator read the block above where they always did
+    SimNoiseGen gen;           // gen.on (then noise == nullptr): the step's noise is drawn in open_loop_noise_kernel
+    const double* lane_scale;  // B, the generator's per-lane factor of sigma, or nullptr (1)
 };
 hipError_t launch_open_loop(const OpenLoopArgs& a, hipStream_t stream);
 

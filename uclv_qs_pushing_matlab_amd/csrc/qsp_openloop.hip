@@ -5,7 +5,9 @@
 //   open_loop_kernel  helper.open_loop_matlab (helper.m:132-193), one thread per (lane, candidate): per
 //                     step the noise, the tangential clip, the plant's delay buffer, the mode and the
 //                     Euler step x + Ts f(x, u) with the OCP's f (euler_step, qsp_math.hpp: the closed
-//                     loop's plant step).
+//                     loop's plant step);
+//   open_loop_noise_kernel  the same with the step's noise drawn from the handle's generator (qsp_noise.hpp)
+//                     instead of read from a table.
 //
 // A candidate's arithmetic is the same sequence of IEEE operations at any M, B, lane index, position
 // among the candidates, set of requested outputs and store path: results agree bit for bit, with
@@ -32,6 +34,7 @@
 #include "../../include/qsp_nmpc.h"
 #include "qsp_math.hpp"
 #include "qsp_candidates.hpp"
+#include "qsp_noise.hpp"
 
 namespace qsp {
 
@@ -102,7 +105,8 @@ __device__ __forceinline__ void flush_tile(const OpenLoopArgs& A, const Tile<K>&
 
 // The workgroup's rows gbase + threadIdx.x, threadIdx.x < nrows (lane: this thread's; every thread of the
 // workgroup calls this, the tiled paths synchronise inside).
-template <int K>
+// GEN: the step's noise is drawn from A.gen (qsp_noise.hpp) instead of read from A.noise.
+template <int K, bool GEN>
 __device__ __forceinline__ void open_loop_rows(const OpenLoopArgs& A, const ShapeDev& sh, int lane, size_t gbase, int nrows,
                                                double* tile_lds) {
     const bool active = (int)threadIdx.x < nrows;
@@ -122,7 +126,12 @@ __device__ __forceinline__ void open_loop_rows(const OpenLoopArgs& A, const Shap
 
     // one step: logs row i through `log`, then advances x
     auto step = [&](int i, auto log) {
-        if (A.noise) {                                         // helper.m:155
+        if constexpr (GEN) {                                   // helper.m:155, the table's values drawn here
+            double nz[4];
+            sim_noise(A.gen, A.lane_scale, lane, i, nz);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) x[c] = x[c] + nz[c];
+        } else if (A.noise) {                                  // helper.m:155
             const double* nz = A.noise + ((size_t)i * A.B + lane) * 4;
 #pragma unroll
             for (int c = 0; c < 4; ++c) x[c] = x[c] + nz[c];
@@ -228,16 +237,40 @@ __global__ void __launch_bounds__(OL_BLOCK) open_loop_kernel(OpenLoopArgs A, int
         __syncthreads();
         const ShapeDev& sh = *reinterpret_cast<const ShapeDev*>(ol_lds);
         const int m0 = blockIdx.y * blockDim.x, left = A.M - m0;   // left >= 1 by the grid
-        open_loop_rows<K>(A, sh, lane, (size_t)lane * A.M + m0, left < (int)blockDim.x ? left : (int)blockDim.x,
-                          ol_lds + SHAPE_D);
+        open_loop_rows<K, false>(A, sh, lane, (size_t)lane * A.M + m0, left < (int)blockDim.x ? left : (int)blockDim.x,
+                                 ol_lds + SHAPE_D);
     } else {
         const long long lane0 = (long long)blockIdx.x * lpb;
         const long long nl = A.B - lane0 < lpb ? A.B - lane0 : lpb;
         const int nrows = (int)nl * A.M;
         long long lane = lane0 + (int)threadIdx.x / A.M;
         if (lane >= A.B) lane = A.B - 1;                       // an idle thread: a valid shape, no loads or stores
-        open_loop_rows<K>(A, shape_clamped(A.shapes, A.n_shapes, A.shape_id, (int)lane), (int)lane, (size_t)lane0 * A.M, nrows,
-                          ol_lds);
+        open_loop_rows<K, false>(A, shape_clamped(A.shapes, A.n_shapes, A.shape_id, (int)lane), (int)lane, (size_t)lane0 * A.M,
+                                 nrows, ol_lds);
+    }
+}
+
+// The same workgroups with the step's noise drawn from A.gen.  A kernel of its own, not a branch in the one
+// above: with the draw compiled into the kernels of a run without noise, the tiled ones went from 121 to 131
+// VGPRs and from 19 to 67 spilled SGPRs, and open_loop_kernel's code must stay what it was
+// (profiles/sim_noise/README.md).
+template <int K, bool ONE_LANE>
+__global__ void __launch_bounds__(OL_BLOCK) open_loop_noise_kernel(OpenLoopArgs A, int lpb) {
+    extern __shared__ __align__(16) double ol_lds[];
+    if (ONE_LANE) {
+        const int lane = blockIdx.x;
+        stage_shape(shape_clamped(A.shapes, A.n_shapes, A.shape_id, lane), ol_lds);
+        __syncthreads();
+        const int m0 = blockIdx.y * blockDim.x, left = A.M - m0;
+        open_loop_rows<K, true>(A, *reinterpret_cast<const ShapeDev*>(ol_lds), lane, (size_t)lane * A.M + m0,
+                                left < (int)blockDim.x ? left : (int)blockDim.x, ol_lds + SHAPE_D);
+    } else {
+        const long long lane0 = (long long)blockIdx.x * lpb;
+        const long long nl = A.B - lane0 < lpb ? A.B - lane0 : lpb;
+        long long lane = lane0 + (int)threadIdx.x / A.M;
+        if (lane >= A.B) lane = A.B - 1;
+        open_loop_rows<K, true>(A, shape_clamped(A.shapes, A.n_shapes, A.shape_id, (int)lane), (int)lane, (size_t)lane0 * A.M,
+                                (int)nl * A.M, ol_lds);
     }
 }
 
@@ -249,12 +282,14 @@ static hipError_t launch_ol(const OpenLoopArgs& a, hipStream_t stream) {
         const long long blocks = ((long long)a.M + nt - 1) / nt;
         if (blocks > 65535) return hipErrorInvalidValue;
         const size_t lds = sizeof(ShapeDev) + (K >= 4 ? Tile<(K >= 4 ? K : 4)>::bytes(nt) : 0);
-        hipLaunchKernelGGL((open_loop_kernel<K, true>), dim3((unsigned)a.B, (unsigned)blocks), dim3((unsigned)nt), lds, stream, a, 1);
+        const auto kernel = a.gen.on ? open_loop_noise_kernel<K, true> : open_loop_kernel<K, true>;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)a.B, (unsigned)blocks), dim3((unsigned)nt), lds, stream, a, 1);
     } else {
         const int lpb = cap / a.M;
         const size_t lds = K >= 4 ? Tile<(K >= 4 ? K : 4)>::bytes(cap) : 0;
-        hipLaunchKernelGGL((open_loop_kernel<K, false>), dim3((unsigned)(((long long)a.B + lpb - 1) / lpb)), dim3((unsigned)cap),
-                           lds, stream, a, lpb);
+        const auto kernel = a.gen.on ? open_loop_noise_kernel<K, false> : open_loop_kernel<K, false>;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)(((long long)a.B + lpb - 1) / lpb)), dim3((unsigned)cap), lds, stream, a,
+                           lpb);
     }
     return hipGetLastError();
 }

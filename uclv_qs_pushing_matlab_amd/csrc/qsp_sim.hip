@@ -4,6 +4,8 @@
 //   closed_loop_pre_kernel, plant_kernel   helper.m:195-322 around each NMPC_controller.solve;
 //   delay_sim_kernel, reproject_kernel     NMPC_controller.delay_buffer_sim and the disturbance's
 //                                          re-projection on their own;
+//   sim_noise_kernel                       the table of sim_noise that the loops draw with the handle's
+//                                          generator (qsp_noise.hpp);
 //   straight_lines_kernel                  TrajectoryGenerator.straight_line per lane;
 //   stage_yref_kernel                      get_y_ref: a controller step's references out of the table;
 //   spline_, dynamics_, rk4_, vbound_kernel  one device function each (qsp_math.hpp), for the tests and
@@ -17,6 +19,7 @@
 #include "../../include/qsp_nmpc.h"
 #include "qsp_math.hpp"
 #include "qsp_kernels.h"
+#include "qsp_noise.hpp"
 
 namespace qsp {
 
@@ -106,8 +109,13 @@ __global__ void closed_loop_pre_kernel(ClosedLoopArgs a, int t) {
         const double sn = reproject_contact(sh, -0.5 * sh.xwidth, e.C[1] - amp, 0.0);
         x[3] = qfma(-sh.b, sn < 0.0 ? 1.0 : 0.0, mat_mod(sn, sh.b));
     }
-    if (a.noise)
+    if (a.noise) {
         for (int c = 0; c < 4; ++c) x[c] += a.noise[((size_t)t * a.B + i) * 4 + c];
+    } else if (a.gen.on) {   // the same values, drawn here
+        double nz[4];
+        sim_noise(a.gen, a.lane_scale, i, t, nz);
+        for (int c = 0; c < 4; ++c) x[c] = x[c] + nz[c];
+    }
     for (int c = 0; c < 4; ++c) {
         a.x[(size_t)i * 4 + c] = x[c];
         if (a.Xtraj) a.Xtraj[((size_t)i * (a.n_steps + 1) + t) * 4 + c] = x[c];
@@ -202,6 +210,24 @@ __global__ void reproject_kernel(const ShapeDev* shapes, int n_shapes, const int
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     s[i] = reproject_contact(shape_clamped(shapes, n_shapes, sid, i), px[i], py[i], s0[i]);
+}
+
+// qsp_gen_sim_noise: one thread per (step, lane), four doubles each
+__global__ void sim_noise_kernel(SimNoiseGen g, const double* lane_scale, int B, long long n, double* noise) {
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n) return;
+    const long long t = e / B;
+    double nz[4];
+    sim_noise(g, lane_scale, (int)(e - t * B), (int)t, nz);
+    for (int c = 0; c < 4; ++c) noise[(size_t)e * 4 + c] = nz[c];
+}
+
+hipError_t launch_sim_noise(const SimNoiseGen& g, const double* lane_scale, int B, int n_steps, double* noise,
+                            hipStream_t stream) {
+    const long long n = (long long)B * n_steps, blocks = (n + 255) / 256;
+    if (B < 1 || n_steps < 1 || blocks > 0x7fffffffll) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(sim_noise_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, g, lane_scale, B, n, noise);
+    return hipGetLastError();
 }
 
 hipError_t launch_closed_loop_pre(const ClosedLoopArgs& a, int t, hipStream_t stream) {

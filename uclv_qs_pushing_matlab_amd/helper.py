@@ -115,6 +115,24 @@ def _plant_for_call(plant, controller, plant_mu_sp, plant_c_ellipse):
             sv.set_plant(**prev)
 
 
+@contextlib.contextmanager
+def _noise_for_call(solver, on, seed):
+    """The handle's sim_noise generator for one call (noise_on_device): installed with `seed`, the reference's
+    sigma and no lane scale; what the handle had before comes back on every exit path.  Off: nothing is touched."""
+    if not on:
+        yield
+        return
+    prev = solver.get_sim_noise()
+    try:
+        solver.set_sim_noise(seed)
+        yield
+    finally:
+        if prev is None:
+            solver.clear_sim_noise()
+        else:
+            solver.set_sim_noise(**prev)
+
+
 def _closed_loop_inputs(controller, x0, time_sim, sim_noise, seed):
     Ts = controller.sample_time
     time_sim_vec = np.arange(0.0, time_sim + 1e-9, Ts)                      # :198
@@ -130,15 +148,19 @@ def _closed_loop_inputs(controller, x0, time_sim, sim_noise, seed):
 
 def closed_loop_matlab(plant, controller, x0, time_sim, print_=False, sim_noise=False, debug_cost=False,
                        disturbance_=False, amplitude_dist=0.0, t_dist=0, seed=0, plant_mu_sp=None,
-                       plant_c_ellipse=None):
+                       plant_c_ellipse=None, noise_on_device=False):
     """Returns (x_s, x_sim, y_s, theta_s, S_p_x, S_p_y, u_n, u_t, time_sim_vec, mode_vect, found_sol),
     each with a leading batch dimension B (helper.m:195-197; x_sim is (B, 2T+1, 4): the reference's
     4 x (2T+1) with its T+1 leading zero columns); amplitude_dist may be per lane.
     The loop simulates with `plant` and solves with the controller's model: a plant other than
     controller.plant is the handle's plant for the call (OcpSolver.set_plant), and plant_mu_sp /
-    plant_c_ellipse (scalars or (B,)) override its friction and limit-surface constant per lane."""
-    time_sim_vec, T, B, noise, x0 = _closed_loop_inputs(controller, x0, time_sim, sim_noise, seed)
-    with _plant_for_call(plant, controller, plant_mu_sp, plant_c_ellipse):
+    plant_c_ellipse (scalars or (B,)) override its friction and limit-surface constant per lane.
+    noise_on_device with sim_noise: the noise is drawn in the kernels from `seed` (OcpSolver.set_sim_noise, for
+    this call) instead of a numpy table: other numbers of the same law, and no T x B x 4 table anywhere."""
+    gen = bool(sim_noise and noise_on_device)
+    time_sim_vec, T, B, noise, x0 = _closed_loop_inputs(controller, x0, time_sim, sim_noise and not gen, seed)
+    with _plant_for_call(plant, controller, plant_mu_sp, plant_c_ellipse), \
+            _noise_for_call(controller.ocp_solver, gen, seed):
         r = controller.ocp_solver.closed_loop(x0, T, index0=1, noise=noise, plant_delay=plant.time_delay,
                                               disturbance=bool(disturbance_), t_dist=int(t_dist),
                                               amplitude=amplitude_dist)
@@ -154,11 +176,13 @@ def closed_loop_matlab(plant, controller, x0, time_sim, print_=False, sim_noise=
 
 def closed_loop_metrics(plant, controller, x0, time_sim, print_=False, sim_noise=False, debug_cost=False,
                         disturbance_=False, amplitude_dist=0.0, t_dist=0, seed=0, plant_mu_sp=None,
-                        plant_c_ellipse=None):
+                        plant_c_ellipse=None, noise_on_device=False):
     """closed_loop_matlab's run with the same arguments, reduced on the device to per-lane metrics
     (OcpSolver.closed_loop_metrics' dict): no trajectory comes back to the host."""
-    _, T, _, noise, x0 = _closed_loop_inputs(controller, x0, time_sim, sim_noise, seed)
-    with _plant_for_call(plant, controller, plant_mu_sp, plant_c_ellipse):
+    gen = bool(sim_noise and noise_on_device)
+    _, T, _, noise, x0 = _closed_loop_inputs(controller, x0, time_sim, sim_noise and not gen, seed)
+    with _plant_for_call(plant, controller, plant_mu_sp, plant_c_ellipse), \
+            _noise_for_call(controller.ocp_solver, gen, seed):
         return controller.ocp_solver.closed_loop_metrics(x0, T, index0=1, noise=noise, plant_delay=plant.time_delay,
                                                          disturbance=bool(disturbance_), t_dist=int(t_dist),
                                                          amplitude=amplitude_dist)
@@ -215,12 +239,14 @@ def mode_trace(solver, X, U, plant_delay_cols=0, shape_id=None):
     return solver.eval_modes(X.reshape(-1, 4), ua.reshape(-1, 2), shape_id=sid).reshape(B, T)
 
 
-def open_loop_matlab(plant, x0, u_n, u_t, time_sim, sample_time, sim_noise=False, seed=0, solver=None):
+def open_loop_matlab(plant, x0, u_n, u_t, time_sim, sample_time, sim_noise=False, seed=0, solver=None,
+                     noise_on_device=False):
     """[x_s, y_s, theta_s, S_p_x, S_p_y, u_n, u_t, time_sim_vec] = open_loop_matlab(plant, x0, u_n, u_t, time_sim,
     sample_time, sim_noise) (helper.m:132-193), batched: x0 (B, 4) or (4,); u_n, u_t scalars or (B,).  Every
     returned trajectory is (B, T) with T = length(0:sample_time:time_sim); u_t is the commanded input after the
     clip; S_p_y = x(4, :) as helper.m:190 returns it (the contact abscissa s, not the spline's y).  Noise is
-    drawn on the host as closed_loop_matlab's (seeded).  solver: an OcpSolver whose batch and shapes to use
+    drawn on the host as closed_loop_matlab's (seeded), or with noise_on_device in the kernel (from `seed`,
+    OcpSolver.set_sim_noise for this call).  solver: an OcpSolver whose batch and shapes to use
     (default: the plant's own one-lane evaluator, for B = 1)."""
     time_sim_vec = np.arange(0.0, time_sim + 1e-9, sample_time)            # :136
     T = len(time_sim_vec)
@@ -230,11 +256,13 @@ def open_loop_matlab(plant, x0, u_n, u_t, time_sim, sample_time, sim_noise=False
     U = np.stack([np.broadcast_to(np.asarray(u_n, np.float64), (B,)),
                   np.broadcast_to(np.asarray(u_t, np.float64), (B,))], 1)[:, None]     # (B, 1, 2): repmat, :144
     noise = None
-    if sim_noise:                                                           # :154-156
+    gen = bool(sim_noise and noise_on_device)
+    if sim_noise and not gen:                                               # :154-156
         rng = np.random.default_rng(seed)
         noise = rng.standard_normal((T, B, 4)) * np.array([1e-5, 1e-5, 1e-3, 1e-4])
-    r = sv.open_loop(x0, U, T, noise=noise, plant_delay=plant.time_delay, clip=True, v_alpha=0.005 * 200,
-                     Ts=sample_time, want=("X", "U_out", "S_p"))
+    with _noise_for_call(sv, gen, seed):
+        r = sv.open_loop(x0, U, T, noise=noise, plant_delay=plant.time_delay, clip=True, v_alpha=0.005 * 200,
+                         Ts=sample_time, want=("X", "U_out", "S_p"))
     X = r["X"][:, 0, :T]
     return (X[:, :, 0], X[:, :, 1], X[:, :, 2], r["S_p"][:, 0, :, 0], X[:, :, 3], r["U_out"][:, 0, :, 0],
             r["U_out"][:, 0, :, 1], time_sim_vec)

@@ -75,6 +75,7 @@ class OcpSolver:
         self.n_shapes = 0
         self.shape_ids = np.zeros(Bn, np.int32)   # host copy of the per-lane shape ids (helper.mode_trace)
         self._plant = None                        # host copy of the installed plant model (set_plant)
+        self._noise_scale = None                  # host copy of the installed generator's lane_scale (set_sim_noise)
         # timings=True: per-kernel HIP events around every solve, for get('time_lin'/'time_qp_sol')
         self._timings = bool(timings)
         self._last_times = None
@@ -175,6 +176,46 @@ class OcpSolver:
         if (hs.value, hp.value) != want:
             raise _lib.QspError(f"plant(): the handle reports {(hs.value, hp.value)}, this object installed {want}")
         return None if p is None else dict(p)
+
+    # ------------------------------------ sim_noise generated on the device
+    def set_sim_noise(self, seed, sigma=None, lane_scale=None, stream=0, step_offset=0, lane_offset=0):
+        """Install the sim_noise generator (qsp_set_sim_noise; helper.m:240-242, :154-156): with it and
+        noise=None, closed_loop, closed_loop_metrics, open_loop and open_loop_device draw x += (sigma *
+        lane_scale[lane]) * randn(4) in their kernels, a pure function of (seed, stream, lane_offset + lane,
+        step_offset + step): no table, and shards (lane_offset) and chunks (step_offset) of a run draw the whole
+        run's numbers.  sigma (4,), None: the reference's 1e-5, 1e-5, 1e-3, 1e-4; lane_scale scalar or (B,),
+        None: 1.  Replaces what was installed; an argument the library rejects leaves it."""
+        g = _lib.SimNoise()
+        self._L.qsp_default_sim_noise(C.byref(g))
+        g.seed, g.stream = int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream) & 0xFFFFFFFF
+        g.step_offset, g.lane_offset = int(step_offset), int(lane_offset)
+        if sigma is not None:
+            g.sigma[:] = [float(v) for v in np.asarray(sigma, np.float64).reshape(4)]
+        sc = None if lane_scale is None else f64(np.broadcast_to(np.asarray(lane_scale, np.float64), (self.B,)))
+        g.lane_scale = None if sc is None else sc.ctypes.data
+        check(self._L.qsp_set_sim_noise(self._h, C.byref(g)), "qsp_set_sim_noise")
+        self._noise_scale = None if sc is None else sc.copy()
+
+    def clear_sim_noise(self):
+        """No generator: noise comes from a table or not at all, the state of a new solver."""
+        check(self._L.qsp_clear_sim_noise(self._h), "qsp_clear_sim_noise")
+        self._noise_scale = None
+
+    def get_sim_noise(self):
+        """What set_sim_noise installed, as the handle reports it: None, or dict(seed, sigma, lane_scale, stream,
+        step_offset, lane_offset); set_sim_noise(**d) installs such a dict again."""
+        g, on, sc = _lib.SimNoise(), C.c_int32(), C.c_int32()
+        check(self._L.qsp_get_sim_noise(self._h, C.byref(g), C.byref(on), C.byref(sc)), "qsp_get_sim_noise")
+        if not on.value:
+            return None
+        return dict(seed=g.seed, sigma=np.array(g.sigma[:]), lane_scale=self._noise_scale.copy() if sc.value else None,
+                    stream=g.stream, step_offset=g.step_offset, lane_offset=g.lane_offset)
+
+    def gen_sim_noise(self, n_steps):
+        """The table the loops draw over n_steps steps with the installed generator: (n_steps, B, 4)."""
+        out = np.zeros((int(n_steps), self.B, 4))
+        check(self._L.qsp_gen_sim_noise(self._h, int(n_steps), ptr(out)), "qsp_gen_sim_noise")
+        return out
 
     # ----------------------------------------------------------------- set
     def _lanes(self, v, width):
@@ -537,7 +578,8 @@ class OcpSolver:
                     amplitude=None):
         """Device-resident closed loop (helper.m:195-322): returns X (B, n+1, 4) (plant states after
         disturbance and noise), Xsim (B, n, 4) (the delay-predicted states the solver sees), U (B, n, 2),
-        status (B, n).  noise: (n, B, 4) additive state noise before each solve, or None; plant_delay [s];
+        status (B, n).  noise: (n, B, 4) additive state noise before each solve, or None (then drawn on the
+        device where set_sim_noise installed a generator); plant_delay [s];
         disturbance at the 1-based step t_dist with per-lane amplitude (y offset + contact re-projection)."""
         n, x0, idx, nz, o, _amp = self._closed_loop_args(x0, n_steps, index0, noise, plant_delay, disturbance, t_dist,
                                                          amplitude)

@@ -9,5 +9,7 @@ for f in $SOURCES; do
   /opt/rocm/bin/hipcc --offload-arch=gfx950 $FLAGS -I include "$@" \
     -c uclv_qs_pushing_matlab_amd/csrc/$f -o /tmp/kres.o -Rpass-analysis=kernel-resource-usage 2>&1
 done |
-  grep -A12 -E "Function Name: _ZN3qsp1(4qp_step|5sqp_loop)" | grep -E "Name|VGPRs:|AGPRs|Scratch|Occupancy" |
-  sed -e 's/.*remark: *//' -e 's/ \[-Rpass.*//' | paste - - - - -
+  sed -n -e 's/ \[-Rpass.*//' -e 's/.*remark: *//p' |
+  awk '/^Function Name:/ { if (row != "") print row; row = ($0 ~ /_ZN3qsp1(4qp_step|5sqp_loop|5merit_ls)/) ? $0 : "" ; next }
+       row != "" && /^(VGPRs:|AGPRs:|ScratchSize|Occupancy)/ { row = row "\t" $0 }
+       END { if (row != "") print row }'

@@ -13,7 +13,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-NAMES = {0: "iteration head (mu, stop tests, ballot)", 1: "barrier_terms", 2: "factorisation walk",
+NAMES = {0: "iteration head (mu over the barrier terms, stop tests, ballot)", 2: "factorisation walk",
          3: "predictor forward walk", 4: "affine directions, step, mu_aff", 5: "corrector_terms",
          6: "corrector difference walk", 7: "corrector forward walk", 8: "corrector directions, step, update",
          10: "kernel head: linearisation, loads", 11: "qp_ipm total", 12: "rollout, outcome, iterate update",

@@ -50,7 +50,8 @@ enum LdsField {
     F_VA = 23,    /* 3  affine-predictor bounded components (ds, dun, dut) */
     F_VN = 26,    /* 3  corrector bounded components */
     F_DX = 23,    /* 4  final QP state step (written after the IPM: aliases F_VA / F_VN) */
-    F_HG = 29,    /* 6  barrier Hessian (0..2) / gradient (3..5) additions */
+    F_HG = 29,    /* 6  the corrector's barrier gradient additions (3..5); 0..2 unused (the predictor's
+                   *    barrier terms go to the factorisation in registers) */
     F_COUNT = 35
 };
 

@@ -136,6 +136,37 @@ __device__ __forceinline__ double group_sum(double v, const GroupScan& g) {
     }
     return __shfl(v, g.base);
 }
+// The same tree with NP pieces of work that do not depend on the sum, work(0) .. work(NP - 1), placed
+// under it.  Every level of the tree ends in an LDS round trip (ds_bpermute) with nothing of the sum's
+// own to issue meanwhile.  For 16 < L <= 32 (wave-uniform) the five levels are written out, so that
+// they and the pieces between them are one straight-line region the scheduler can interleave; any
+// other L does the pieces first and takes the loop.  Partner, mask and the first-lane read are
+// group_sum's: the association does not change.
+template <int NP, class Work>
+__device__ __forceinline__ double group_sum_over(double v, const GroupScan& g, Work work) {
+    if (g.L > 16 && g.L <= 32) {
+        const int lane = (int)(threadIdx.x & 63);
+        const int lig = lane - g.base;
+#pragma unroll
+        for (int i = 0; i < 5; ++i) {
+            const int off = 1 << i;
+            const double o = __shfl(v, lane + off);
+#pragma unroll
+            for (int q = 0; q < NP; ++q)
+                if (q * 5 / NP == i) work(q);
+            v += (lig + off < g.L) ? o : 0.0;
+        }
+        return __shfl(v, g.base);
+    }
+#pragma unroll
+    for (int q = 0; q < NP; ++q) work(q);
+    return group_sum(v, g);
+}
+// group_sum with its levels written out where they can be: what the caller issues next and does not
+// need the sum for (operand loads) moves under the round trips.
+__device__ __forceinline__ double group_sum_flat(double v, const GroupScan& g) {
+    return group_sum_over<0>(v, g, [](int) {});
+}
 __device__ __forceinline__ double group_min(double v, const GroupScan& g) { return group_reduce(v, g, OpMin()); }
 __device__ __forceinline__ double group_max(double v, const GroupScan& g) { return group_reduce(v, g, OpMax()); }
 
@@ -881,22 +912,21 @@ __device__ __forceinline__ void velem_read(const VElem& e, int src, VElem& f) {
 }
 
 // ------------------------------------------------------------------ QP core
-// Barrier terms of slot ls into LDS (predictor): hg[0..2] Hessian additions, hg[3..5]
-// gradient additions.  The corrector changes only the gradient (corrector_terms).
+// Barrier terms of bound pair j of slot ls (predictor): hgv[ls][j] Hessian addition, hgv[ls][3 + j]
+// gradient addition, handed to the factorisation in registers (it reads them once, right after the
+// loop's exit test: no LDS round trip).  They depend on t, lm, rt and the iterate only, not on mu.
+// The corrector changes only the gradient (corrector_terms, through F_HG).
 template <int S>
-__device__ __forceinline__ void barrier_terms(const Ctx& c, const SolveParams& p, const Stage<S>& st, int ls) {
-    const int k = kof<S>(c, ls);
-    double lo[3], hi[3];
-    bnd_lohi<S>(p, st, ls, lo, hi);
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        const bool act = bnd_act(c, p, k, j);
-        const double ll = st.lm(ls, 2 * j), lh = st.lm(ls, 2 * j + 1);
-        const double sl = ll * st.rt(ls, 2 * j), sh = lh * st.rt(ls, 2 * j + 1);
-        const double gadd = qfma(-sh, hi[j], -sl * lo[j]) + (lh - ll);
-        st.hg(ls, j) = act ? sl + sh : 0.0;
-        st.hg(ls, 3 + j) = act ? gadd : 0.0;
-    }
+__device__ __forceinline__ void barrier_term(const Ctx& c, const SolveParams& p, const Stage<S>& st, int ls, int j,
+                                             double (&hgv)[S][6]) {
+    const double v = st.v(ls, j);
+    const double lo = p.lh[j] - v, hi = p.uh[j] - v;   // bnd_lohi's
+    const bool act = bnd_act(c, p, kof<S>(c, ls), j);
+    const double ll = st.lm(ls, 2 * j), lh = st.lm(ls, 2 * j + 1);
+    const double sl = ll * st.rt(ls, 2 * j), sh = lh * st.rt(ls, 2 * j + 1);
+    const double gadd = qfma(-sh, hi, -sl * lo) + (lh - ll);
+    hgv[ls][j] = act ? sl + sh : 0.0;
+    hgv[ls][3 + j] = act ? gadd : 0.0;
 }
 
 // The step length is the largest alpha with t + alpha dt >= 0 and l + alpha dl >= 0,
@@ -1016,7 +1046,7 @@ __device__ __forceinline__ void apply_step(const Stage<S>& st, int ls, const dou
 // (F_VA / F_VN).
 template <int S, bool FACTOR, bool ALT = false>
 __device__ __forceinline__ void riccati_solve(const Ctx& c, const SolveParams& p, Stage<S>& st, const double dx0[4],
-                                              int out, double (&M)[S][16]) {
+                                              int out, double (&M)[S][16], const double (&hgv)[S][6]) {
     SEG_T(t_rs);
     double P[10], pv[4];
 #pragma unroll
@@ -1039,12 +1069,12 @@ __device__ __forceinline__ void riccati_solve(const Ctx& c, const SolveParams& p
 #pragma unroll
     for (int ls = 0; ls < S; ++ls) {
         if (FACTOR) {
-            hx3[ls] = qfma(p.tau, p.W[3], st.hg(ls, 0));
-            hu[ls][0] = qfma(p.tau, p.W[4], st.hg(ls, 1));
-            hu[ls][1] = qfma(p.tau, p.W[5], st.hg(ls, 2));
-            gx3[ls] = st.g[ls][3] + st.hg(ls, 3);
-            gu[ls][0] = st.g[ls][4] + st.hg(ls, 4);
-            gu[ls][1] = st.g[ls][5] + st.hg(ls, 5);
+            hx3[ls] = qfma(p.tau, p.W[3], hgv[ls][0]);
+            hu[ls][0] = qfma(p.tau, p.W[4], hgv[ls][1]);
+            hu[ls][1] = qfma(p.tau, p.W[5], hgv[ls][2]);
+            gx3[ls] = st.g[ls][3] + hgv[ls][3];
+            gu[ls][0] = st.g[ls][4] + hgv[ls][4];
+            gu[ls][1] = st.g[ls][5] + hgv[ls][5];
         } else {
             gx3[ls] = st.hg(ls, 3);
             gu[ls][0] = st.hg(ls, 4);
@@ -1421,7 +1451,12 @@ __device__ int qp_ipm(const Ctx& c, const SolveParams& p, Stage<S>& st, const do
         for (int ls = 0; ls < S; ++ls)
 #pragma unroll
             for (int q = 0; q < 6; ++q) tl_sum = qfma(st.t(ls, q), st.lm(ls, q), tl_sum);
-        const double mu = group_sum(tl_sum, c.gs) / m;
+        // The predictor's barrier terms go under the sum's shuffle levels: they do not depend on
+        // mu, and the break below stands between the sum and their place in front of the
+        // factorisation.  The pass in front of the break that ends the loop is computed for
+        // nothing (registers only); a finished instance recomputes the terms of its frozen state.
+        double hgv[S][6];
+        const double mu = group_sum_over<3 * S>(tl_sum, c.gs, [&](int q) { barrier_term<S>(c, p, st, q / 3, q % 3, hgv); }) / m;
         // divergence first (mu non-finite or past qp_mu_max: a NaN mu would pass the stop test),
         // then the stop test, then the stall exit (locally infeasible QP: the step length stays
         // tiny while mu grows)
@@ -1435,13 +1470,10 @@ __device__ int qp_ipm(const Ctx& c, const SolveParams& p, Stage<S>& st, const do
 #ifdef QSP_SEGSTAMP
         if ((threadIdx.x & 63) == 0) atomicAdd(&g_seg[31], 1ull);
 #endif
-        SEG_NEXT(0, t_seg);
+        SEG_NEXT(0, t_seg);   // with the predictor's barrier terms (segment 1, theirs alone, is gone)
         // ---- predictor
-#pragma unroll
-        for (int ls = 0; ls < S; ++ls) barrier_terms<S>(c, p, st, ls);
-        SEG_NEXT(1, t_seg);
         double M[S][16];   // closed-loop matrices A + B K (S = 1), shared by both forward walks
-        riccati_solve<S, true, ALT>(c, p, st, dx0, F_VA, M);
+        riccati_solve<S, true, ALT>(c, p, st, dx0, F_VA, M, hgv);
         SEG_T(t_seg2);
         // affine directions: computed once, kept in registers through the corrector
         double at[S][6], al[S][6];
@@ -1452,7 +1484,7 @@ __device__ int qp_ipm(const Ctx& c, const SolveParams& p, Stage<S>& st, const do
         double ma = 0.0;
 #pragma unroll
         for (int ls = 0; ls < S; ++ls) ma = affine_mu_part<S>(c, p, st, ls, at[ls], al[ls], aa, ma);
-        const double mua = group_sum(ma, c.gs) / m;
+        const double mua = group_sum_flat(ma, c.gs) / m;
         const double r = mua / mu;
         const double sg = fmax(r * r * r, p.sigma_min);
         const double smu = sg * mu;
@@ -1461,7 +1493,7 @@ __device__ int qp_ipm(const Ctx& c, const SolveParams& p, Stage<S>& st, const do
 #pragma unroll
         for (int ls = 0; ls < S; ++ls) corrector_terms<S>(c, p, st, ls, at[ls], al[ls], smu);
         SEG_ADD(5, t_seg2);
-        riccati_solve<S, false, ALT>(c, p, st, dx0, F_VN, M);
+        riccati_solve<S, false, ALT>(c, p, st, dx0, F_VN, M, hgv);
         SEG_T(t_seg3);
         double dt[S][6], dl[S][6];
         num = 1.0; den = p.frac;       // initial bound 1/frac

@@ -1,6 +1,6 @@
 /*
  * or_opts.h — solver options shared by the CPU oracle's two restatements (TEST INFRASTRUCTURE
- * ONLY): qsp_oracle.c (literal) and qsp_twin.c (kernel order).  Layout mirrored by oracle.py Opts.
+ * ONLY): qsp_oracle.c (literal) and qsp_twin.cpp (kernel order; C++).  Plain C.  Layout mirrored by oracle.py Opts.
  */
 #ifndef OR_OPTS_H
 #define OR_OPTS_H

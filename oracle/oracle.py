@@ -6,8 +6,9 @@ __graft_entry__.smoke() and bench.py's cpu_baseline leg only.
 Two restatements of the reference path share one interface:
   Oracle(...)            the literal restatement (qsp_oracle.c: full basis sum, forward AD,
                          a dense Riccati interior point) -- pins the formulas;
-  Oracle(..., twin=True) the kernel-order twin (qsp_twin.c: the device library's formulation
-                         and operation order, explicit fma) -- reproduces the device bit for bit.
+  Oracle(..., twin=True) the kernel-order twin (qsp_twin.cpp: the device library's own lane
+                         arithmetic, csrc/qsp_{fp,math,riccati}.hpp, inside a sequential restatement
+                         of the kernels' orchestration) -- reproduces the device bit for bit.
 """
 import ctypes as C
 import os

@@ -1,26 +1,35 @@
 /*
- * qsp_twin.c — the CPU oracle's kernel-order twin.
+ * qsp_twin.cpp — the CPU oracle's kernel-order twin.
  *
  * TEST INFRASTRUCTURE ONLY.  Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg
  * may load this library, and only as the checker; the product (uclv_qs_pushing_matlab_amd/) never
  * links or calls it.
  *
  * PARITY STATUS: UNPINNED against acados/CasADi/HPIPM (not runnable here), as
- * qsp_oracle.c.  This file restates the same reference path as qsp_oracle.c -- the B-spline contour
+ * qsp_oracle.c.  This file runs the same reference path as qsp_oracle.c -- the B-spline contour
  * (acados_nmpc/bspline_shape.m:40-116, 137-152), the motion-cone dynamics
  * (PusherSliderModel.m:503-603), ERK/RK4 with sensitivities (NMPC_controller.m:272), the linear-LS
  * OCP with bgh bounds (NMPC_controller.m:174-268), the Mehrotra interior point standing in for
  * HPIPM (:272-276), fixed-K and merit-backtracking SQP (:271-276), the NMPC_controller.solve
- * wrapper (:329-423) and helper.closed_loop_matlab (helper.m:195-322) -- but evaluates it in the
- * device library's formulation and operation order: span-based de Boor and the hand-derived
- * Jacobian, the structured Riccati step with its closed-loop walks, the lane-group reductions'
- * summation tree, every fused multiply-add as an explicit fma() (the library is built with
- * -ffp-contract=off, this file too).  The operations are IEEE-exact on both sides (checked on the
- * device by scripts/ubench/fp_exact.hip), so this twin reproduces the library's results BIT FOR
- * BIT, lane by lane, including lanes where the fixed-K SQP is chaotic.  qsp_oracle.c's literal
- * restatement (full basis sum, AD) pins this formulation's building blocks to rounding level
- * (tests/test_oracle.py); the twin pins the device's execution of it exactly.
- * Kernel counterparts are cited as qsp_math.hpp / qsp_solver.hip function names.
+ * wrapper (:329-423) and helper.closed_loop_matlab (helper.m:195-322) -- in the device library's
+ * formulation and operation order.
+ *
+ * Division of labour.  The lane-local arithmetic -- qfma, rcp, sin_cos, the span-based
+ * de Boor, the dynamics with its hand-derived Jacobian, RK4, the structured Riccati step, the scans'
+ * maps and elements, the adjoint and merit stage terms -- is NOT restated here: this file compiles
+ * the kernels' own headers (csrc/qsp_fp.hpp, qsp_math.hpp, qsp_riccati.hpp) for the host, with
+ * -ffp-contract=off as the library.  What it restates, as plain sequential loops, is the
+ * ORCHESTRATION the device runs in DPP moves, LDS records and matrix-core instructions: which lane
+ * walks when, the lane-group reductions' summation tree, the scans' levels, the matrix-core
+ * product's element order, the barrier and step-length terms tied to the kernels' LDS stage, the
+ * IPM and SQP loops, the controller wrapper and the closed loop.  The operations are IEEE-exact on
+ * both sides (checked on the device by scripts/ubench/fp_exact.hip), so this twin reproduces the
+ * library's results BIT FOR BIT, lane by lane, including lanes where the fixed-K SQP is chaotic:
+ * the comparison proves that the GPU's compiler and hardware evaluate the shared source as x86 does
+ * and that the device executes the algorithm.  qsp_oracle.c's literal restatement (full basis sum,
+ * AD; plain C, no product header) pins the formulas independently to rounding level
+ * (tests/test_oracle.py, tests/test_twin.py); tests/golden/twin_bits.npz pins this twin's bits in time.
+ * Kernel counterparts are cited as qsp_solver.hip function names.
  */
 #include <math.h>
 #include <stdlib.h>
@@ -31,68 +40,18 @@
 #endif
 
 #include "or_opts.h"
-#include "qsp_nmpc.h"     /* QSP_WALK_* (tw_factor_walk) */
-#include "qsp_layout.h"   /* the library's own layout rules: stages per lane, lanes per instance, mfw_fits */
+#include "qsp_nmpc.h"      /* QSP_WALK_* (tw_factor_walk) */
+#include "qsp_layout.h"    /* the library's own layout rules: stages per lane, lanes per instance, mfw_fits */
+#include "qsp_math.hpp"    /* the library's own lane arithmetic: qsp_fp.hpp, the model ... */
+#include "qsp_riccati.hpp" /* ... and the QP's per-lane steps */
+
+using namespace qsp;
 
 #define TW_MAX_N 128
 #define TW_MAX_SLOTS (TW_MAX_N + 2)
-#define TW_MAX_CTRL 64
-
-static inline double qfma(double a, double b, double c) { return fma(a, b, c); }
-
-/* rcp (qsp_fp.hpp): the device refines its hardware reciprocal by two Newton steps, which lands on
- * the correctly rounded 1/x; the same two steps from 1.0 / x give the same bits (also for 0, inf) */
-static inline double rcp(double x)
-{
-    double r = 1.0 / x;
-    double e = fma(-x, r, 1.0);
-    r = fma(r, e, r);
-    e = fma(-x, r, 1.0);
-    return fma(r, e, r);
-}
-
-/* sin_cos (qsp_fp.hpp): fdlibm reduction + kernels, the library's own sequence */
-static void sin_cos(double x, double *sp, double *cp)
-{
-    const double invpio2 = 6.36619772367581382433e-01;
-    const double pio2_1 = 1.57079632673412561417e+00;
-    const double pio2_2 = 6.07710050630396597660e-11;
-    const double pio2_2t = 2.02226624879595063154e-21;
-    const double fn = rint(x * invpio2);
-    double r = x - fn * pio2_1;
-    double w = fn * pio2_2;
-    const double t = r;
-    r = t - w;
-    w = fn * pio2_2t - ((t - r) - w);
-    const double y = r - w;
-    const double yy = (r - y) - w;
-    const double S1 = -1.66666666666666324348e-01, S2 = 8.33333333332248946124e-03,
-                 S3 = -1.98412698298579493134e-04, S4 = 2.75573137070700676789e-06,
-                 S5 = -2.50507602534068634195e-08, S6 = 1.58969099521155010221e-10;
-    const double C1 = 4.16666666666666019037e-02, C2 = -1.38888888888741095749e-03,
-                 C3 = 2.48015872894767294178e-05, C4 = -2.75573143513906633035e-07,
-                 C5 = 2.08757232129817482790e-09, C6 = -1.13596475577881948265e-11;
-    const double z = y * y, zz = z * z;
-    const double rs = S2 + z * (S3 + z * S4) + z * zz * (S5 + z * S6);
-    const double v = z * y;
-    const double ks = y - ((z * (0.5 * yy - v * rs) - yy) - v * S1);
-    const double rc = z * (C1 + z * (C2 + z * C3)) + zz * zz * (C4 + z * (C5 + z * C6));
-    const double hz = 0.5 * z, wc = 1.0 - hz;
-    const double kc = wc + (((1.0 - wc) - hz) + (z * rc - y * yy));
-    const double q = fn - 4.0 * floor(fn * 0.25);
-    const int q1 = q == 1.0, q2 = q == 2.0, q3 = q == 3.0;
-    *sp = q1 ? kc : (q2 ? -ks : (q3 ? -kc : ks));
-    *cp = q1 ? -ks : (q2 ? -kc : (q3 ? ks : kc));
-}
 
 /* ------------------------------------------------------------------ shapes (qsp_set_shapes) */
-typedef struct {
-    int n;
-    double b, c, mu, inv_h, xwidth;
-    double knots[TW_MAX_CTRL + 4], ctrl[2 * TW_MAX_CTRL], dctrl[2 * TW_MAX_CTRL], ddctrl[2 * TW_MAX_CTRL];
-} tw_shape;
-
-static void make_shape(tw_shape *d, const int32_t *n_ctrl, const double *ctrl, const double *knots,
+static void make_shape(ShapeDev *d, const int32_t *n_ctrl, const double *ctrl, const double *knots,
                        const double *params, int max_ctrl, int id, double xwidth)
 {
     memset(d, 0, sizeof *d);
@@ -119,234 +78,6 @@ static void make_shape(tw_shape *d, const int32_t *n_ctrl, const double *ctrl, c
     }
 }
 
-/* ------------------------------------------------------------------ spline (spline_eval) */
-typedef struct { double C[2], D[2], Dd[2]; } spl;
-
-static void spline_eval(const tw_shape *sh, double sig, spl *o)
-{
-    const int n = sh->n;
-    const double *S = sh->knots;
-    const int inside = (sig >= S[3]) && (sig < S[n]);
-    /* the span guess; outside [S3, Sn) every output is masked to zero, so the guess only matters
-     * inside, where sig * inv_h is a small non-negative number (truncated as the device does) */
-    const double qg = sig * sh->inv_h;
-    int j = 3 + ((qg > -1e9 && qg < 1e9) ? (int)qg : 0);
-    j = j < 3 ? 3 : (j > n - 1 ? n - 1 : j);
-    if (sig < S[j]) j = (j > 3) ? j - 1 : j;
-    if (sig < S[j]) j = (j > 3) ? j - 1 : j;
-    if (sig >= S[j + 1]) j = (j < n - 1) ? j + 1 : j;
-    if (sig >= S[j + 1]) j = (j < n - 1) ? j + 1 : j;
-    const double l1 = sig - S[j], l2 = sig - S[j - 1], l3 = sig - S[j - 2];
-    const double r1 = S[j + 1] - sig, r2 = S[j + 2] - sig, r3 = S[j + 3] - sig;
-    double N1_0, N1_1, N2_0, N2_1, N2_2, N3_0, N3_1, N3_2, N3_3;
-    {
-        const double t = 1.0 / (r1 + l1);
-        N1_0 = r1 * t;
-        N1_1 = l1 * t;
-    }
-    {
-        const double t0 = N1_0 / (r1 + l2);
-        const double t1 = N1_1 / (r2 + l1);
-        N2_0 = r1 * t0;
-        N2_1 = qfma(r2, t1, l2 * t0);
-        N2_2 = l1 * t1;
-    }
-    {
-        const double t0 = N2_0 / (r1 + l3);
-        const double t1 = N2_1 / (r2 + l2);
-        const double t2 = N2_2 / (r3 + l1);
-        N3_0 = r1 * t0;
-        N3_1 = qfma(r2, t1, l3 * t0);
-        N3_2 = qfma(r3, t2, l2 * t1);
-        N3_3 = l1 * t2;
-    }
-    const double *P = sh->ctrl + 2 * (j - 3);
-    const double *cd = sh->dctrl + 2 * (j - 2);
-    const double *dd = sh->ddctrl + 2 * (j - 1);
-    for (int c = 0; c < 2; ++c) {
-        double Cv = N3_0 * P[c];
-        Cv = qfma(N3_1, P[2 + c], Cv);
-        Cv = qfma(N3_2, P[4 + c], Cv);
-        Cv = qfma(N3_3, P[6 + c], Cv);
-        double Dv = N2_0 * cd[c];
-        Dv = qfma(N2_1, cd[2 + c], Dv);
-        Dv = qfma(N2_2, cd[4 + c], Dv);
-        const double Ddv = qfma(N1_1, dd[2 + c], N1_0 * dd[c]);
-        o->C[c] = inside ? Cv : 0.0;
-        o->D[c] = inside ? Dv : 0.0;
-        o->Dd[c] = inside ? Ddv : 0.0;
-    }
-}
-
-static double smod_model(double s, double b) { return fmod(s, b) + ((s < 0.0) ? b : 0.0); }
-
-static double mat_mod(double a, double b)
-{
-    const double r = qfma(-floor(a / b), b, a);
-    return (r == b) ? 0.0 : r;
-}
-
-static double angle_rate_of(const spl *e)
-{
-    return qfma(e->D[0], e->Dd[1], -(e->D[1] * e->Dd[0])) / qfma(e->D[0], e->D[0], e->D[1] * e->D[1]);
-}
-
-static double v_bound(const tw_shape *sh, const or_opts *o, double s)
-{
-    const double sm = mat_mod(s, sh->b);
-    spl e;
-    spline_eval(sh, sm, &e);
-    const double ta = fabs(angle_rate_of(&e));
-    const double v = o->v_alpha / (fabs(ta - o->t_angle0) + 0.0001) + o->d_v;
-    return v < o->u_t_ub ? v : o->u_t_ub;
-}
-
-/* ------------------------------------------------------------------ dynamics */
-typedef struct { double f[4], Jth[2], Js[4], Jun[4], Jut[4]; } dyn;
-
-static inline double blend3(double ist, double a, double isl, double b, double isr, double c)
-{
-    return qfma(isr, c, qfma(isl, b, ist * a));
-}
-
-static void dynamics(const tw_shape *sh, double th, double s, double un, double ut, dyn *o, int with_jac)
-{
-    const double sig = smod_model(s, sh->b);
-    spl e;
-    spline_eval(sh, sig, &e);
-    const double l2 = qfma(e.D[0], e.D[0], e.D[1] * e.D[1]);
-    const double l = sqrt(l2);
-    const double il = 1.0 / l;
-    const double tx = e.D[0] * il, ty = e.D[1] * il;
-    const double nx = ty, ny = -tx;
-    const double Px = e.C[0], Py = e.C[1];
-    const double px = qfma(nx, Px, ny * Py);
-    const double py = qfma(tx, Px, ty * Py);
-    const double c2 = sh->c * sh->c, mu = sh->mu;
-    const double pxpy = px * py, px2 = px * px;
-    const double q00 = qfma(px, px, c2), q11 = qfma(py, py, c2);
-    const double fac = 1.0 / qfma(py, py, q00);
-    const double nl = qfma(mu, px2, qfma(mu, c2, -pxpy));
-    const double dl = qfma(-mu, pxpy, q11);
-    const double nr = qfma(-mu, px2, qfma(-mu, c2, -pxpy));
-    const double dr = qfma(mu, pxpy, q11);
-    const double gl = nl / dl, gr = nr / dr;
-    const double rho = ut / un;
-    double sn, cs;
-    sin_cos(th, &sn, &cs);
-    const double H00 = qfma(tx, pxpy, nx * q00), H01 = qfma(tx, q11, nx * pxpy);
-    const double H10 = qfma(ty, pxpy, ny * q00), H11 = qfma(ty, q11, ny * pxpy);
-    const double G00 = fac * H00, G01 = fac * H01, G10 = fac * H10, G11 = fac * H11;
-    const double M00 = qfma(-sn, G10, cs * G00), M01 = qfma(-sn, G11, cs * G01);
-    const double M10 = qfma(cs, G10, sn * G00), M11 = qfma(cs, G11, sn * G01);
-    const double ist = ((rho >= gr) && (rho <= gl)) ? 1.0 : 0.0;
-    const double isl = (rho > gl) ? 1.0 : 0.0;
-    const double isr = (rho < gr) ? 1.0 : 0.0;
-    const double st0 = qfma(M01, ut, M00 * un);
-    const double st1 = qfma(M11, ut, M10 * un);
-    const double st2 = fac * qfma(px, ut, -(py * un));
-    const double vl0 = qfma(M01, gl, M00), vl1 = qfma(M11, gl, M10);
-    const double vr0 = qfma(M01, gr, M00), vr1 = qfma(M11, gr, M10);
-    const double wl = fac * qfma(gl, px, -py), wr = fac * qfma(gr, px, -py);
-    o->f[0] = blend3(ist, st0, isl, vl0 * un, isr, vr0 * un);
-    o->f[1] = blend3(ist, st1, isl, vl1 * un, isr, vr1 * un);
-    o->f[2] = blend3(ist, st2, isl, wl * un, isr, wr * un);
-    o->f[3] = qfma(isr, qfma(-gr, un, ut), isl * qfma(-gl, un, ut));
-    if (!with_jac) return;
-    const double tDd = qfma(ty, e.Dd[1], tx * e.Dd[0]);
-    const double txs = qfma(-tx, tDd, e.Dd[0]) * il, tys = qfma(-ty, tDd, e.Dd[1]) * il;
-    const double nxs = tys, nys = -txs;
-    const double pxs = qfma(nxs, Px, nys * Py);
-    const double pys = qfma(txs, Px, tys * Py) + l;
-    const double pxpys = qfma(px, pys, pxs * py);
-    const double q00s = 2.0 * px * pxs, q11s = 2.0 * py * pys;
-    const double facs = -fac * fac * (q00s + q11s);
-    const double gls = qfma(-gl, qfma(-mu, pxpys, q11s), qfma(mu, q00s, -pxpys)) / dl;
-    const double grs = qfma(-gr, qfma(mu, pxpys, q11s), qfma(-mu, q00s, -pxpys)) / dr;
-    const double G00s = qfma(facs, H00, fac * qfma(tx, pxpys, qfma(txs, pxpy, qfma(nx, q00s, nxs * q00))));
-    const double G01s = qfma(facs, H01, fac * qfma(tx, q11s, qfma(txs, q11, qfma(nx, pxpys, nxs * pxpy))));
-    const double G10s = qfma(facs, H10, fac * qfma(ty, pxpys, qfma(tys, pxpy, qfma(ny, q00s, nys * q00))));
-    const double G11s = qfma(facs, H11, fac * qfma(ty, q11s, qfma(tys, q11, qfma(ny, pxpys, nys * pxpy))));
-    const double M00s = qfma(-sn, G10s, cs * G00s), M01s = qfma(-sn, G11s, cs * G01s);
-    const double M10s = qfma(cs, G10s, sn * G00s), M11s = qfma(cs, G11s, sn * G01s);
-    const double M00t = qfma(-cs, G10, -sn * G00), M01t = qfma(-cs, G11, -sn * G01);
-    const double M10t = qfma(-sn, G10, cs * G00), M11t = qfma(-sn, G11, cs * G01);
-    const double st0t = qfma(M01t, ut, M00t * un), st1t = qfma(M11t, ut, M10t * un);
-    const double st0s = qfma(M01s, ut, M00s * un), st1s = qfma(M11s, ut, M10s * un);
-    const double st2s = qfma(facs, qfma(px, ut, -(py * un)), fac * qfma(pxs, ut, -(pys * un)));
-    const double vl0s = qfma(M01, gls, qfma(M01s, gl, M00s)), vl1s = qfma(M11, gls, qfma(M11s, gl, M10s));
-    const double vr0s = qfma(M01, grs, qfma(M01s, gr, M00s)), vr1s = qfma(M11, grs, qfma(M11s, gr, M10s));
-    const double vl0t = qfma(M01t, gl, M00t), vl1t = qfma(M11t, gl, M10t);
-    const double vr0t = qfma(M01t, gr, M00t), vr1t = qfma(M11t, gr, M10t);
-    const double wls = qfma(facs, qfma(gl, px, -py), fac * (qfma(gl, pxs, gls * px) - pys));
-    const double wrs = qfma(facs, qfma(gr, px, -py), fac * (qfma(gr, pxs, grs * px) - pys));
-    o->Jth[0] = blend3(ist, st0t, isl, vl0t * un, isr, vr0t * un);
-    o->Jth[1] = blend3(ist, st1t, isl, vl1t * un, isr, vr1t * un);
-    o->Js[0] = blend3(ist, st0s, isl, vl0s * un, isr, vr0s * un);
-    o->Js[1] = blend3(ist, st1s, isl, vl1s * un, isr, vr1s * un);
-    o->Js[2] = blend3(ist, st2s, isl, wls * un, isr, wrs * un);
-    o->Js[3] = -qfma(isr, grs * un, isl * (gls * un));
-    o->Jun[0] = blend3(ist, M00, isl, vl0, isr, vr0);
-    o->Jun[1] = blend3(ist, M10, isl, vl1, isr, vr1);
-    o->Jun[2] = blend3(-ist, fac * py, isl, wl, isr, wr);
-    o->Jun[3] = -qfma(isr, gr, isl * gl);
-    o->Jut[0] = ist * M01;
-    o->Jut[1] = ist * M11;
-    o->Jut[2] = ist * (fac * px);
-    o->Jut[3] = isl + isr;
-}
-
-/* ------------------------------------------------------------------ RK4 + VDE (rk4) */
-typedef struct { double xn[4], a[6], B[8]; } lin;
-
-static void rk4(const tw_shape *sh, double h, const double x[4], const double u[2], lin *o, int with_sens)
-{
-    static const double ca[4] = {0.0, 0.5, 0.5, 1.0};
-    const double cb[4] = {1.0 / 6.0, 1.0 / 3.0, 1.0 / 3.0, 1.0 / 6.0};
-    double acc[4] = {x[0], x[1], x[2], x[3]};
-    double Sa[4][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {1, 0, 0, 0}, {0, 1, 0, 0}};
-    double K[4] = {0, 0, 0, 0};
-    double SK[4][4] = {{0}};
-    for (int st = 0; st < 4; ++st) {
-        const double aa = h * ca[st];
-        double xs[4], Ss[2][4];
-        for (int i = 0; i < 4; ++i) xs[i] = (st == 0) ? x[i] : qfma(aa, K[i], x[i]);
-        for (int c = 0; c < 4; ++c) {
-            const double e2 = (c == 0) ? 1.0 : 0.0, e3 = (c == 1) ? 1.0 : 0.0;
-            Ss[0][c] = (st == 0) ? e2 : qfma(aa, SK[2][c], e2);
-            Ss[1][c] = (st == 0) ? e3 : qfma(aa, SK[3][c], e3);
-        }
-        dyn d;
-        dynamics(sh, xs[2], xs[3], u[0], u[1], &d, with_sens);
-        for (int i = 0; i < 4; ++i) K[i] = d.f[i];
-        if (with_sens) {
-            for (int c = 0; c < 4; ++c) {
-                const double jt = Ss[0][c], js = Ss[1][c];
-                SK[0][c] = qfma(d.Js[0], js, d.Jth[0] * jt);
-                SK[1][c] = qfma(d.Js[1], js, d.Jth[1] * jt);
-                SK[2][c] = d.Js[2] * js;
-                SK[3][c] = d.Js[3] * js;
-            }
-            for (int i = 0; i < 4; ++i) {
-                SK[i][2] += d.Jun[i];
-                SK[i][3] += d.Jut[i];
-            }
-        }
-        const double w = h * cb[st];
-        for (int i = 0; i < 4; ++i) acc[i] = qfma(w, K[i], acc[i]);
-        if (with_sens)
-            for (int i = 0; i < 4; ++i)
-                for (int c = 0; c < 4; ++c) Sa[i][c] = qfma(w, SK[i][c], Sa[i][c]);
-    }
-    for (int i = 0; i < 4; ++i) o->xn[i] = acc[i];
-    if (with_sens) {
-        o->a[0] = Sa[0][0]; o->a[1] = Sa[0][1];
-        o->a[2] = Sa[1][0]; o->a[3] = Sa[1][1];
-        o->a[4] = Sa[2][1]; o->a[5] = Sa[3][1];
-        for (int i = 0; i < 4; ++i) { o->B[2 * i] = Sa[i][2]; o->B[2 * i + 1] = Sa[i][3]; }
-    }
-}
-
 /* ================================================================== the QP (qp_ipm) */
 typedef struct {
     double a[6], B[8], bb[4], g[6], v[3];
@@ -356,18 +87,15 @@ typedef struct {
     double at[6], al[6], dt[6], dl[6];
 } tw_stage;
 
-/* the solve parameters the kernels read (SolveParams): the options plus the QP-level overrides */
-typedef struct {
-    int N, S, L, nlp_mode, sqp_iters, qp_iters, qp_stall_iters, s0_bound, factor_scan, mfma_walk;
-    double Ts, tau, W[6], We[4], lh[3], uh[3];
-    double mu0, t_min, frac, sigma_min, mu_stop, res_stop, qp_tol_stat, qp_tol_eq, qp_stall_alpha, qp_mu_max;
-    double tol_stat, tol_eq, tol_ineq, tol_comp, ls_alpha_min, ls_alpha_red, ls_eps;
-    double v_alpha, d_v, t_angle0, u_n_lb, u_t_ub;
-} tw_par;
+/* the solve parameters the kernels read, plus the layout they imply.  mfma_walk is the twin's own
+ * decision here (mfw_on / mfw_is, the kernels' record layout, stay unset) */
+struct tw_par : SolveParams {
+    int S, L;
+};
 
 static void make_par(tw_par *p, const or_opts *o)
 {
-    memset(p, 0, sizeof *p);
+    *p = tw_par{};
     p->N = o->N;
     p->S = stages_per_lane(o->N, o->nlp_mode, o->stages_per_lane);
     p->L = lanes_per_instance(p->N, p->S);
@@ -393,12 +121,12 @@ static void make_par(tw_par *p, const or_opts *o)
     p->qp_stall_alpha = o->qp_stall_alpha; p->qp_mu_max = o->qp_mu_max;
     p->tol_stat = o->tol_stat; p->tol_eq = o->tol_eq; p->tol_ineq = o->tol_ineq; p->tol_comp = o->tol_comp;
     p->ls_alpha_min = o->ls_alpha_min; p->ls_alpha_red = o->ls_alpha_red; p->ls_eps = o->ls_eps;
-    p->v_alpha = o->v_alpha; p->d_v = o->d_v; p->t_angle0 = o->t_angle0; p->u_n_lb = o->u_n_lb; p->u_t_ub = o->u_t_ub;
+    p->cp = CtrlParams{o->v_alpha, o->d_v, o->t_angle0, o->u_n_lb, o->u_t_ub};
 }
 
 /* The factorisation the twin emulates for these options, in the library's QSP_WALK_* coding
  * (qsp_get_factor_walk reports the library's side of the same choice). */
-int tw_factor_walk(const or_opts *o)
+extern "C" int tw_factor_walk(const or_opts *o)
 {
     tw_par p;
     make_par(&p, o);
@@ -435,95 +163,6 @@ static inline int bnd_act(const tw_par *p, int k, int j) { return (k < p->N) && 
 static inline void bnd_lohi(const tw_par *p, const tw_stage *s, double lo[3], double hi[3])
 {
     for (int j = 0; j < 3; ++j) { lo[j] = p->lh[j] - s->v[j]; hi[j] = p->uh[j] - s->v[j]; }
-}
-
-static inline int sidx(int i, int j)
-{
-    if (i > j) { int t = i; i = j; j = t; }
-    return i == 0 ? j : (i == 1 ? 3 + j : (i == 2 ? 5 + j : 9));
-}
-
-/* ric_factor_step */
-static void ric_factor_step(const double a[6], const double B[8], const double bb[4], const double Hx[4],
-                            const double Hu[2], const double gx[4], const double gu[2], double P[10], double pv[4],
-                            double K[8], double Rn[3], double kk[2], int upd)
-{
-    double Pm[4][4], PA[4][4], PB[4][2], pp[4], St[2][4], rt[2], Qt[10], qt[4];
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 4; ++j) Pm[i][j] = P[sidx(i, j)];
-    for (int i = 0; i < 4; ++i) {
-        PA[i][0] = Pm[i][0];
-        PA[i][1] = Pm[i][1];
-        PA[i][2] = qfma(Pm[i][1], a[2], qfma(Pm[i][0], a[0], Pm[i][2]));
-        PA[i][3] = qfma(Pm[i][3], a[5], qfma(Pm[i][2], a[4], qfma(Pm[i][1], a[3], Pm[i][0] * a[1])));
-    }
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 2; ++j)
-            PB[i][j] = qfma(Pm[i][3], B[6 + j], qfma(Pm[i][2], B[4 + j], qfma(Pm[i][1], B[2 + j], Pm[i][0] * B[j])));
-    for (int i = 0; i < 4; ++i)
-        pp[i] = qfma(Pm[i][3], bb[3], qfma(Pm[i][2], bb[2], qfma(Pm[i][1], bb[1], qfma(Pm[i][0], bb[0], pv[i]))));
-    const double R00 = qfma(B[6], PB[3][0], qfma(B[4], PB[2][0], qfma(B[2], PB[1][0], qfma(B[0], PB[0][0], Hu[0]))));
-    const double R01 = qfma(B[6], PB[3][1], qfma(B[4], PB[2][1], qfma(B[2], PB[1][1], B[0] * PB[0][1])));
-    const double R11 = qfma(B[7], PB[3][1], qfma(B[5], PB[2][1], qfma(B[3], PB[1][1], qfma(B[1], PB[0][1], Hu[1]))));
-    for (int i = 0; i < 2; ++i) {
-        St[i][0] = PB[0][i];
-        St[i][1] = PB[1][i];
-        St[i][2] = qfma(PB[1][i], a[2], qfma(PB[0][i], a[0], PB[2][i]));
-        St[i][3] = qfma(PB[3][i], a[5], qfma(PB[2][i], a[4], qfma(PB[1][i], a[3], PB[0][i] * a[1])));
-    }
-    for (int i = 0; i < 2; ++i)
-        rt[i] = qfma(B[6 + i], pp[3], qfma(B[4 + i], pp[2], qfma(B[2 + i], pp[1], qfma(B[i], pp[0], gu[i]))));
-    for (int j = 0; j < 4; ++j) {
-        const double c0 = PA[0][j], c1 = PA[1][j], c2 = PA[2][j], c3 = PA[3][j];
-        Qt[sidx(0, j)] = c0;
-        if (j >= 1) Qt[sidx(1, j)] = c1;
-        if (j >= 2) Qt[sidx(2, j)] = qfma(a[2], c1, qfma(a[0], c0, j == 2 ? Hx[2] + c2 : c2));
-        if (j >= 3) Qt[sidx(3, j)] = qfma(a[5], c3, qfma(a[4], c2, qfma(a[3], c1, qfma(a[1], c0, Hx[3]))));
-    }
-    Qt[0] += Hx[0];
-    Qt[4] += Hx[1];
-    qt[0] = gx[0] + pp[0];
-    qt[1] = gx[1] + pp[1];
-    qt[2] = qfma(a[2], pp[1], qfma(a[0], pp[0], gx[2] + pp[2]));
-    qt[3] = qfma(a[5], pp[3], qfma(a[4], pp[2], qfma(a[3], pp[1], qfma(a[1], pp[0], gx[3]))));
-    const double idet = rcp(qfma(R00, R11, -(R01 * R01)));
-    Rn[0] = (-R11) * idet; Rn[1] = R01 * idet; Rn[2] = (-R00) * idet;
-    for (int j = 0; j < 4; ++j) {
-        K[j] = qfma(Rn[1], St[1][j], Rn[0] * St[0][j]);
-        K[4 + j] = qfma(Rn[2], St[1][j], Rn[1] * St[0][j]);
-    }
-    kk[0] = qfma(Rn[1], rt[1], Rn[0] * rt[0]);
-    kk[1] = qfma(Rn[2], rt[1], Rn[1] * rt[0]);
-    if (!upd) return;
-    for (int i = 0; i < 4; ++i)
-        for (int j = i; j < 4; ++j) P[sidx(i, j)] = qfma(St[1][i], K[4 + j], qfma(St[0][i], K[j], Qt[sidx(i, j)]));
-    for (int i = 0; i < 4; ++i) pv[i] = qfma(K[4 + i], rt[1], qfma(K[i], rt[0], qt[i]));
-}
-
-/* ric_delta_step */
-static void ric_delta_step(const double a[6], const double B[8], double dgx3, const double dgu[2], const double K[8],
-                           const double Rn[3], double pv[4], double dkk[2])
-{
-    double rt[2], qt[4];
-    for (int i = 0; i < 2; ++i)
-        rt[i] = qfma(B[6 + i], pv[3], qfma(B[4 + i], pv[2], qfma(B[2 + i], pv[1], qfma(B[i], pv[0], dgu[i]))));
-    qt[0] = pv[0];
-    qt[1] = pv[1];
-    qt[2] = qfma(a[2], pv[1], qfma(a[0], pv[0], pv[2]));
-    qt[3] = qfma(a[5], pv[3], qfma(a[4], pv[2], qfma(a[3], pv[1], qfma(a[1], pv[0], dgx3))));
-    dkk[0] = qfma(Rn[1], rt[1], Rn[0] * rt[0]);
-    dkk[1] = qfma(Rn[2], rt[1], Rn[1] * rt[0]);
-    for (int i = 0; i < 4; ++i) pv[i] = qfma(K[4 + i], rt[1], qfma(K[i], rt[0], qt[i]));
-}
-
-/* dyn_step */
-static void dyn_step(const double a[6], const double B[8], const double bb[4], const double du[2], double dx[4])
-{
-    const double n0 = qfma(B[1], du[1], qfma(B[0], du[0], qfma(a[1], dx[3], qfma(a[0], dx[2], bb[0] + dx[0]))));
-    const double n1 = qfma(B[3], du[1], qfma(B[2], du[0], qfma(a[3], dx[3], qfma(a[2], dx[2], bb[1] + dx[1]))));
-    const double n2 = qfma(B[5], du[1], qfma(B[4], du[0], qfma(a[4], dx[3], bb[2] + dx[2])));
-    const double n3 = qfma(B[7], du[1], qfma(B[6], du[0], qfma(a[5], dx[3], bb[3])));
-    dx[0] = n0; dx[1] = n1; dx[2] = n2; dx[3] = n3;
 }
 
 /* barrier_terms */
@@ -632,77 +271,33 @@ static void apply_step(tw_stage *s, double alpha)
     }
 }
 
-/* ---- S = 2: the affine passes as scans (qsp_solver.hip Aff, aff_*; riccati_solve<2, ...>) */
-typedef struct { double F[16], c[4]; } tw_aff;   /* x -> F x + c */
-
-/* g <- g o f, in place row by row (aff_compose) */
-static void aff_compose(tw_aff *g, const tw_aff *f)
-{
-    for (int i = 0; i < 4; ++i) {
-        double r[5];
-        for (int j = 0; j < 4; ++j)
-            r[j] = qfma(g->F[4 * i + 3], f->F[12 + j], qfma(g->F[4 * i + 2], f->F[8 + j],
-                        qfma(g->F[4 * i + 1], f->F[4 + j], g->F[4 * i] * f->F[j])));
-        r[4] = qfma(g->F[4 * i + 3], f->c[3], qfma(g->F[4 * i + 2], f->c[2], qfma(g->F[4 * i + 1], f->c[1],
-                    qfma(g->F[4 * i], f->c[0], g->c[i]))));
-        for (int j = 0; j < 4; ++j) g->F[4 * i + j] = r[j];
-        g->c[i] = r[4];
-    }
-}
-static void aff_apply(const tw_aff *m, const double x[4], double y[4])
-{
-    for (int i = 0; i < 4; ++i)
-        y[i] = qfma(m->F[4 * i + 3], x[3], qfma(m->F[4 * i + 2], x[2], qfma(m->F[4 * i + 1], x[1], qfma(m->F[4 * i], x[0], m->c[i]))));
-}
-static void aff_identity(tw_aff *m)
-{
-    for (int q = 0; q < 16; ++q) m->F[q] = (q % 5 == 0) ? 1.0 : 0.0;
-    for (int q = 0; q < 4; ++q) m->c[q] = 0.0;
-}
-static void aff_forward(const tw_stage *s, tw_aff *m)
-{
-    const double *a = s->a, *B = s->B, *K = s->K;
-    const double Am[4][4] = {{1.0, 0.0, a[0], a[1]}, {0.0, 1.0, a[2], a[3]}, {0.0, 0.0, 1.0, a[4]}, {0.0, 0.0, 0.0, a[5]}};
-    for (int i = 0; i < 4; ++i) {
-        for (int q = 0; q < 4; ++q) m->F[4 * i + q] = qfma(B[2 * i + 1], K[4 + q], qfma(B[2 * i], K[q], Am[i][q]));
-        m->c[i] = qfma(B[2 * i + 1], s->kk[1], qfma(B[2 * i], s->kk[0], s->bb[i]));
-    }
-}
-static void aff_delta(const tw_stage *s, double dgx3, const double dgu[2], tw_aff *m)
-{
-    const double *a = s->a, *B = s->B, *K = s->K;
-    const double Am[4][4] = {{1.0, 0.0, a[0], a[1]}, {0.0, 1.0, a[2], a[3]}, {0.0, 0.0, 1.0, a[4]}, {0.0, 0.0, 0.0, a[5]}};
-    for (int i = 0; i < 4; ++i) {
-        for (int q = 0; q < 4; ++q) m->F[4 * q + i] = qfma(B[2 * i + 1], K[4 + q], qfma(B[2 * i], K[q], Am[i][q]));
-        m->c[i] = qfma(K[4 + i], dgu[1], qfma(K[i], dgu[0], i == 3 ? dgx3 : 0.0));
-    }
-}
-
+/* ---- S = 2: the affine passes as scans (riccati_solve<2, ...>; Aff, aff_*: qsp_riccati.hpp) */
 /* the S = 2 difference pass: suffix scan of the lanes' backward maps (slot 1's, then slot 0's;
  * identity past the horizon), dp_N = 0; each slot's dkk from the dp reaching it */
 static void delta_scan_s2(const tw_par *p, tw_stage *st, const double *gx3, double (*gu)[2])
 {
     const int N = p->N, L = p->L;
-    tw_aff d[64], nd[64];
+    Aff d[64], nd[64];
     for (int l = 0; l < L; ++l) {
         const int k0 = 2 * l;
         if (k0 + 1 < N) {
-            tw_aff m1;
-            aff_delta(st + k0, gx3[k0], gu[k0], d + l);
-            aff_delta(st + k0 + 1, gx3[k0 + 1], gu[k0 + 1], &m1);
-            aff_compose(d + l, &m1);
+            const tw_stage *s0 = st + k0, *s1 = st + k0 + 1;
+            Aff m1;
+            aff_delta(s0->a, s0->B, s0->K, gx3[k0], gu[k0], d[l]);
+            aff_delta(s1->a, s1->B, s1->K, gx3[k0 + 1], gu[k0 + 1], m1);
+            aff_compose(d[l], m1);
         } else if (k0 < N) {
-            aff_delta(st + k0, gx3[k0], gu[k0], d + l);
+            aff_delta(st[k0].a, st[k0].B, st[k0].K, gx3[k0], gu[k0], d[l]);
         } else {
-            aff_identity(d + l);
+            aff_identity(d[l]);
         }
     }
     for (int off = 1; off < L; off <<= 1) {
         for (int l = 0; l < L; ++l) {
             nd[l] = d[l];
-            if (l + off < L) aff_compose(nd + l, d + l + off);
+            if (l + off < L) aff_compose(nd[l], d[l + off]);
         }
-        memcpy(d, nd, sizeof(tw_aff) * (size_t)L);
+        memcpy(d, nd, sizeof(Aff) * (size_t)L);
     }
     for (int l = 0; l < L; ++l) {
         double pv[4];
@@ -725,30 +320,31 @@ static void delta_scan_s2(const tw_par *p, tw_stage *st, const double *gx3, doub
 static void forward_scan_s2(const tw_par *p, tw_stage *st, const double dx0[4], int factor)
 {
     const int N = p->N, L = p->L;
-    tw_aff e[64], ne[64];
+    Aff e[64], ne[64];
     for (int l = 0; l < L; ++l) {
         const int k0 = 2 * l;
         if (k0 + 1 < N) {   /* the last lane's map is consumed by no lane (values there are unused) */
-            tw_aff m1;
-            aff_forward(st + k0, e + l);
-            aff_forward(st + k0 + 1, &m1);
-            aff_compose(&m1, e + l);
+            const tw_stage *s0 = st + k0, *s1 = st + k0 + 1;
+            Aff m1;
+            aff_forward(s0->a, s0->B, s0->bb, s0->K, s0->kk, e[l]);
+            aff_forward(s1->a, s1->B, s1->bb, s1->K, s1->kk, m1);
+            aff_compose(m1, e[l]);
             e[l] = m1;
         } else {
-            aff_identity(e + l);
+            aff_identity(e[l]);
         }
     }
     for (int off = 1; off < L; off <<= 1) {
         for (int l = 0; l < L; ++l) {
             ne[l] = e[l];
-            if (l >= off) aff_compose(ne + l, e + l - off);
+            if (l >= off) aff_compose(ne[l], e[l - off]);
         }
-        memcpy(e, ne, sizeof(tw_aff) * (size_t)L);
+        memcpy(e, ne, sizeof(Aff) * (size_t)L);
     }
     for (int l = 0; l < L; ++l) {
         double dx[4];
         if (l == 0) memcpy(dx, dx0, sizeof dx);
-        else aff_apply(e + l - 1, dx0, dx);
+        else aff_apply(e[l - 1], dx0, dx);
         for (int ls = 0; ls < 2; ++ls) {
             const int k = 2 * l + ls;
             if (k >= N) break;
@@ -765,112 +361,31 @@ static void forward_scan_s2(const tw_par *p, tw_stage *st, const double dx0[4], 
     }
 }
 
-/* ---- S = 2: the factorisation as an associative scan (qsp_solver.hip VElem, velem_*; riccati_solve<2, true>):
- * the conditional value-function elements of Sarkka & Garcia-Fernandez (IEEE TAC 2023),
- * e_k = (A_k, c_k - B Hu^-1 gu, B Hu^-1 B', -gx, diag Hx), e_N = (0, 0, 0, -g_N, We), combined in
- * the kernel's association order; P_k = J, p_k = -eta of the suffix product over k..N */
-typedef struct { double A[16], b[4], C[10], eta[4], J[10]; } tw_velem;
-
-static void velem_stage(const double a[6], const double B[8], const double bb[4], const double Hx[4], const double Hu[2],
-                        const double gx[4], const double gu[2], tw_velem *e)
-{
-    const double F[16] = {1.0, 0.0, a[0], a[1], 0.0, 1.0, a[2], a[3], 0.0, 0.0, 1.0, a[4], 0.0, 0.0, 0.0, a[5]};
-    memcpy(e->A, F, sizeof F);
-    const double ih0 = rcp(Hu[0]), ih1 = rcp(Hu[1]);
-    const double v0 = ih0 * gu[0], v1 = ih1 * gu[1];
-    for (int i = 0; i < 4; ++i) {
-        e->b[i] = qfma(-B[2 * i + 1], v1, qfma(-B[2 * i], v0, bb[i]));
-        e->eta[i] = -gx[i];
-        const double w0 = B[2 * i] * ih0, w1 = B[2 * i + 1] * ih1;
-        for (int j = i; j < 4; ++j) {
-            e->C[sidx(i, j)] = qfma(w1, B[2 * j + 1], w0 * B[2 * j]);
-            e->J[sidx(i, j)] = (i == j) ? Hx[i] : 0.0;
-        }
-    }
-}
-static void velem_terminal(const double We[4], const double g[6], tw_velem *e)
-{
-    memset(e, 0, sizeof *e);
-    for (int q = 0; q < 4; ++q) { e->eta[q] = -g[q]; e->J[sidx(q, q)] = We[q]; }
-}
-/* e <- e (x) f in place (velem_combine) */
-static void velem_combine(tw_velem *e, const tw_velem *f)
-{
-    double T[4][4], TA[4][4], Um[4][4], w[4], z[4];
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 4; ++j)
-            T[i][j] = qfma(e->C[sidx(i, 3)], f->J[sidx(3, j)], qfma(e->C[sidx(i, 2)], f->J[sidx(2, j)],
-                      qfma(e->C[sidx(i, 1)], f->J[sidx(1, j)], qfma(e->C[sidx(i, 0)], f->J[sidx(0, j)], i == j ? 1.0 : 0.0))));
-    for (int c = 0; c < 4; ++c) {
-        const double piv = rcp(T[c][c]);
-        T[c][c] = 1.0;
-        for (int j = 0; j < 4; ++j) T[c][j] *= piv;
-        for (int r = 0; r < 4; ++r) {
-            if (r == c) continue;
-            const double fct = T[r][c];
-            T[r][c] = 0.0;
-            for (int j = 0; j < 4; ++j) T[r][j] = qfma(-fct, T[c][j], T[r][j]);
-        }
-    }
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 4; ++j) {
-            TA[i][j] = qfma(f->A[4 * i + 3], T[3][j], qfma(f->A[4 * i + 2], T[2][j], qfma(f->A[4 * i + 1], T[1][j], f->A[4 * i] * T[0][j])));
-            Um[i][j] = qfma(e->A[12 + i], T[j][3], qfma(e->A[8 + i], T[j][2], qfma(e->A[4 + i], T[j][1], e->A[i] * T[j][0])));
-        }
-    for (int i = 0; i < 4; ++i) {
-        w[i] = qfma(e->C[sidx(i, 3)], f->eta[3], qfma(e->C[sidx(i, 2)], f->eta[2], qfma(e->C[sidx(i, 1)], f->eta[1], qfma(e->C[sidx(i, 0)], f->eta[0], e->b[i]))));
-        z[i] = qfma(-f->J[sidx(i, 3)], e->b[3], qfma(-f->J[sidx(i, 2)], e->b[2], qfma(-f->J[sidx(i, 1)], e->b[1], qfma(-f->J[sidx(i, 0)], e->b[0], f->eta[i]))));
-    }
-    for (int i = 0; i < 4; ++i) {
-        e->b[i] = qfma(TA[i][3], w[3], qfma(TA[i][2], w[2], qfma(TA[i][1], w[1], qfma(TA[i][0], w[0], f->b[i]))));
-        e->eta[i] = qfma(Um[i][3], z[3], qfma(Um[i][2], z[2], qfma(Um[i][1], z[1], qfma(Um[i][0], z[0], e->eta[i]))));
-    }
-    {
-        double Y[4][4];
-        for (int i = 0; i < 4; ++i)
-            for (int j = 0; j < 4; ++j)
-                Y[i][j] = qfma(Um[i][3], f->J[sidx(3, j)], qfma(Um[i][2], f->J[sidx(2, j)], qfma(Um[i][1], f->J[sidx(1, j)], Um[i][0] * f->J[sidx(0, j)])));
-        for (int i = 0; i < 4; ++i)
-            for (int j = i; j < 4; ++j)
-                e->J[sidx(i, j)] = qfma(Y[i][3], e->A[12 + j], qfma(Y[i][2], e->A[8 + j], qfma(Y[i][1], e->A[4 + j], qfma(Y[i][0], e->A[j], e->J[sidx(i, j)]))));
-    }
-    {
-        double X[4][4];
-        for (int i = 0; i < 4; ++i)
-            for (int j = 0; j < 4; ++j)
-                X[i][j] = qfma(TA[i][3], e->C[sidx(3, j)], qfma(TA[i][2], e->C[sidx(2, j)], qfma(TA[i][1], e->C[sidx(1, j)], TA[i][0] * e->C[sidx(0, j)])));
-        for (int i = 0; i < 4; ++i)
-            for (int j = i; j < 4; ++j)
-                e->C[sidx(i, j)] = qfma(X[i][3], f->A[4 * j + 3], qfma(X[i][2], f->A[4 * j + 2], qfma(X[i][1], f->A[4 * j + 1], qfma(X[i][0], f->A[4 * j], f->C[sidx(i, j)]))));
-    }
-    for (int j = 0; j < 4; ++j) {
-        const double c0 = e->A[j], c1 = e->A[4 + j], c2 = e->A[8 + j], c3 = e->A[12 + j];
-        for (int i = 0; i < 4; ++i) e->A[4 * i + j] = qfma(TA[i][3], c3, qfma(TA[i][2], c2, qfma(TA[i][1], c1, TA[i][0] * c0)));
-    }
-}
-
+/* ---- S = 2: the factorisation as an associative scan (riccati_solve<2, true>): the conditional
+ * value-function elements (VElem, velem_*: qsp_riccati.hpp) combined in the kernel's association
+ * order; P_k = J, p_k = -eta of the suffix product over k..N */
 /* developer check of the element arithmetic (scripts/ubench/velem_check.hip runs the same on the
  * device): per case two stages (a, B, bb, Hx, Hu, gx, gu: 30 doubles each) and a terminal (We, g: 8);
  * out = e0 (x) e1, then (x) the terminal element (We[0] > 0) or (x) e1 (x) e0 (We[0] <= 0): 2 x 44 doubles */
-void tw_velem_check(int32_t n, const double *in, double *out)
+extern "C" void tw_velem_check(int32_t n, const double *in, double *out)
 {
     for (int i = 0; i < n; ++i) {
         const double *c = in + (size_t)i * 68;
-        tw_velem e, e1, t;
-        velem_stage(c, c + 6, c + 14, c + 18, c + 22, c + 24, c + 28, &e);
-        velem_stage(c + 30, c + 36, c + 44, c + 48, c + 52, c + 54, c + 58, &e1);
-        velem_combine(&e, &e1);
+        VElem e, e1, t;
+        velem_stage(c, c + 6, c + 14, c + 18, c + 22, c + 24, c + 28, e);
+        velem_stage(c + 30, c + 36, c + 44, c + 48, c + 52, c + 54, c + 58, e1);
+        velem_combine(e, e1);
         memcpy(out + (size_t)i * 88, &e, sizeof e);
         const double g6[6] = {c[64], c[65], c[66], c[67], 0.0, 0.0};
         if (c[60] > 0.0) {
-            velem_terminal(c + 60, g6, &t);
+            velem_terminal(c + 60, g6, t);
         } else {   /* a general element on the right: the case's two stages combined in the other order */
-            tw_velem u;
-            velem_stage(c + 30, c + 36, c + 44, c + 48, c + 52, c + 54, c + 58, &t);
-            velem_stage(c, c + 6, c + 14, c + 18, c + 22, c + 24, c + 28, &u);
-            velem_combine(&t, &u);
+            VElem u;
+            velem_stage(c + 30, c + 36, c + 44, c + 48, c + 52, c + 54, c + 58, t);
+            velem_stage(c, c + 6, c + 14, c + 18, c + 22, c + 24, c + 28, u);
+            velem_combine(t, u);
         }
-        velem_combine(&e, &t);
+        velem_combine(e, t);
         memcpy(out + (size_t)i * 88 + 44, &e, sizeof e);
     }
 }
@@ -882,12 +397,12 @@ static void factor_scan_s2(const tw_par *p, tw_stage *st, const double *hx3, dou
                            double (*gu)[2])
 {
     const int N = p->N, L = p->L;
-    tw_velem e[64], ne[64], e1[64];
+    VElem e[64], ne[64], e1[64];
     for (int l = 0; l < L; ++l) {
         const int k0 = 2 * l, k1 = k0 + 1;
         for (int ls = 0; ls < 2; ++ls) {
             const int k = k0 + ls;
-            tw_velem *d = ls == 0 ? e + l : e1 + l;
+            VElem &d = ls == 0 ? e[l] : e1[l];
             if (k < N) {
                 const tw_stage *s = st + k;
                 const double Hx[4] = {p->tau * p->W[0], p->tau * p->W[1], p->tau * p->W[2], hx3[k]};
@@ -897,27 +412,27 @@ static void factor_scan_s2(const tw_par *p, tw_stage *st, const double *hx3, dou
                 velem_terminal(p->We, st[N].g, d);
             }
         }
-        if (k1 <= N) velem_combine(e + l, e1 + l);
+        if (k1 <= N) velem_combine(e[l], e1[l]);
     }
     for (int off = 1; off < L; off <<= 1) {
         for (int l = 0; l < L; ++l) {
             ne[l] = e[l];
-            if (l + off < L) velem_combine(ne + l, e + l + off);
+            if (l + off < L) velem_combine(ne[l], e[l + off]);
         }
-        memcpy(e, ne, sizeof(tw_velem) * (size_t)L);
+        memcpy(e, ne, sizeof(VElem) * (size_t)L);
     }
     for (int l = 0; l < L; ++l) {
         const int k0 = 2 * l, k1 = k0 + 1;
         if (k1 < N) {
-            const tw_velem *f = e + l + 1;
-            velem_combine(e1 + l, f);
+            const VElem &f = e[l + 1];
+            velem_combine(e1[l], f);
             double Pn[10], pn[4];
-            for (int q = 0; q < 10; ++q) Pn[q] = f->J[q];
-            for (int q = 0; q < 4; ++q) pn[q] = -f->eta[q];
+            for (int q = 0; q < 10; ++q) Pn[q] = f.J[q];
+            for (int q = 0; q < 4; ++q) pn[q] = -f.eta[q];
             tw_stage *s = st + k1;
             const double gx[4] = {s->g[0], s->g[1], s->g[2], gx3[k1]};
             const double Hx[4] = {p->tau * p->W[0], p->tau * p->W[1], p->tau * p->W[2], hx3[k1]};
-            ric_factor_step(s->a, s->B, s->bb, Hx, hu[k1], gx, gu[k1], Pn, pn, s->K, s->Rn, s->kk, 0);
+            ric_factor_step(s->a, s->B, s->bb, Hx, hu[k1], gx, gu[k1], Pn, pn, s->K, s->Rn, s->kk, false);
         }
         if (k0 < N) {
             double Pn[10], pn[4];
@@ -926,7 +441,7 @@ static void factor_scan_s2(const tw_par *p, tw_stage *st, const double *hx3, dou
             tw_stage *s = st + k0;
             const double gx[4] = {s->g[0], s->g[1], s->g[2], gx3[k0]};
             const double Hx[4] = {p->tau * p->W[0], p->tau * p->W[1], p->tau * p->W[2], hx3[k0]};
-            ric_factor_step(s->a, s->B, s->bb, Hx, hu[k0], gx, gu[k0], Pn, pn, s->K, s->Rn, s->kk, 0);
+            ric_factor_step(s->a, s->B, s->bb, Hx, hu[k0], gx, gu[k0], Pn, pn, s->K, s->Rn, s->kk, false);
         }
     }
 }
@@ -1022,7 +537,6 @@ static void factor_walk_mfma(const tw_par *p, tw_stage *st, const double *hx3, d
 static void riccati_solve(const tw_par *p, tw_stage *st, const double dx0[4], int factor)
 {
     const int N = p->N, S = p->S;
-    double P[10], pv[4];
     double hx3[TW_MAX_SLOTS], hu[TW_MAX_SLOTS][2], gx3[TW_MAX_SLOTS], gu[TW_MAX_SLOTS][2];
     for (int k = 0; k < N; ++k) {
         const tw_stage *s = st + k;
@@ -1064,26 +578,14 @@ static void riccati_solve(const tw_par *p, tw_stage *st, const double dx0[4], in
         factor_scan_s2(p, st, hx3, hu, gx3, gu);
     } else if (factor && p->mfma_walk) {
         factor_walk_mfma(p, st, hx3, hu, gx3, gu);
-    } else {
-        if (factor) {
-            for (int i = 0; i < 10; ++i) P[i] = 0.0;
-            P[0] = p->We[0]; P[4] = p->We[1]; P[7] = p->We[2]; P[9] = p->We[3];
-            for (int i = 0; i < 4; ++i) pv[i] = st[N].g[i];
-        } else {
-            for (int i = 0; i < 4; ++i) pv[i] = 0.0;
-        }
+    } else {   /* the factorisation by the lane walk (both difference passes are taken above) */
+        double P[10], pv[4];
+        ric_terminal(*p, st[N].g, P, pv);
         for (int k = N - 1; k >= 0; --k) {
             tw_stage *s = st + k;
-            if (factor) {
-                const double gx[4] = {s->g[0], s->g[1], s->g[2], gx3[k]};
-                const double Hx[4] = {p->tau * p->W[0], p->tau * p->W[1], p->tau * p->W[2], hx3[k]};
-                ric_factor_step(s->a, s->B, s->bb, Hx, hu[k], gx, gu[k], P, pv, s->K, s->Rn, s->kk, k > 0);
-            } else {
-                double dkk[2];
-                ric_delta_step(s->a, s->B, gx3[k], gu[k], s->K, s->Rn, pv, dkk);
-                s->kk[0] += dkk[0];
-                s->kk[1] += dkk[1];
-            }
+            const double gx[4] = {s->g[0], s->g[1], s->g[2], gx3[k]};
+            const double Hx[4] = {p->tau * p->W[0], p->tau * p->W[1], p->tau * p->W[2], hx3[k]};
+            ric_factor_step(s->a, s->B, s->bb, Hx, hu[k], gx, gu[k], P, pv, s->K, s->Rn, s->kk, k > 0);
         }
     }
     double dx[4] = {dx0[0], dx0[1], dx0[2], dx0[3]};
@@ -1113,21 +615,7 @@ static void riccati_solve(const tw_par *p, tw_stage *st, const double dx0[4], in
         }
         return;
     }
-    if (S == 2) {
-        forward_scan_s2(p, st, dx0, factor);
-        return;
-    }
-    for (int k = 0; k < N; ++k) {
-        tw_stage *s = st + k;
-        double du[2];
-        du[0] = qfma(s->K[3], dx[3], qfma(s->K[2], dx[2], qfma(s->K[1], dx[1], qfma(s->K[0], dx[0], s->kk[0]))));
-        du[1] = qfma(s->K[7], dx[3], qfma(s->K[6], dx[2], qfma(s->K[5], dx[1], qfma(s->K[4], dx[0], s->kk[1]))));
-        double *out = factor ? s->VA : s->VN;
-        out[0] = dx[3];
-        out[1] = du[0];
-        out[2] = du[1];
-        dyn_step(s->a, s->B, s->bb, du, dx);
-    }
+    forward_scan_s2(p, st, dx0, factor);
 }
 
 enum { QP_EXIT_CONV = 0, QP_EXIT_CAP = 1, QP_EXIT_STALL = 2, QP_EXIT_DIVERGED = 3 };
@@ -1239,19 +727,6 @@ static void qp_rollout(const tw_par *p, tw_stage *st, const double dx0[4])
     }
 }
 
-/* adjoint_step */
-static void adjoint_step(const tw_par *p, const double a[6], const double dx[4], const double g[6], double dlam_s,
-                         double pi[4])
-{
-    double np[4];
-    np[0] = qfma(p->tau * p->W[0], dx[0], g[0]) + pi[0];
-    np[1] = qfma(p->tau * p->W[1], dx[1], g[1]) + pi[1];
-    np[2] = qfma(p->tau * p->W[2], dx[2], g[2]) + (qfma(a[2], pi[1], a[0] * pi[0]) + pi[2]);
-    np[3] = qfma(p->tau * p->W[3], dx[3], g[3]) + qfma(a[5], pi[3], qfma(a[4], pi[2], qfma(a[3], pi[1], a[1] * pi[0])));
-    np[3] += dlam_s;
-    memcpy(pi, np, sizeof np);
-}
-
 /* the QP's dynamics multipliers pi_k (k = 0..N-1) by the adjoint recursion (qp_adjoint_store) */
 static void qp_adjoint(const tw_par *p, const tw_stage *st, double *PI /* N x 4 */)
 {
@@ -1260,7 +735,7 @@ static void qp_adjoint(const tw_par *p, const tw_stage *st, double *PI /* N x 4 
     for (int i = 0; i < 4; ++i) pi[i] = qfma(p->We[i], st[N].dxs[i], st[N].g[i]);
     for (int k = N - 1; k >= 0; --k) {
         memcpy(PI + 4 * k, pi, sizeof pi);
-        if (k >= 1) adjoint_step(p, st[k].a, st[k].dxs, st[k].g, st[k].lm[1] - st[k].lm[0], pi);
+        if (k >= 1) adjoint_step(*p, st[k].a, st[k].dxs, st[k].g, st[k].lm[1] - st[k].lm[0], pi);
     }
 }
 
@@ -1276,18 +751,18 @@ typedef struct {
  * stationarity, equality, inequality, complementarity residuals of the last KKT test, its SQP
  * iteration, the last line-search step length.  NULL: off. */
 static double *g_kkt_diag = NULL;
-void tw_set_kkt_diag(double *buf) { g_kkt_diag = buf; }
+extern "C" void tw_set_kkt_diag(double *buf) { g_kkt_diag = buf; }
 
 /* stage data of slot k from the SQP iterate (qp_step_kernel's LIN block) */
-static void load_stage(const tw_par *p, const tw_shape *sh, tw_stage *s, int k, const double *X, const double *U,
+static void load_stage(const tw_par *p, const ShapeDev *sh, tw_stage *s, int k, const double *X, const double *U,
                        const double *yref, const double *ye, int lin_live)
 {
     const int N = p->N;
     const int kc = k <= N ? k : N, ku = k < N ? k : N - 1;
     if (kc < N && lin_live) {
         const double *xk = X + 4 * kc, *uk = U + 2 * kc;
-        lin Ln;
-        rk4(sh, p->Ts, xk, uk, &Ln, 1);
+        Lin Ln;
+        rk4<true>(*sh, p->Ts, xk, uk, Ln);
         const double *yr = yref + 6 * kc;
         memcpy(s->a, Ln.a, sizeof s->a);
         memcpy(s->B, Ln.B, sizeof s->B);
@@ -1350,32 +825,8 @@ static int nlp_converged(const tw_par *p, const tw_stage *st, const double *PI, 
     return rs < p->tol_stat && re < p->tol_eq && ri < p->tol_ineq && rc < p->tol_comp;
 }
 
-/* merit_stage */
-static double merit_stage(const tw_par *p, int k, const double x[4], const double u[2], const double *yr,
-                          const double *ye, const double def[4], const double nu[4], const double eta[6])
-{
-    if (k == p->N) {
-        double s = 0.0;
-        for (int i = 0; i < 4; ++i) { const double r = x[i] - ye[i]; s = qfma(p->We[i] * r, r, s); }
-        return 0.5 * s;
-    }
-    double s = 0.0;
-    for (int i = 0; i < 4; ++i) { const double r = x[i] - yr[i]; s = qfma(p->W[i] * r, r, s); }
-    for (int i = 0; i < 2; ++i) { const double r = u[i] - yr[4 + i]; s = qfma(p->W[4 + i] * r, r, s); }
-    double ph = 0.5 * p->tau * s;
-    for (int i = 0; i < 4; ++i) ph = qfma(nu[i], fabs(def[i]), ph);
-    const double v[3] = {x[3], u[0], u[1]};
-    for (int j = 0; j < 3; ++j) {
-        if (j == 0 && k == 0 && !p->s0_bound) continue;
-        const double vl = p->lh[j] - v[j], vh = v[j] - p->uh[j];
-        if (vl > 0.0) ph = qfma(eta[2 * j], vl, ph);
-        if (vh > 0.0) ph = qfma(eta[2 * j + 1], vh, ph);
-    }
-    return ph;
-}
-
 /* merit_ls_kernel for one instance (stages = lanes 0..N of its group) */
-static void merit_ls(const tw_par *p, const tw_shape *sh, tw_ws *w, double *X, double *U, const double *yref,
+static void merit_ls(const tw_par *p, const ShapeDev *sh, tw_ws *w, double *X, double *U, const double *yref,
                      const double *ye)
 {
     const int N = p->N, L = N + 1;
@@ -1418,7 +869,7 @@ static void merit_ls(const tw_par *p, const tw_shape *sh, tw_ws *w, double *X, d
     }
     for (int k = 0; k <= N; ++k) {
         const int ku = k < N ? k : N - 1;
-        lane[k] = merit_stage(p, k, xk[k], uk[k], yref + 6 * ku, ye, st[k].bb, NUk[k], ETAk[k]);
+        lane[k] = merit_stage(*p, k, xk[k], uk[k], yref + 6 * ku, ye, st[k].bb, NUk[k], ETAk[k]);
     }
     const double phi0 = group_sum(lane, L);
     for (int k = 0; k <= N; ++k) lane[k] = dph[k];
@@ -1434,12 +885,12 @@ static void merit_ls(const tw_par *p, const tw_shape *sh, tw_ws *w, double *X, d
         for (int k = 0; k <= N; ++k) {
             double def[4] = {0.0, 0.0, 0.0, 0.0};
             if (k < N) {
-                lin Lt;
-                rk4(sh, p->Ts, xt[k], ut[k], &Lt, 0);
+                Lin Lt;
+                rk4<false>(*sh, p->Ts, xt[k], ut[k], Lt);
                 for (int q = 0; q < 4; ++q) def[q] = Lt.xn[q] - xt[k + 1][q];
             }
             const int ku = k < N ? k : N - 1;
-            lane[k] = merit_stage(p, k, xt[k], ut[k], yref + 6 * ku, ye, def, NUk[k], ETAk[k]);
+            lane[k] = merit_stage(*p, k, xt[k], ut[k], yref + 6 * ku, ye, def, NUk[k], ETAk[k]);
         }
         const double phi = group_sum(lane, L);
         if (phi <= qfma(p->ls_eps * alpha, dphi, phi0)) break;
@@ -1476,7 +927,7 @@ typedef struct {
  * staged y_ref; PI_out (N x 4) receives the multipliers (nlp_mode 0: the last successful QP's,
  * shifted when `shift`; nlp_mode 1: the NLP iterate's, written by the epilogue).  PI_in: the
  * initial dynamics multipliers (nlp_mode 1; NULL: zeros). */
-static void sqp_solve(const tw_par *p, const tw_shape *sh, tw_ws *w, const double x0[4], const double *yref,
+static void sqp_solve(const tw_par *p, const ShapeDev *sh, tw_ws *w, const double x0[4], const double *yref,
                       const double *ye, double *X, double *U, const double *PI_in, double *PI_out, int shift,
                       int wdone0, tw_out *o)
 {
@@ -1590,17 +1041,19 @@ static double epilogue_cost(const tw_par *p, const double *X, const double *U, c
 static int s0_infeasible(const tw_par *p, double s0) { return p->s0_bound && !(s0 >= p->lh[0] && s0 <= p->uh[0]); }
 
 /* ================================================================== exported API (as qsp_oracle.c) */
+extern "C" {
+
 int tw_spline_eval(const int32_t *n_ctrl, const double *ctrl, const double *knots, const double *params,
                    int max_ctrl, int32_t n, const int32_t *shape_id, const double *s,
                    double *C, double *D, double *Dd, double *kappa)
 {
     for (int32_t i = 0; i < n; ++i) {
-        tw_shape sh;
+        ShapeDev sh;
         make_shape(&sh, n_ctrl, ctrl, knots, params, max_ctrl, shape_id[i], 0.0);
-        spl e;
-        spline_eval(&sh, s[i], &e);
+        SplineEval e;
+        spline_eval(sh, s[i], e);
         for (int c = 0; c < 2; ++c) { C[2 * i + c] = e.C[c]; D[2 * i + c] = e.D[c]; Dd[2 * i + c] = e.Dd[c]; }
-        kappa[i] = angle_rate_of(&e);
+        kappa[i] = angle_rate_of(e);
     }
     return 0;
 }
@@ -1610,10 +1063,10 @@ int tw_dynamics(const int32_t *n_ctrl, const double *ctrl, const double *knots, 
 {
     #pragma omp parallel for schedule(static)
     for (int32_t i = 0; i < n; ++i) {
-        tw_shape sh;
+        ShapeDev sh;
         make_shape(&sh, n_ctrl, ctrl, knots, params, max_ctrl, shape_id[i], 0.0);
-        dyn d;
-        dynamics(&sh, x[4 * i + 2], x[4 * i + 3], u[2 * i], u[2 * i + 1], &d, 1);
+        DynOut d;
+        dynamics<true>(sh, x[4 * i + 2], x[4 * i + 3], u[2 * i], u[2 * i + 1], d);
         for (int r = 0; r < 4; ++r) {
             f[4 * i + r] = d.f[r];
             if (J) {
@@ -1633,10 +1086,10 @@ int tw_rk4(const int32_t *n_ctrl, const double *ctrl, const double *knots, const
 {
     #pragma omp parallel for schedule(static)
     for (int32_t i = 0; i < n; ++i) {
-        tw_shape sh;
+        ShapeDev sh;
         make_shape(&sh, n_ctrl, ctrl, knots, params, max_ctrl, shape_id[i], 0.0);
-        lin L;
-        rk4(&sh, h, x + 4 * i, u + 2 * i, &L, 1);
+        Lin L;
+        rk4<true>(sh, h, x + 4 * i, u + 2 * i, L);
         const double Af[16] = {1.0, 0.0, L.a[0], L.a[1], 0.0, 1.0, L.a[2], L.a[3], 0.0, 0.0, 1.0, L.a[4], 0.0, 0.0, 0.0, L.a[5]};
         memcpy(A + (size_t)16 * i, Af, sizeof Af);
         memcpy(B + (size_t)8 * i, L.B, sizeof L.B);
@@ -1649,9 +1102,9 @@ int tw_vbound(const int32_t *n_ctrl, const double *ctrl, const double *knots, co
               int max_ctrl, const or_opts *o, int32_t n, const int32_t *shape_id, const double *s, double *vb)
 {
     for (int32_t i = 0; i < n; ++i) {
-        tw_shape sh;
+        ShapeDev sh;
         make_shape(&sh, n_ctrl, ctrl, knots, params, max_ctrl, shape_id[i], 0.0);
-        vb[i] = v_bound(&sh, o, s[i]);
+        vb[i] = v_bound(sh, CtrlParams{o->v_alpha, o->d_v, o->t_angle0, o->u_n_lb, o->u_t_ub}, s[i]);
     }
     return 0;
 }
@@ -1750,7 +1203,7 @@ int tw_ocp_solve(const int32_t *n_ctrl, const double *ctrl, const double *knots,
         tw_ws *w = (tw_ws *)malloc(sizeof(tw_ws));
         #pragma omp for schedule(dynamic, 1)
         for (int32_t i = 0; i < nb; ++i) {
-            tw_shape sh;
+            ShapeDev sh;
             make_shape(&sh, n_ctrl, ctrl, knots, params, max_ctrl, shape_id[i], 0.0);
             double *Xi = X + (size_t)i * 4 * (N + 1), *Ui = U + (size_t)i * 2 * N, *Pi = PI + (size_t)i * 4 * N;
             const double *yr = yref + (size_t)i * 6 * N, *ye = yref_e + (size_t)i * 4;
@@ -1797,7 +1250,7 @@ static void stage_yref(const double *traj, int32_t T, int32_t D, int32_t index_t
 
 /* NMPC_controller.solve on one lane (prologue_kernel in controller mode, the SQP, the epilogue's
  * shifted warm start).  Warm X/U/PI + valid in/out; returns the status. */
-static int ctrl_lane(const tw_par *p, const tw_shape *sh, tw_ws *w, const double x0_in[4], const double *traj,
+static int ctrl_lane(const tw_par *p, const ShapeDev *sh, tw_ws *w, const double x0_in[4], const double *traj,
                      int32_t T, int32_t D, int32_t index_time, double *Xw, double *Uw, double *PIw, uint8_t *valid,
                      double u0[2], tw_out *out, double *cost)
 {
@@ -1808,31 +1261,21 @@ static int ctrl_lane(const tw_par *p, const tw_shape *sh, tw_ws *w, const double
     x0[3] = qfma(-sh->b, (x0[3] < 0.0) ? 1.0 : 0.0, mat_mod(x0[3], sh->b));
     const int cold = !*valid;
     for (int k = 0; k < N; ++k) {
-        U[2 * k] = cold ? p->u_n_lb : Uw[2 * k];
+        U[2 * k] = cold ? p->cp.u_n_lb : Uw[2 * k];
         U[2 * k + 1] = cold ? 0.0 : Uw[2 * k + 1];
     }
     double xc[4] = {x0[0], x0[1], x0[2], x0[3]};
-    const or_opts *oo = NULL;
-    (void)oo;
     for (int k = 0; k <= N; ++k) {
         for (int c = 0; c < 4; ++c) X[4 * k + c] = xc[c];
         if (k == N) break;
-        /* v_bound with the handle's controller parameters */
-        const double sm = mat_mod(xc[3], sh->b);
-        spl e;
-        spline_eval(sh, sm, &e);
-        const double ta = fabs(angle_rate_of(&e));
-        double vb = p->v_alpha / (fabs(ta - p->t_angle0) + 0.0001) + p->d_v;
-        vb = vb < p->u_t_ub ? vb : p->u_t_ub;
+        const double vb = v_bound(*sh, p->cp, xc[3]);   /* with the handle's controller parameters */
         const double ut_old = U[2 * k + 1];
         if (fabs(ut_old) > vb) {
             const double sgn = ut_old > 0.0 ? 1.0 : -1.0;
             U[2 * k + 1] = sgn * vb;
             U[2 * k] = U[2 * k + 1] * U[2 * k] / ut_old;
         }
-        dyn d;
-        dynamics(sh, xc[2], xc[3], U[2 * k], U[2 * k + 1], &d, 0);
-        for (int c = 0; c < 4; ++c) xc[c] = qfma(p->Ts, d.f[c], xc[c]);
+        euler_step(*sh, p->Ts, xc, U[2 * k], U[2 * k + 1]);
     }
     double PIin[TW_MAX_N * 4];
     memcpy(PIin, PIw, sizeof(double) * 4 * N);
@@ -1872,7 +1315,7 @@ int tw_controller_solve(const int32_t *n_ctrl, const double *ctrl, const double 
         tw_ws *w = (tw_ws *)malloc(sizeof(tw_ws));
         #pragma omp for schedule(dynamic, 1)
         for (int32_t i = 0; i < nb; ++i) {
-            tw_shape sh;
+            ShapeDev sh;
             make_shape(&sh, n_ctrl, ctrl, knots, params, max_ctrl, shape_id[i], 0.0);
             tw_out out;
             status[i] = ctrl_lane(&p, &sh, w, x0_in + 4 * i, traj + (traj_per_lane ? (size_t)i * T * 6 : 0), T,
@@ -1890,20 +1333,20 @@ int tw_controller_solve(const int32_t *n_ctrl, const double *ctrl, const double 
 }
 
 /* contact re-projection (reproject_contact / contact_phi) */
-static double contact_phi(const tw_shape *sh, double s, double px, double py)
+static double contact_phi(const ShapeDev *sh, double s, double px, double py)
 {
-    spl e;
-    spline_eval(sh, mat_mod(s, sh->b), &e);
+    SplineEval e;
+    spline_eval(*sh, mat_mod(s, sh->b), e);
     const double ex = e.C[0] - px, ey = e.C[1] - py;
     return qfma(ey, ey, ex * ex);
 }
 
-static double reproject_contact(const tw_shape *sh, double px, double py, double s0)
+static double reproject_contact(const ShapeDev *sh, double px, double py, double s0)
 {
     double s = s0, phi = contact_phi(sh, s, px, py);
     for (int it = 0; it < 60; ++it) {
-        spl e;
-        spline_eval(sh, mat_mod(s, sh->b), &e);
+        SplineEval e;
+        spline_eval(*sh, mat_mod(s, sh->b), e);
         const double ex = e.C[0] - px, ey = e.C[1] - py;
         const double g = 2.0 * qfma(ey, e.D[1], ex * e.D[0]);
         const double h = 2.0 * qfma(ey, e.Dd[1], qfma(ex, e.Dd[0], qfma(e.D[1], e.D[1], e.D[0] * e.D[0])));
@@ -1932,7 +1375,7 @@ int tw_reproject_contact(const int32_t *n_ctrl, const double *ctrl, const double
                          const double *s0, double *s)
 {
     for (int32_t i = 0; i < n; ++i) {
-        tw_shape sh;
+        ShapeDev sh;
         make_shape(&sh, n_ctrl, ctrl, knots, params, max_ctrl, shape_id[i], 0.0);
         s[i] = reproject_contact(&sh, px[i], py[i], s0[i]);
     }
@@ -1966,7 +1409,7 @@ int tw_closed_loop(const int32_t *n_ctrl, const double *ctrl, const double *knot
         double *ubp = (double *)calloc(2 * (size_t)(plant_delay_cols + 1), sizeof(double));
         #pragma omp for schedule(dynamic, 1)
         for (int32_t i = 0; i < nb; ++i) {
-            tw_shape sh;
+            ShapeDev sh;
             make_shape(&sh, n_ctrl, ctrl, knots, params, max_ctrl, shape_id[i], xwidth ? xwidth[shape_id[i]] : 0.0);
             uint8_t valid = 0;
             memset(Xw, 0, sizeof(double) * 4 * (N + 1));
@@ -1982,8 +1425,8 @@ int tw_closed_loop(const int32_t *n_ctrl, const double *ctrl, const double *knot
                 if (dist_step > 0 && t + 1 == dist_step) {
                     const double amp = dist_amp ? dist_amp[i] : 0.0;
                     x[1] += amp;
-                    spl e;
-                    spline_eval(&sh, mat_mod(x[3], sh.b), &e);
+                    SplineEval e;
+                    spline_eval(sh, mat_mod(x[3], sh.b), e);
                     const double sn = reproject_contact(&sh, -0.5 * sh.xwidth, e.C[1] - amp, 0.0);
                     x[3] = qfma(-sh.b, sn < 0.0 ? 1.0 : 0.0, mat_mod(sn, sh.b));
                 }
@@ -1994,9 +1437,7 @@ int tw_closed_loop(const int32_t *n_ctrl, const double *ctrl, const double *knot
                 memcpy(xs, x, sizeof xs);
                 for (int k = 1; k <= delay_cols; ++k) {
                     const double *u = ubc + 2 * (delay_cols - k);
-                    dyn d;
-                    dynamics(&sh, xs[2], xs[3], u[0], u[1], &d, 0);
-                    for (int c = 0; c < 4; ++c) xs[c] = qfma(p.Ts, d.f[c], xs[c]);
+                    euler_step(sh, p.Ts, xs, u[0], u[1]);
                 }
                 if (Xsim) memcpy(Xsim + ((size_t)i * n_steps + t) * 4, xs, sizeof xs);
                 double u[2];
@@ -2017,9 +1458,7 @@ int tw_closed_loop(const int32_t *n_ctrl, const double *ctrl, const double *knot
                     ubp[0] = u[0];
                     ubp[1] = u[1];
                 }
-                dyn d;
-                dynamics(&sh, x[2], x[3], ua[0], ua[1], &d, 0);
-                for (int c = 0; c < 4; ++c) x[c] = qfma(p.Ts, d.f[c], x[c]);
+                euler_step(sh, p.Ts, x, ua[0], ua[1]);
                 memcpy(Utraj + ((size_t)i * n_steps + t) * 2, u, sizeof u);
                 if (Straj) Straj[(size_t)i * n_steps + t] = st;
                 if (g_kkt_diag && st == 2) {
@@ -2042,3 +1481,5 @@ int tw_closed_loop(const int32_t *n_ctrl, const double *ctrl, const double *knot
     }
     return 0;
 }
+
+}   /* extern "C" */

@@ -98,7 +98,7 @@ int main(int argc, char** argv) {
             switch (op) {
                 case OP_SQRT: h1 = sqrt(a[i]); break;
                 case OP_DIV: h1 = a[i] / b[i]; break;
-                case OP_RCP: h1 = qsp::rcp_host(a[i]); break;
+                case OP_RCP: h1 = qsp::rcp(a[i]); break;
                 case OP_FMOD: h1 = fmod(a[i], b[i]); break;
                 case OP_FLOOR: h1 = floor(a[i] / b[i]); break;
                 case OP_FMA: h1 = fma(a[i], b[i], c[i]); break;

@@ -43,7 +43,7 @@ int main() {
     long bad = 0, badneg = 0, badw = 0, badw_normal = 0, bycls[3] = {0, 0, 0};
     long byexp[64] = {0}, cnt[64] = {0};
     for (int i = 0; i < n; ++i) {
-        const double h = qsp::rcp_host(x[i]);
+        const double h = qsp::rcp(x[i]);
         int e = 0;
         frexp(x[i], &e);
         const int bucket = (e + 1024) / 32;

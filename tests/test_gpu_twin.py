@@ -1,9 +1,10 @@
-"""Bit-exact GPU parity: the HIP library against the oracle's kernel-order twin (oracle/qsp_twin.c).
+"""Bit-exact GPU parity: the HIP library against the oracle's kernel-order twin (oracle/qsp_twin.cpp).
 
 The library is built with -ffp-contract=off and writes every fused multiply-add out; the twin
-restates the same reference path (PusherSliderModel.m:503-603, bspline_shape.m:40-152, the acados
+runs the same reference path (PusherSliderModel.m:503-603, bspline_shape.m:40-152, the acados
 SQP/HPIPM algorithms of NMPC_controller.m:270-300, the solve wrapper :329-423, helper.m:195-322)
-in the same formulation and operation order on the CPU.  Every operation involved is IEEE-exact
+on the CPU: the library's own lane arithmetic compiled for the host, inside a sequential
+restatement of the kernels' orchestration.  Every operation involved is IEEE-exact
 on both sides (scripts/ubench/fp_exact.hip), so the expected result is equality of every bit, on
 every lane -- including the lanes where the fixed-K full-step SQP is chaotic, where
 any rounding-level difference would show.  Tolerance: none (np.array_equal, NaN == NaN).

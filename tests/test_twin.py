@@ -1,4 +1,4 @@
-"""CPU: the oracle's kernel-order twin (oracle/qsp_twin.c) against the literal restatement
+"""CPU: the oracle's kernel-order twin (oracle/qsp_twin.cpp) against the literal restatement
 (oracle/qsp_oracle.c) and the committed fixtures.
 
 The twin is what the GPU is compared with bit for bit (tests/test_gpu_twin.py); these tests pin
@@ -69,7 +69,7 @@ def test_building_blocks_match_literal(oracle, twin):
 
 
 def test_sincos_against_libm(twin):
-    """The library's own sin/cos (qsp_fp.hpp, restated in the twin): within one ulp of libm on the
+    """The library's own sin/cos (qsp_fp.hpp, compiled into the twin): within one ulp of libm on the
     model's angle range -- seen through f, whose theta dependence is R(theta) G."""
     x = np.zeros((2000, 4))
     x[:, 2] = np.linspace(-20.0, 20.0, 2000)

@@ -1,47 +1,56 @@
 // qsp_fp.hpp — FP64 primitives whose bits the CPU oracle reproduces.
 //
 // The library is compiled with -ffp-contract=off: every fused multiply-add in the solve is an
-// explicit fma() (qfma below), so the oracle's kernel-order restatement performs the same IEEE
-// operations in the same order and reproduces the device results bit for bit.  The operations
-// used are those gfx950 rounds exactly as the host does (+ - * / sqrt fma, fmod, floor, rint;
-// scripts/ubench/fp_exact.hip checks them), plus the two below:
+// explicit fma() (qfma below), so the oracle's kernel-order twin, which compiles this header for
+// the host, performs the same IEEE operations in the same order and reproduces the device results
+// bit for bit.  The operations used are those gfx950 rounds exactly as the host does (+ - * / sqrt
+// fma, fmod, floor, rint; scripts/ubench/fp_exact.hip checks them), plus the two below:
 //   rcp     1/x from the hardware reciprocal refined by two Newton steps.  From any start
 //           within 2^-27 the second step lands on the correctly rounded 1/x (barring a
-//           2^-90-close tie), so the oracle writes it as the same two steps from 1.0 / x.
+//           2^-90-close tie), so the host evaluates it as the same two steps from 1.0 / x.
 //   sin_cos sin and cos by fdlibm's Cody–Waite reduction (two stages, 118 bits of pi/2) and
 //           the fdlibm/musl kernel polynomials, written out here so that both sides evaluate
 //           the same sequence (ocml's and glibc's sin differ in the last bit).  Accurate to
 //           about one ulp for |x| < 2^20 pi/2; beyond that the reduction degrades (the model's
 //           theta stays within a few radians).
+//
+// This header, qsp_math.hpp and qsp_riccati.hpp are the one statement of the lane-local arithmetic:
+// straight-line functions that read no other lane.  hipcc compiles them into the kernels; a plain
+// C++ compiler (no ROCm include path) compiles them into the CPU twin, oracle/qsp_twin.cpp (test
+// infrastructure may read a product header; the product never reads the twin).  Their qualifiers:
+//   QSP_FN         a device function;           QSP_HD_FN  one the host code of the library calls too;
+//   QSP_MEMBER_FN  a device member function -- on the host all three are plain inline functions.
 #pragma once
+#ifdef __HIPCC__
 #include <hip/hip_runtime.h>
+#define QSP_FN __device__ __forceinline__
+#define QSP_HD_FN __host__ __device__ __forceinline__
+#define QSP_MEMBER_FN __device__ __forceinline__
+#else
+#include <math.h>
+#define QSP_FN static inline
+#define QSP_HD_FN static inline
+#define QSP_MEMBER_FN inline
+#endif
 
 namespace qsp {
 
 // explicit fused multiply-add: a * b + c with one rounding
-__host__ __device__ __forceinline__ double qfma(double a, double b, double c) { return __builtin_fma(a, b, c); }
+QSP_HD_FN double qfma(double a, double b, double c) { return __builtin_fma(a, b, c); }
 
-__device__ __forceinline__ double rcp(double x) {
+QSP_HD_FN double rcp(double x) {
 #if defined(__HIP_DEVICE_COMPILE__)
     double r = __builtin_amdgcn_rcp(x);
 #else
-    double r = 1.0 / x;   // host pass of device code (never run)
+    double r = 1.0 / x;   // the host: the CPU twin and the developer tools (scripts/ubench/rcp_check.hip, fp_exact.hip)
 #endif
     double e = __builtin_fma(-x, r, 1.0);
     r = __builtin_fma(r, e, r);
     e = __builtin_fma(-x, r, 1.0);
     return __builtin_fma(r, e, r);
 }
-// the host counterpart (developer tools; the oracle restates it in C)
-inline double rcp_host(double x) {
-    double r = 1.0 / x;
-    double e = __builtin_fma(-x, r, 1.0);
-    r = __builtin_fma(r, e, r);
-    e = __builtin_fma(-x, r, 1.0);
-    return __builtin_fma(r, e, r);
-}
 
-__host__ __device__ __forceinline__ void sin_cos(double x, double* sp, double* cp) {
+QSP_HD_FN void sin_cos(double x, double* sp, double* cp) {
     // x = n pi/2 + (y + yy), |y| <= pi/4 (fdlibm __ieee754_rem_pio2, medium case, two stages)
     const double invpio2 = 6.36619772367581382433e-01;
     const double pio2_1 = 1.57079632673412561417e+00;    // first 33 bits of pi/2

@@ -2,7 +2,9 @@
  * how many stages a lane holds, the LDS fields of a lane, and which horizons factorise on the
  * matrix cores.  Plain integer arithmetic that compiles as C99 and as HIP C++ (host and device):
  * qsp_solver.hip and qsp_capi.hip include it, and so does the CPU twin that checks the kernels bit
- * for bit (test infrastructure may read this product header; the product never reads the twin). */
+ * for bit (test infrastructure may read a product header; the product never reads the twin).  The
+ * twin reads three more on the same terms, C++ only: qsp_fp.hpp, qsp_math.hpp and qsp_riccati.hpp,
+ * the lane-local arithmetic. */
 #ifndef QSP_LAYOUT_H
 #define QSP_LAYOUT_H
 

@@ -7,10 +7,10 @@
 //   dynamics f(x,u)                     : acados_nmpc/PusherSliderModel.m:503-603
 //   ERK integrator (RK4, 1 step)        : acados sim_method "erk" (NMPC_controller.m:272)
 // Every fused multiply-add is written out (qfma; the library is built with
-// -ffp-contract=off): the oracle's kernel-order twin (oracle/qsp_twin.c) evaluates the same
-// operations in the same order and reproduces these results bit for bit.
+// -ffp-contract=off): the oracle's kernel-order twin (oracle/qsp_twin.cpp) compiles this header for
+// the host and so evaluates the same operations in the same order, and reproduces these results bit
+// for bit (the qualifier macros and the runtime / <math.h> include: qsp_fp.hpp).
 #pragma once
-#include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "qsp_fp.hpp"
@@ -30,7 +30,7 @@ struct SplineEval {
     double Dd[2];   // d FC_dot / d sigma
 };
 
-__device__ __forceinline__ void spline_eval(const ShapeDev& sh, double sig, SplineEval& o) {
+QSP_FN void spline_eval(const ShapeDev& sh, double sig, SplineEval& o) {
     const int n = sh.n;
     const double* S = sh.knots;
     const bool inside = (sig >= S[3]) && (sig < S[n]);
@@ -88,28 +88,28 @@ __device__ __forceinline__ void spline_eval(const ShapeDev& sh, double sig, Spli
 }
 
 // s_mod inside the OCP model: fmod(s,b) + (s<0)*b   (PusherSliderModel.m:526)
-__device__ __forceinline__ double smod_model(double s, double b) {
+QSP_FN double smod_model(double s, double b) {
     return fmod(s, b) + ((s < 0.0) ? b : 0.0);
 }
 
 // MATLAB floor-mod  mod(a,b) = a - floor(a/b)*b   (NMPC_controller.m:320,332)
-__device__ __forceinline__ double mat_mod(double a, double b) {
+QSP_FN double mat_mod(double a, double b) {
     const double r = qfma(-floor(a / b), b, a);
     return (r == b) ? 0.0 : r;
 }
 
 // tangent-angle rate kappa = d/ds atan2(C'_y, C'_x)  (bspline_shape.m:137-144)
-__device__ __forceinline__ double angle_rate_of(const SplineEval& e) {
+QSP_FN double angle_rate_of(const SplineEval& e) {
     return qfma(e.D[0], e.Dd[1], -(e.D[1] * e.Dd[0])) / qfma(e.D[0], e.D[0], e.D[1] * e.D[1]);
 }
-__device__ __forceinline__ double angle_rate(const ShapeDev& sh, double sig) {
+QSP_FN double angle_rate(const ShapeDev& sh, double sig) {
     SplineEval e;
     spline_eval(sh, sig, e);
     return angle_rate_of(e);
 }
 
 // tangential velocity bound v_bound(s)  (NMPC_controller.m:319-327)
-__device__ __forceinline__ double v_bound(const ShapeDev& sh, const CtrlParams& cp, double s) {
+QSP_FN double v_bound(const ShapeDev& sh, const CtrlParams& cp, double s) {
     const double sm = mat_mod(s, sh.b);
     const double ta = fabs(angle_rate(sh, sm));
     const double v = cp.v_alpha / (fabs(ta - cp.t_angle0) + 0.0001) + cp.d_v;
@@ -128,7 +128,7 @@ struct DynOut {
 };
 
 // indicator blend i_st * a + i_sl * b + i_sr * c (PusherSliderModel.m:587-589)
-__device__ __forceinline__ double blend3(double ist, double a, double isl, double b, double isr, double c) {
+QSP_FN double blend3(double ist, double a, double isl, double b, double isr, double c) {
     return qfma(isr, c, qfma(isl, b, ist * a));
 }
 
@@ -140,18 +140,18 @@ __device__ __forceinline__ double blend3(double ist, double a, double isl, doubl
 // that calls it (a value or a const double& argument moved or retyped the loads and reordered the
 // schedule of the rollout and open-loop kernels); LaneCM holds a lane's values.
 struct ShapeCM {
-    __device__ __forceinline__ double c(const ShapeDev& sh) const { return sh.c; }
-    __device__ __forceinline__ double mu(const ShapeDev& sh) const { return sh.mu; }
+    QSP_MEMBER_FN double c(const ShapeDev& sh) const { return sh.c; }
+    QSP_MEMBER_FN double mu(const ShapeDev& sh) const { return sh.mu; }
 };
 struct LaneCM {
     double c_, mu_;
-    __device__ __forceinline__ double c(const ShapeDev&) const { return c_; }
-    __device__ __forceinline__ double mu(const ShapeDev&) const { return mu_; }
+    QSP_MEMBER_FN double c(const ShapeDev&) const { return c_; }
+    QSP_MEMBER_FN double mu(const ShapeDev&) const { return mu_; }
 };
 
 template <bool WITH_JAC, class CM>
-__device__ __forceinline__ void dynamics_cm(const ShapeDev& sh, const CM& cm, double th, double s, double un, double ut,
-                                            DynOut& o) {
+QSP_FN void dynamics_cm(const ShapeDev& sh, const CM& cm, double th, double s, double un, double ut,
+                        DynOut& o) {
     const double sig = smod_model(s, sh.b);
     SplineEval e;
     spline_eval(sh, sig, e);
@@ -257,7 +257,7 @@ __device__ __forceinline__ void dynamics_cm(const ShapeDev& sh, const CM& cm, do
 }
 
 template <bool WITH_JAC>
-__device__ __forceinline__ void dynamics(const ShapeDev& sh, double th, double s, double un, double ut, DynOut& o) {
+QSP_FN void dynamics(const ShapeDev& sh, double th, double s, double un, double ut, DynOut& o) {
     dynamics_cm<WITH_JAC>(sh, ShapeCM{}, th, s, un, ut, o);
 }
 
@@ -265,14 +265,14 @@ __device__ __forceinline__ void dynamics(const ShapeDev& sh, double th, double s
 // :357-380): the one step of the prologue's rollout, the closed loop's plant and delay prediction,
 // the rollout costs and the open-loop simulation, whose chains therefore agree bit for bit.
 template <class CM>
-__device__ __forceinline__ void euler_step_cm(const ShapeDev& sh, const CM& cm, double Ts, double x[4], double un, double ut) {
+QSP_FN void euler_step_cm(const ShapeDev& sh, const CM& cm, double Ts, double x[4], double un, double ut) {
     DynOut d;
     dynamics_cm<false>(sh, cm, x[2], x[3], un, ut, d);
 #pragma unroll
     for (int c = 0; c < 4; ++c) x[c] = qfma(Ts, d.f[c], x[c]);
 }
 
-__device__ __forceinline__ void euler_step(const ShapeDev& sh, double Ts, double x[4], double un, double ut) {
+QSP_FN void euler_step(const ShapeDev& sh, double Ts, double x[4], double un, double ut) {
     euler_step_cm(sh, ShapeCM{}, Ts, x, un, ut);
 }
 
@@ -300,7 +300,7 @@ struct MotionCone {
 
 // motion_cone_cm: the core with the source of c and mu as an argument (dynamics_cm's counterpart)
 template <class CM>
-__device__ __forceinline__ MotionCone motion_cone_cm(const ShapeDev& sh, const CM& cm, double s, double un, double ut) {
+QSP_FN MotionCone motion_cone_cm(const ShapeDev& sh, const CM& cm, double s, double un, double ut) {
     const double sig = smod_model(s, sh.b);
     SplineEval e;
     spline_eval(sh, sig, e);
@@ -332,7 +332,7 @@ __device__ __forceinline__ MotionCone motion_cone_cm(const ShapeDev& sh, const C
     return o;
 }
 
-__device__ __forceinline__ MotionCone motion_cone(const ShapeDev& sh, double s, double un, double ut) {
+QSP_FN MotionCone motion_cone(const ShapeDev& sh, double s, double un, double ut) {
     return motion_cone_cm(sh, ShapeCM{}, s, un, ut);
 }
 
@@ -348,7 +348,7 @@ struct Lin {
 };
 
 template <bool WITH_SENS>
-__device__ __forceinline__ void rk4(const ShapeDev& sh, double h, const double x[4], const double u[2], Lin& o) {
+QSP_FN void rk4(const ShapeDev& sh, double h, const double x[4], const double u[2], Lin& o) {
     const double ca[4] = {0.0, 0.5, 0.5, 1.0};
     const double cb[4] = {1.0 / 6.0, 1.0 / 3.0, 1.0 / 3.0, 1.0 / 6.0};
     double acc[4] = {x[0], x[1], x[2], x[3]};

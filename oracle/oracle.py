@@ -7,7 +7,7 @@ Two restatements of the reference path share one interface:
   Oracle(...)            the literal restatement (qsp_oracle.c: full basis sum, forward AD,
                          a dense Riccati interior point) -- pins the formulas;
   Oracle(..., twin=True) the kernel-order twin (qsp_twin.cpp: the device library's own lane
-                         arithmetic, csrc/qsp_{fp,math,riccati}.hpp, inside a sequential restatement
+                         arithmetic, csrc/qsp_{fp,math,riccati,ipm}.hpp, inside a sequential restatement
                          of the kernels' orchestration) -- reproduces the device bit for bit.
 """
 import ctypes as C

@@ -15,14 +15,20 @@
  * formulation and operation order.
  *
  * Division of labour.  The lane-local arithmetic -- qfma, rcp, sin_cos, the span-based
- * de Boor, the dynamics with its hand-derived Jacobian, RK4, the structured Riccati step, the scans'
- * maps and elements, the adjoint and merit stage terms -- is NOT restated here: this file compiles
- * the kernels' own headers (csrc/qsp_fp.hpp, qsp_math.hpp, qsp_riccati.hpp) for the host, with
+ * de Boor, the dynamics with its hand-derived Jacobian, RK4, the contact re-projection, the structured
+ * Riccati step, the scans' maps and elements, the adjoint and merit stage terms, the IPM's barrier
+ * terms, directions, step and exit test, the merit SQP's KKT residuals and updates, the controller's
+ * guess roll-out -- is NOT restated here: this file compiles the kernels' own headers
+ * (csrc/qsp_fp.hpp, qsp_math.hpp, qsp_riccati.hpp, qsp_ipm.hpp) for the host, with
  * -ffp-contract=off as the library.  What it restates, as plain sequential loops, is the
  * ORCHESTRATION the device runs in DPP moves, LDS records and matrix-core instructions: which lane
  * walks when, the lane-group reductions' summation tree, the scans' levels, the matrix-core
- * product's element order, the barrier and step-length terms tied to the kernels' LDS stage, the
- * IPM and SQP loops, the controller wrapper and the closed loop.  The operations are IEEE-exact on
+ * product's element order, the IPM and SQP loops, the controller wrapper and the closed loop.
+ * Still written out here as in the kernels, each for a measured reason (profiles/ipm_shared/README.md
+ * section B): qp_ipm's t.lm sum and centring scalar and load_stage (as shared functions they cost the
+ * SQP kernels registers), qp_ipm's start point (registers equal, but 0.4 % slower on the headline
+ * workload), merit_ls's directional-derivative term and epilogue_cost (their kernels' instruction
+ * counts move by more than 1 %).  The operations are IEEE-exact on
  * both sides (checked on the device by scripts/ubench/fp_exact.hip), so this twin reproduces the
  * library's results BIT FOR BIT, lane by lane, including lanes where the fixed-K SQP is chaotic:
  * the comparison proves that the GPU's compiler and hardware evaluate the shared source as x86 does
@@ -43,7 +49,8 @@
 #include "qsp_nmpc.h"      /* QSP_WALK_* (tw_factor_walk) */
 #include "qsp_layout.h"    /* the library's own layout rules: stages per lane, lanes per instance, mfw_fits */
 #include "qsp_math.hpp"    /* the library's own lane arithmetic: qsp_fp.hpp, the model ... */
-#include "qsp_riccati.hpp" /* ... and the QP's per-lane steps */
+#include "qsp_riccati.hpp" /* ... the QP's per-lane steps ... */
+#include "qsp_ipm.hpp"     /* ... and the per-stage arithmetic of the interior point and the SQP */
 
 using namespace qsp;
 
@@ -86,6 +93,19 @@ typedef struct {
     double VA[3], VN[3], du[2], dxs[4];
     double at[6], al[6], dt[6], dl[6];
 } tw_stage;
+
+/* one slot as the view qsp_ipm.hpp's functions take (the kernels': Stage<S>, with the slot number ls) */
+struct tw_view {
+    tw_stage *s;
+    double &t(int, int q) const { return s->t[q]; }
+    double &lm(int, int q) const { return s->lm[q]; }
+    double &rt(int, int q) const { return s->rt[q]; }
+    double &v(int, int j) const { return s->v[j]; }
+    double &va(int, int j) const { return s->VA[j]; }
+    double &vn(int, int j) const { return s->VN[j]; }
+    double &hg(int, int i) const { return s->hg[i]; }
+    double &du(int, int i) const { return s->du[i]; }
+};
 
 /* the solve parameters the kernels read, plus the layout they imply.  mfma_walk is the twin's own
  * decision here (mfw_on / mfw_is, the kernels' record layout, stay unset) */
@@ -156,119 +176,6 @@ static double group_max(const double *v, int L)
     double r = v[L - 1];
     for (int i = L - 2; i >= 0; --i) r = (v[i] > r) ? v[i] : r;
     return r;
-}
-
-static inline int bnd_act(const tw_par *p, int k, int j) { return (k < p->N) && (j > 0 || k >= 1 || p->s0_bound != 0); }
-
-static inline void bnd_lohi(const tw_par *p, const tw_stage *s, double lo[3], double hi[3])
-{
-    for (int j = 0; j < 3; ++j) { lo[j] = p->lh[j] - s->v[j]; hi[j] = p->uh[j] - s->v[j]; }
-}
-
-/* barrier_terms */
-static void barrier_terms(const tw_par *p, tw_stage *s, int k)
-{
-    double lo[3], hi[3];
-    bnd_lohi(p, s, lo, hi);
-    for (int j = 0; j < 3; ++j) {
-        const int act = bnd_act(p, k, j);
-        const double ll = s->lm[2 * j], lh = s->lm[2 * j + 1];
-        const double sl = ll * s->rt[2 * j], sh = lh * s->rt[2 * j + 1];
-        const double gadd = qfma(-sh, hi[j], -sl * lo[j]) + (lh - ll);
-        s->hg[j] = act ? sl + sh : 0.0;
-        s->hg[3 + j] = act ? gadd : 0.0;
-    }
-}
-
-#define RATIO(tv, dv) do { if ((dv) < 0.0 && (tv) * den < num * -(dv)) { num = (tv); den = -(dv); } } while (0)
-
-/* affine_dirs: directions kept in at / al, ratio folded into num/den of the lane */
-static void affine_dirs(const tw_par *p, tw_stage *s, int k, double *pnum, double *pden)
-{
-    double num = *pnum, den = *pden;
-    double lo[3], hi[3];
-    bnd_lohi(p, s, lo, hi);
-    for (int j = 0; j < 3; ++j) {
-        const int act = bnd_act(p, k, j);
-        const double tl = s->t[2 * j], th = s->t[2 * j + 1];
-        const double ll = s->lm[2 * j], lh = s->lm[2 * j + 1];
-        const double sl = ll * s->rt[2 * j], sh = lh * s->rt[2 * j + 1];
-        const double v = s->VA[j];
-        s->at[2 * j] = v - lo[j] - tl;
-        s->at[2 * j + 1] = hi[j] - v - th;
-        s->al[2 * j] = qfma(-sl, s->at[2 * j], -ll);
-        s->al[2 * j + 1] = qfma(-sh, s->at[2 * j + 1], -lh);
-        const double dtl = act ? s->at[2 * j] : 0.0, dth = act ? s->at[2 * j + 1] : 0.0;
-        const double dll = act ? s->al[2 * j] : 0.0, dlh = act ? s->al[2 * j + 1] : 0.0;
-        RATIO(tl, dtl);
-        RATIO(th, dth);
-        RATIO(ll, dll);
-        RATIO(lh, dlh);
-    }
-    *pnum = num;
-    *pden = den;
-}
-
-static double affine_mu_part(const tw_par *p, const tw_stage *s, int k, double aa, double part)
-{
-    for (int j = 0; j < 3; ++j) {
-        const int act = bnd_act(p, k, j);
-        const double tl = s->t[2 * j], th = s->t[2 * j + 1];
-        const double ll = s->lm[2 * j], lh = s->lm[2 * j + 1];
-        const double dtl = act ? s->at[2 * j] : 0.0, dth = act ? s->at[2 * j + 1] : 0.0;
-        const double dll = act ? s->al[2 * j] : 0.0, dlh = act ? s->al[2 * j + 1] : 0.0;
-        part = qfma(qfma(aa, dtl, tl), qfma(aa, dll, ll), part);
-        part = qfma(qfma(aa, dth, th), qfma(aa, dlh, lh), part);
-    }
-    return part;
-}
-
-static void corrector_terms(const tw_par *p, tw_stage *s, int k, double smu)
-{
-    for (int j = 0; j < 3; ++j) {
-        const int act = bnd_act(p, k, j);
-        const double cl = qfma(-s->at[2 * j], s->al[2 * j], smu), ch = qfma(-s->at[2 * j + 1], s->al[2 * j + 1], smu);
-        s->hg[3 + j] = act ? qfma(ch, s->rt[2 * j + 1], -(cl * s->rt[2 * j])) : 0.0;
-    }
-}
-
-static void corrector_dirs(const tw_par *p, tw_stage *s, int k, double smu, double *pnum, double *pden)
-{
-    double num = *pnum, den = *pden;
-    double lo[3], hi[3];
-    bnd_lohi(p, s, lo, hi);
-    for (int j = 0; j < 3; ++j) {
-        const int act = bnd_act(p, k, j);
-        const double tl = s->t[2 * j], th = s->t[2 * j + 1];
-        const double ll = s->lm[2 * j], lh = s->lm[2 * j + 1];
-        const double rtl = s->rt[2 * j], rth = s->rt[2 * j + 1];
-        const double sl = ll * rtl, sh = lh * rth;
-        const double v = s->VN[j];
-        double dtl = v - lo[j] - tl, dth = hi[j] - v - th;
-        double dll = qfma(-sl, dtl, -ll), dlh = qfma(-sh, dth, -lh);
-        dll = qfma(qfma(-s->at[2 * j], s->al[2 * j], smu), rtl, dll);
-        dlh = qfma(qfma(-s->at[2 * j + 1], s->al[2 * j + 1], smu), rth, dlh);
-        dtl = act ? dtl : 0.0; dth = act ? dth : 0.0;
-        dll = act ? dll : 0.0; dlh = act ? dlh : 0.0;
-        RATIO(tl, dtl);
-        RATIO(th, dth);
-        RATIO(ll, dll);
-        RATIO(lh, dlh);
-        s->dt[2 * j] = dtl; s->dt[2 * j + 1] = dth;
-        s->dl[2 * j] = dll; s->dl[2 * j + 1] = dlh;
-    }
-    *pnum = num;
-    *pden = den;
-}
-
-static void apply_step(tw_stage *s, double alpha)
-{
-    for (int q = 0; q < 6; ++q) {
-        const double tn = qfma(alpha, s->dt[q], s->t[q]);
-        s->t[q] = tn;
-        s->rt[q] = rcp(tn);
-        s->lm[q] = qfma(alpha, s->dl[q], s->lm[q]);
-    }
 }
 
 /* ---- S = 2: the affine passes as scans (riccati_solve<2, ...>; Aff, aff_*: qsp_riccati.hpp) */
@@ -618,21 +525,21 @@ static void riccati_solve(const tw_par *p, tw_stage *st, const double dx0[4], in
     forward_scan_s2(p, st, dx0, factor);
 }
 
-enum { QP_EXIT_CONV = 0, QP_EXIT_CAP = 1, QP_EXIT_STALL = 2, QP_EXIT_DIVERGED = 3 };
-
 /* qp_ipm: slots 0 .. L*S-1 of st are filled (a, B, bb, g, v; padding slots past N hold the terminal
  * stage's data as the kernel loads them).  Returns the iterations taken; *exit why it stopped. */
 static int qp_ipm(const tw_par *p, tw_stage *st, const double dx0[4], int *exit, int skip)
 {
     const int N = p->N, S = p->S, L = p->L;
     const double m = 2.0 * (3.0 * N - (p->s0_bound ? 0.0 : 1.0));
+    /* the start point and its residuals: written out here as in the kernel's qp_ipm (as one shared
+     * function it cost the headline workload 0.4 %, profiles/ipm_shared/README.md): edit both */
     double r0 = 0.0, rg0 = 0.0, rb0 = 0.0;
     for (int k = 0; k < L * S; ++k) {
         tw_stage *s = st + k;
         double lo[3], hi[3], gl[3];
-        bnd_lohi(p, s, lo, hi);
+        bnd_lohi(*p, tw_view{s}, 0, lo, hi);
         for (int j = 0; j < 3; ++j) {
-            const int act = bnd_act(p, k, j);
+            const int act = bnd_act(*p, N, k, j);
             const double tl = fmax(-lo[j], p->t_min), th = fmax(hi[j], p->t_min);
             if (act) r0 = fmax(r0, fmax(tl + lo[j], th - hi[j]));
             const double rl = rcp(tl), rh = rcp(th);
@@ -658,35 +565,35 @@ static int qp_ipm(const tw_par *p, tw_stage *st, const double dx0[4], int *exit,
     rs_stop = rs_g < rs_stop ? rs_g : rs_stop;
     rs_stop = rs_b < rs_stop ? rs_b : rs_stop;
     double rscale = 1.0;
-    int nit = 0, stall = 0, conv = 0, stalled = 0, div = 0;
+    int nit = 0, stall = 0;
+    bool conv = false, stalled = false, div = false;
     double lane[64], num[64], den[64];
     for (int it = 0;; ++it) {
         for (int l = 0; l < L; ++l) {
-            double acc = 0.0;
+            double acc = 0.0;   /* the lane's t.lm sum, as the kernel's loop-top tl_sum */
             for (int ls = 0; ls < S; ++ls)
                 for (int q = 0; q < 6; ++q) acc = qfma(st[l * S + ls].t[q], st[l * S + ls].lm[q], acc);
             lane[l] = acc;
         }
         const double mu = group_sum(lane, L) / m;
-        div = !skip && !(mu < p->qp_mu_max);
-        conv = !div && (skip || (!(mu >= p->mu_stop) && !(rscale >= rs_stop)));
-        stalled = !conv && !div && p->qp_stall_iters > 0 && stall >= p->qp_stall_iters;
+        ipm_exit_test(*p, mu, rscale, rs_stop, stall, skip != 0, div, conv, stalled);
         const int done = conv || div || stalled;
         if (it == p->qp_iters || done) break;
         nit++;
         /* predictor */
-        for (int k = 0; k < L * S; ++k) barrier_terms(p, st + k, k);
+        for (int k = 0; k < L * S; ++k)
+            for (int j = 0; j < 3; ++j) barrier_term(*p, N, tw_view{st + k}, 0, k, j, st[k].hg);
         riccati_solve(p, st, dx0, 1);
         for (int l = 0; l < L; ++l) {
             num[l] = 1.0;
             den[l] = 1.0;
-            for (int ls = 0; ls < S; ++ls) affine_dirs(p, st + l * S + ls, l * S + ls, num + l, den + l);
+            for (int k = l * S; k < l * S + S; ++k) affine_dirs(*p, N, tw_view{st + k}, 0, k, st[k].at, st[k].al, num[l], den[l]);
             lane[l] = num[l] / den[l];
         }
         const double aa = group_min(lane, L);
         for (int l = 0; l < L; ++l) {
             double ma = 0.0;
-            for (int ls = 0; ls < S; ++ls) ma = affine_mu_part(p, st + l * S + ls, l * S + ls, aa, ma);
+            for (int k = l * S; k < l * S + S; ++k) ma = affine_mu_part(*p, N, tw_view{st + k}, 0, k, st[k].at, st[k].al, aa, ma);
             lane[l] = ma;
         }
         const double mua = group_sum(lane, L) / m;
@@ -694,12 +601,13 @@ static int qp_ipm(const tw_par *p, tw_stage *st, const double dx0[4], int *exit,
         const double sg = fmax(r * r * r, p->sigma_min);
         const double smu = sg * mu;
         /* corrector */
-        for (int k = 0; k < L * S; ++k) corrector_terms(p, st + k, k, smu);
+        for (int k = 0; k < L * S; ++k) corrector_terms(*p, N, tw_view{st + k}, 0, k, st[k].at, st[k].al, smu);
         riccati_solve(p, st, dx0, 0);
         for (int l = 0; l < L; ++l) {
             num[l] = 1.0;
             den[l] = p->frac;
-            for (int ls = 0; ls < S; ++ls) corrector_dirs(p, st + l * S + ls, l * S + ls, smu, num + l, den + l);
+            for (int k = l * S; k < l * S + S; ++k)
+                corrector_dirs(*p, N, tw_view{st + k}, 0, k, st[k].at, st[k].al, smu, st[k].dt, st[k].dl, num[l], den[l]);
             lane[l] = num[l] / den[l];
         }
         double alpha = p->frac * group_min(lane, L);
@@ -707,13 +615,11 @@ static int qp_ipm(const tw_par *p, tw_stage *st, const double dx0[4], int *exit,
         stall = alpha < p->qp_stall_alpha ? stall + 1 : 0;
         rscale *= 1.0 - alpha;
         for (int k = 0; k < L * S; ++k) {
-            tw_stage *s = st + k;
-            apply_step(s, alpha);
-            s->du[0] = qfma(alpha, s->VN[1] - s->du[0], s->du[0]);
-            s->du[1] = qfma(alpha, s->VN[2] - s->du[1], s->du[1]);
+            apply_step(tw_view{st + k}, 0, st[k].dt, st[k].dl, alpha);
+            damp_du(tw_view{st + k}, 0, alpha);
         }
     }
-    *exit = conv ? QP_EXIT_CONV : (div ? QP_EXIT_DIVERGED : (stalled ? QP_EXIT_STALL : QP_EXIT_CAP));
+    *exit = ipm_exit_code(conv, div, stalled);
     return nit;
 }
 
@@ -785,42 +691,15 @@ static void load_stage(const tw_par *p, const ShapeDev *sh, tw_stage *s, int k, 
 static int nlp_converged(const tw_par *p, const tw_stage *st, const double *PI, const double *LAM, double *kkt)
 {
     const int N = p->N;
-    double rs = 0.0, re = 0.0, ri = 0.0, rc = 0.0, ru = 0.0, rx = 0.0, rt = 0.0;
+    double re = 0.0, ri = 0.0, rc = 0.0, ru = 0.0, rx = 0.0, rt = 0.0;
     for (int k = 0; k <= N; ++k) {
         const tw_stage *s = st + k;
         const double zero[6] = {0, 0, 0, 0, 0, 0};
         const double *PIk = k < N ? PI + 4 * k : zero, *LAMk = k < N ? LAM + 6 * k : zero;
         const double *PIp = k >= 1 ? PI + 4 * (k - 1) : zero;
-        if (k < N) {
-            const double *B = s->B, *a = s->a;
-            for (int i = 0; i < 2; ++i) {
-                const double r = (s->g[4 + i] + qfma(B[6 + i], PIk[3], qfma(B[4 + i], PIk[2], qfma(B[2 + i], PIk[1], B[i] * PIk[0])))) +
-                                 (LAMk[2 * (1 + i) + 1] - LAMk[2 * (1 + i)]);
-                rs = fmax(rs, fabs(r));
-                ru = fmax(ru, fabs(r));
-            }
-            if (k >= 1) {
-                const double at[4] = {PIk[0], PIk[1], qfma(a[2], PIk[1], a[0] * PIk[0]) + PIk[2],
-                                      qfma(a[5], PIk[3], qfma(a[4], PIk[2], qfma(a[3], PIk[1], a[1] * PIk[0])))};
-                for (int i = 0; i < 4; ++i) {
-                    double r = s->g[i] - PIp[i] + at[i];
-                    if (i == 3) r += LAMk[1] - LAMk[0];
-                    rs = fmax(rs, fabs(r));
-                    rx = fmax(rx, fabs(r));
-                }
-            }
-            for (int i = 0; i < 4; ++i) re = fmax(re, fabs(s->bb[i]));
-            for (int j = 0; j < 3; ++j) {
-                if (j == 0 && k == 0 && !p->s0_bound) continue;
-                const double sl = s->v[j] - p->lh[j], sh_ = p->uh[j] - s->v[j];
-                ri = fmax(ri, fmax(-sl, -sh_));
-                rc = fmax(rc, fmax(fabs(LAMk[2 * j] * sl), fabs(LAMk[2 * j + 1] * sh_)));
-            }
-        } else {
-            for (int i = 0; i < 4; ++i) rs = fmax(rs, fabs(s->g[i] - PIp[i]));
-            for (int i = 0; i < 4; ++i) rt = fmax(rt, fabs(s->g[i] - PIp[i]));
-        }
+        kkt_stage(*p, k, s->a, s->B, s->g, s->bb, s->v, PIk, PIp, LAMk, ru, rx, rt, re, ri, rc);
     }
+    const double rs = fmax(fmax(ru, rx), rt);   /* the kernel keeps the three in one maximum */
     kkt[0] = ru; kkt[1] = rx; kkt[2] = rt; kkt[3] = re; kkt[4] = ri; kkt[5] = rc;
     return rs < p->tol_stat && re < p->tol_eq && ri < p->tol_ineq && rc < p->tol_comp;
 }
@@ -843,14 +722,8 @@ static void merit_ls(const tw_par *p, const ShapeDev *sh, tw_ws *w, double *X, d
         for (int q = 0; q < 4; ++q) NUk[k][q] = stg ? w->NU[4 * k + q] : 0.0;
         for (int q = 0; q < 6; ++q) ETAk[k][q] = stg ? w->ETA[6 * k + q] : 0.0;
         if (stg) {
-            for (int q = 0; q < 4; ++q) {
-                const double a = fabs(w->qPI[4 * k + q]), wq = 0.5 * (NUk[k][q] + a);
-                NUk[k][q] = a > wq ? a : wq;
-            }
-            for (int q = 0; q < 6; ++q) {
-                const double a = fabs(st[k].lm[q]), wq = 0.5 * (ETAk[k][q] + a);
-                ETAk[k][q] = a > wq ? a : wq;
-            }
+            for (int q = 0; q < 4; ++q) NUk[k][q] = merit_weight(NUk[k][q], fabs(w->qPI[4 * k + q]));
+            for (int q = 0; q < 6; ++q) ETAk[k][q] = merit_weight(ETAk[k][q], fabs(st[k].lm[q]));
         }
         double d = 0.0;
         for (int i = 0; i < 4; ++i) d = qfma(st[k].g[i], dxk[k][i], d);
@@ -904,14 +777,8 @@ static void merit_ls(const tw_par *p, const ShapeDev *sh, tw_ws *w, double *X, d
         if (k < N) {
             U[2 * k] = qfma(alpha, duk[k][0], uk[k][0]);
             U[2 * k + 1] = qfma(alpha, duk[k][1], uk[k][1]);
-            for (int q = 0; q < 4; ++q) {
-                const double pk = w->nlpPI[4 * k + q];
-                w->nlpPI[4 * k + q] = qfma(alpha, w->qPI[4 * k + q] - pk, pk);
-            }
-            for (int q = 0; q < 6; ++q) {
-                const double lk = w->LAM[6 * k + q];
-                w->LAM[6 * k + q] = qfma(alpha, st[k].lm[q] - lk, lk);
-            }
+            for (int q = 0; q < 4; ++q) w->nlpPI[4 * k + q] = damp_update(alpha, w->qPI[4 * k + q], w->nlpPI[4 * k + q]);
+            for (int q = 0; q < 6; ++q) w->LAM[6 * k + q] = damp_update(alpha, st[k].lm[q], w->LAM[6 * k + q]);
             memcpy(w->NU + 4 * k, NUk[k], sizeof(double) * 4);
             memcpy(w->ETA + 6 * k, ETAk[k], sizeof(double) * 6);
         }
@@ -1037,8 +904,6 @@ static double epilogue_cost(const tw_par *p, const double *X, const double *U, c
     for (int q = 0; q < 4; ++q) { const double r = X[4 * N + q] - ye[q]; s = qfma(p->We[q] * r, r, s); }
     return qfma(0.5, s, cost);
 }
-
-static int s0_infeasible(const tw_par *p, double s0) { return p->s0_bound && !(s0 >= p->lh[0] && s0 <= p->uh[0]); }
 
 /* ================================================================== exported API (as qsp_oracle.c) */
 extern "C" {
@@ -1210,7 +1075,7 @@ int tw_ocp_solve(const int32_t *n_ctrl, const double *ctrl, const double *knots,
             double PIin[TW_MAX_N * 4];
             memcpy(PIin, Pi, sizeof(double) * 4 * N);
             tw_out out;
-            const int w0 = s0_infeasible(&p, x0[4 * i + 3]) ? 3 : 0;
+            const int w0 = s0_infeasible(p, x0[4 * i + 3]) ? 3 : 0;
             sqp_solve(&p, &sh, w, x0 + 4 * i, yr, ye, Xi, Ui, PIin, Pi, 0, w0, &out);
             status[i] = out.status;
             if (iters) iters[i] = out.sqp_iter;
@@ -1258,28 +1123,16 @@ static int ctrl_lane(const tw_par *p, const ShapeDev *sh, tw_ws *w, const double
     double yref[TW_MAX_N * 6], ye[4], X[(TW_MAX_N + 1) * 4], U[TW_MAX_N * 2];
     stage_yref(traj, T, D, index_time, N, yref, ye);
     double x0[4] = {x0_in[0], x0_in[1], x0_in[2], x0_in[3]};
-    x0[3] = qfma(-sh->b, (x0[3] < 0.0) ? 1.0 : 0.0, mat_mod(x0[3], sh->b));
+    x0[3] = wrap_contact(*sh, x0[3]);
     const int cold = !*valid;
     for (int k = 0; k < N; ++k) {
         U[2 * k] = cold ? p->cp.u_n_lb : Uw[2 * k];
         U[2 * k + 1] = cold ? 0.0 : Uw[2 * k + 1];
     }
-    double xc[4] = {x0[0], x0[1], x0[2], x0[3]};
-    for (int k = 0; k <= N; ++k) {
-        for (int c = 0; c < 4; ++c) X[4 * k + c] = xc[c];
-        if (k == N) break;
-        const double vb = v_bound(*sh, p->cp, xc[3]);   /* with the handle's controller parameters */
-        const double ut_old = U[2 * k + 1];
-        if (fabs(ut_old) > vb) {
-            const double sgn = ut_old > 0.0 ? 1.0 : -1.0;
-            U[2 * k + 1] = sgn * vb;
-            U[2 * k] = U[2 * k + 1] * U[2 * k] / ut_old;
-        }
-        euler_step(*sh, p->Ts, xc, U[2 * k], U[2 * k + 1]);
-    }
+    guess_rollout(*sh, *p, x0, U, X);   /* with the handle's controller parameters */
     double PIin[TW_MAX_N * 4];
     memcpy(PIin, PIw, sizeof(double) * 4 * N);
-    const int w0 = s0_infeasible(p, x0[3]) ? 3 : 0;
+    const int w0 = s0_infeasible(*p, x0[3]) ? 3 : 0;
     sqp_solve(p, sh, w, x0, yref, ye, X, U, cold ? NULL : PIin, PIw, 1, w0, out);
     if (cost) *cost = epilogue_cost(p, X, U, yref, ye);
     u0[0] = U[0];
@@ -1332,44 +1185,7 @@ int tw_controller_solve(const int32_t *n_ctrl, const double *ctrl, const double 
     return 0;
 }
 
-/* contact re-projection (reproject_contact / contact_phi) */
-static double contact_phi(const ShapeDev *sh, double s, double px, double py)
-{
-    SplineEval e;
-    spline_eval(*sh, mat_mod(s, sh->b), e);
-    const double ex = e.C[0] - px, ey = e.C[1] - py;
-    return qfma(ey, ey, ex * ex);
-}
-
-static double reproject_contact(const ShapeDev *sh, double px, double py, double s0)
-{
-    double s = s0, phi = contact_phi(sh, s, px, py);
-    for (int it = 0; it < 60; ++it) {
-        SplineEval e;
-        spline_eval(*sh, mat_mod(s, sh->b), e);
-        const double ex = e.C[0] - px, ey = e.C[1] - py;
-        const double g = 2.0 * qfma(ey, e.D[1], ex * e.D[0]);
-        const double h = 2.0 * qfma(ey, e.Dd[1], qfma(ex, e.Dd[0], qfma(e.D[1], e.D[1], e.D[0] * e.D[0])));
-        if (fabs(g) < 1e-14) break;
-        double step = h > 0.0 ? -g / h : (g > 0.0 ? -0.05 : 0.05) * sh->b;
-        const double smax = 0.25 * sh->b;
-        step = fmin(fmax(step, -smax), smax);
-        int ok = 0;
-        double sn = s, phin = phi;
-        for (int k = 0; k < 60; ++k) {
-            sn = s + step;
-            phin = contact_phi(sh, sn, px, py);
-            if (phin < phi) { ok = 1; break; }
-            step *= 0.5;
-        }
-        if (!ok) break;
-        s = sn;
-        phi = phin;
-        if (fabs(step) < 1e-13 * sh->b) break;
-    }
-    return s;
-}
-
+/* contact re-projection: reproject_contact, qsp_math.hpp */
 int tw_reproject_contact(const int32_t *n_ctrl, const double *ctrl, const double *knots, const double *params,
                          int max_ctrl, int32_t n, const int32_t *shape_id, const double *px, const double *py,
                          const double *s0, double *s)
@@ -1377,7 +1193,7 @@ int tw_reproject_contact(const int32_t *n_ctrl, const double *ctrl, const double
     for (int32_t i = 0; i < n; ++i) {
         ShapeDev sh;
         make_shape(&sh, n_ctrl, ctrl, knots, params, max_ctrl, shape_id[i], 0.0);
-        s[i] = reproject_contact(&sh, px[i], py[i], s0[i]);
+        s[i] = reproject_contact(sh, px[i], py[i], s0[i]);
     }
     return 0;
 }
@@ -1427,8 +1243,8 @@ int tw_closed_loop(const int32_t *n_ctrl, const double *ctrl, const double *knot
                     x[1] += amp;
                     SplineEval e;
                     spline_eval(sh, mat_mod(x[3], sh.b), e);
-                    const double sn = reproject_contact(&sh, -0.5 * sh.xwidth, e.C[1] - amp, 0.0);
-                    x[3] = qfma(-sh.b, sn < 0.0 ? 1.0 : 0.0, mat_mod(sn, sh.b));
+                    const double sn = reproject_contact(sh, -0.5 * sh.xwidth, e.C[1] - amp, 0.0);
+                    x[3] = wrap_contact(sh, sn);
                 }
                 if (noise)
                     for (int c = 0; c < 4; ++c) x[c] += noise[((size_t)t * nb + i) * 4 + c];

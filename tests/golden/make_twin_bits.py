@@ -2,9 +2,9 @@
 tests/twin_bits_cases.py, as raw 64-bit patterns.
 
 The twin and the kernels evaluate one source of lane arithmetic (csrc/qsp_fp.hpp, qsp_math.hpp,
-qsp_riccati.hpp), so a change of rounding order there moves both sides together and the GPU-vs-twin
-comparison cannot see it; this fixture can.  It was first written by the last twin that restated
-that arithmetic by hand.  Regenerate it only when a change of the arithmetic is the intent:
+qsp_riccati.hpp, qsp_ipm.hpp), so a change of rounding order there moves both sides together and the GPU-vs-twin
+comparison cannot see it; this fixture can.  Each case was written by the last twin that restated
+the arithmetic it reaches by hand.  Regenerate it only when a change of the arithmetic is the intent:
     python tests/golden/make_twin_bits.py
 """
 import os

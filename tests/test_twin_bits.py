@@ -1,8 +1,8 @@
 """CPU: the twin's outputs against tests/golden/twin_bits.npz, in every bit.
 
-The twin calls the kernels' own lane arithmetic (csrc/qsp_fp.hpp, qsp_math.hpp, qsp_riccati.hpp), so
+The twin calls the kernels' own lane arithmetic (csrc/qsp_fp.hpp, qsp_math.hpp, qsp_riccati.hpp, qsp_ipm.hpp), so
 the GPU-vs-twin comparison no longer notices a change of rounding order made there: both sides move
-together.  This fixture, first written by the last hand-restated twin, does.  Every operation on
+together.  This fixture, each case written by the last twin that restated that arithmetic by hand, does.  Every operation on
 the path is one the host rounds deterministically (+ - * / sqrt fma, fmod, floor, rint; sin_cos and
 rcp are the project's own sequences), so the bits depend neither on the machine nor on the OpenMP
 thread count."""
@@ -40,5 +40,5 @@ def test_twin_bits(case, computed, golden):
         assert np.array_equal(got, want), (
             f"{k}: {int((got != want).sum())} of {want.size} words differ from tests/golden/twin_bits.npz. "
             "The lane arithmetic shared by the kernels and the twin (csrc/qsp_fp.hpp, qsp_math.hpp, "
-            "qsp_riccati.hpp) or the twin's orchestration changed its bits.  Regenerate the fixture "
+            "qsp_riccati.hpp, qsp_ipm.hpp) or the twin's orchestration changed its bits.  Regenerate the fixture "
             "(tests/golden/make_twin_bits.py) only if that change was the intent.")

@@ -14,7 +14,7 @@
 //           about one ulp for |x| < 2^20 pi/2; beyond that the reduction degrades (the model's
 //           theta stays within a few radians).
 //
-// This header, qsp_math.hpp and qsp_riccati.hpp are the one statement of the lane-local arithmetic:
+// This header, qsp_math.hpp, qsp_riccati.hpp and qsp_ipm.hpp are the one statement of the lane-local arithmetic:
 // straight-line functions that read no other lane.  hipcc compiles them into the kernels; a plain
 // C++ compiler (no ROCm include path) compiles them into the CPU twin, oracle/qsp_twin.cpp (test
 // infrastructure may read a product header; the product never reads the twin).  Their qualifiers:

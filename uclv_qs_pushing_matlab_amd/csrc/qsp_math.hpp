@@ -116,6 +116,49 @@ QSP_FN double v_bound(const ShapeDev& sh, const CtrlParams& cp, double s) {
     return v < cp.u_t_ub ? v : cp.u_t_ub;
 }
 
+// ---------------------------------------------------------------- contact re-projection
+// a contact coordinate wrapped into [-b, b): floor-mod into [0, b), less b for a negative s
+// (NMPC_controller.m:332, helper.m:234)
+QSP_FN double wrap_contact(const ShapeDev& sh, double s) { return qfma(-sh.b, s < 0.0 ? 1.0 : 0.0, mat_mod(s, sh.b)); }
+
+// |C(s) - p|^2 with C at the floor-mod of s (evalSpline, bspline_shape.m:192-199)
+QSP_FN double contact_phi(const ShapeDev& sh, double s, double px, double py) {
+    SplineEval e;
+    spline_eval(sh, mat_mod(s, sh.b), e);
+    const double ex = e.C[0] - px, ey = e.C[1] - py;
+    return qfma(ey, ey, ex * ex);
+}
+
+// The contact point after a lateral disturbance: argmin_s |C(s) - p|^2 from s0 (fminunc in the
+// reference, helper.m:230; restated as a damped Newton iteration, shared with the oracle's twin)
+QSP_FN double reproject_contact(const ShapeDev& sh, double px, double py, double s0) {
+    double s = s0, phi = contact_phi(sh, s, px, py);
+    for (int it = 0; it < 60; ++it) {
+        SplineEval e;
+        spline_eval(sh, mat_mod(s, sh.b), e);
+        const double ex = e.C[0] - px, ey = e.C[1] - py;
+        const double g = 2.0 * qfma(ey, e.D[1], ex * e.D[0]);
+        const double h = 2.0 * qfma(ey, e.Dd[1], qfma(ex, e.Dd[0], qfma(e.D[1], e.D[1], e.D[0] * e.D[0])));
+        if (fabs(g) < 1e-14) break;
+        double step = h > 0.0 ? -g / h : (g > 0.0 ? -0.05 : 0.05) * sh.b;
+        const double smax = 0.25 * sh.b;
+        step = fmin(fmax(step, -smax), smax);
+        bool ok = false;
+        double sn = s, phin = phi;
+        for (int k = 0; k < 60; ++k) {
+            sn = s + step;
+            phin = contact_phi(sh, sn, px, py);
+            if (phin < phi) { ok = true; break; }
+            step *= 0.5;
+        }
+        if (!ok) break;
+        s = sn;
+        phi = phin;
+        if (fabs(step) < 1e-13 * sh.b) break;
+    }
+    return s;
+}
+
 // ---------------------------------------------------------------- dynamics
 // f(x,u) and its Jacobian.  f does not depend on (x, y); d f/d theta only has
 // rows 0,1.  Jacobian columns: Jth[2], Js[4], Jun[4], Jut[4].

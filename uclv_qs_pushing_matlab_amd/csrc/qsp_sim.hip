@@ -31,44 +31,6 @@ namespace qsp {
 //   plant_kernel: the controller input buffer push (helper.m:255), the plant x(:,i+1) = x(:,i) +
 //     Ts * evalModelVariableShape(x(:,i), u) with the plant's own delay buffer (:289-307), logs.
 
-// |C(s) - p|^2 with C at the floor-mod of s (evalSpline, bspline_shape.m:192-199)
-__device__ __forceinline__ double contact_phi(const ShapeDev& sh, double s, double px, double py) {
-    SplineEval e;
-    spline_eval(sh, mat_mod(s, sh.b), e);
-    const double ex = e.C[0] - px, ey = e.C[1] - py;
-    return qfma(ey, ey, ex * ex);
-}
-
-// The contact point after a lateral disturbance: argmin_s |C(s) - p|^2 from s0 (fminunc in the
-// reference, helper.m:230; restated as a damped Newton iteration, as the oracle's reproject_contact)
-__device__ double reproject_contact(const ShapeDev& sh, double px, double py, double s0) {
-    double s = s0, phi = contact_phi(sh, s, px, py);
-    for (int it = 0; it < 60; ++it) {
-        SplineEval e;
-        spline_eval(sh, mat_mod(s, sh.b), e);
-        const double ex = e.C[0] - px, ey = e.C[1] - py;
-        const double g = 2.0 * qfma(ey, e.D[1], ex * e.D[0]);
-        const double h = 2.0 * qfma(ey, e.Dd[1], qfma(ex, e.Dd[0], qfma(e.D[1], e.D[1], e.D[0] * e.D[0])));
-        if (fabs(g) < 1e-14) break;
-        double step = h > 0.0 ? -g / h : (g > 0.0 ? -0.05 : 0.05) * sh.b;
-        const double smax = 0.25 * sh.b;
-        step = fmin(fmax(step, -smax), smax);
-        bool ok = false;
-        double sn = s, phin = phi;
-        for (int k = 0; k < 60; ++k) {
-            sn = s + step;
-            phin = contact_phi(sh, sn, px, py);
-            if (phin < phi) { ok = true; break; }
-            step *= 0.5;
-        }
-        if (!ok) break;
-        s = sn;
-        phi = phin;
-        if (fabs(step) < 1e-13 * sh.b) break;
-    }
-    return s;
-}
-
 // With a plant model installed (qsp_set_plant_*) the three kernels below take lane i's shape, c and
 // mu from it (plant_of): the reference simulates, predicts and re-projects with `plant`
 // (helper.m:226-233, :244, :294-307) and keeps the controller's model for solve alone.
@@ -107,7 +69,7 @@ __global__ void closed_loop_pre_kernel(ClosedLoopArgs a, int t) {
         SplineEval e;
         spline_eval(sh, mat_mod(x[3], sh.b), e);
         const double sn = reproject_contact(sh, -0.5 * sh.xwidth, e.C[1] - amp, 0.0);
-        x[3] = qfma(-sh.b, sn < 0.0 ? 1.0 : 0.0, mat_mod(sn, sh.b));
+        x[3] = wrap_contact(sh, sn);
     }
     if (a.noise) {
         for (int c = 0; c < 4; ++c) x[c] += a.noise[((size_t)t * a.B + i) * 4 + c];

@@ -36,6 +36,7 @@
 #include "qsp_layout.h"
 #include "qsp_math.hpp"
 #include "qsp_riccati.hpp"
+#include "qsp_ipm.hpp"
 #include "qsp_kernels.h"
 
 #ifndef QSP_MIN_WAVES
@@ -218,6 +219,9 @@ struct Stage {
     __device__ __forceinline__ double& dxs(int ls, int i) const { return f(F_DX, ls, i); }
     __device__ __forceinline__ double& hg(int ls, int i) const { return f(F_HG, ls, i); }
     __device__ __forceinline__ double& rt(int ls, int q) const { return f(F_RT, ls, q); }
+    // with the accessors above, the view of this lane's slots that qsp_ipm.hpp's functions take
+    __device__ __forceinline__ double& va(int ls, int j) const { return f(F_VA, ls, j); }
+    __device__ __forceinline__ double& vn(int ls, int j) const { return f(F_VN, ls, j); }
 };
 
 struct Ctx {
@@ -228,9 +232,7 @@ struct Ctx {
 };
 
 // Wave geometry of a thread (qsp_layout.h): its group of L lanes, its place in it, and the instance
-// of the launch's range [0, nI) the group holds (real: there is one).  sqp_loop_kernel's and
-// merit_ls_kernel's; qp_step_kernel writes the same lines out (the call there changes the
-// instructions of one of its instantiations).
+// of the launch's range [0, nI) the group holds (real: there is one).
 template <int S>
 __device__ __forceinline__ Ctx ctx_of(int lane, int N, int nI) {
     Ctx c;
@@ -250,22 +252,6 @@ __device__ __forceinline__ Ctx ctx_of(int lane, int N, int nI) {
 
 template <int S>
 __device__ __forceinline__ int kof(const Ctx& c, int ls) { return c.lig * S + ls; }
-
-// Is bound side j (0 = s, 1 = u_n, 2 = u_t) of stage k part of the QP?  Stages 0..N-1; the s
-// bound at stage 0 only with stage0_s_bound (s_0 is fixed by x0 there: the pair is a
-// constant slack that enters the complementarity measure, NMPC_controller.m:237,251-252).
-__device__ __forceinline__ bool bnd_act(const Ctx& c, const SolveParams& p, int k, int j) {
-    return (k < c.N) && (j > 0 || k >= 1 || p.s0_bound != 0);
-}
-
-// bounds of the QP step of slot ls: lo = lh - v, hi = uh - v, v = (s, u_n, u_t)
-template <int S>
-__device__ __forceinline__ void bnd_lohi(const SolveParams& p, const Stage<S>& st, int ls, double lo[3], double hi[3]) {
-    const double v0 = st.v(ls, 0), v1 = st.v(ls, 1), v2 = st.v(ls, 2);
-    lo[0] = p.lh[0] - v0; hi[0] = p.uh[0] - v0;
-    lo[1] = p.lh[1] - v1; hi[1] = p.uh[1] - v1;
-    lo[2] = p.lh[2] - v2; hi[2] = p.uh[2] - v2;
-}
 
 // chain hand-over along the wavefront without an LDS round trip (DPP wave shift)
 // (lanes without a source keep their own value, so the move can be done in place)
@@ -602,135 +588,7 @@ __device__ __forceinline__ void velem_read(const VElem& e, int src, VElem& f) {
 }
 
 // ------------------------------------------------------------------ QP core
-// Barrier terms of bound pair j of slot ls (predictor): hgv[ls][j] Hessian addition, hgv[ls][3 + j]
-// gradient addition, handed to the factorisation in registers (it reads them once, right after the
-// loop's exit test: no LDS round trip).  They depend on t, lm, rt and the iterate only, not on mu.
-// The corrector changes only the gradient (corrector_terms, through F_HG).
-template <int S>
-__device__ __forceinline__ void barrier_term(const Ctx& c, const SolveParams& p, const Stage<S>& st, int ls, int j,
-                                             double (&hgv)[S][6]) {
-    const double v = st.v(ls, j);
-    const double lo = p.lh[j] - v, hi = p.uh[j] - v;   // bnd_lohi's
-    const bool act = bnd_act(c, p, kof<S>(c, ls), j);
-    const double ll = st.lm(ls, 2 * j), lh = st.lm(ls, 2 * j + 1);
-    const double sl = ll * st.rt(ls, 2 * j), sh = lh * st.rt(ls, 2 * j + 1);
-    const double gadd = qfma(-sh, hi, -sl * lo) + (lh - ll);
-    hgv[ls][j] = act ? sl + sh : 0.0;
-    hgv[ls][3 + j] = act ? gadd : 0.0;
-}
-
-// The step length is the largest alpha with t + alpha dt >= 0 and l + alpha dl >= 0,
-// tracked as a ratio num/den without dividing (den > 0): a candidate t/(-dt) replaces
-// num/den when t * den < num * (-dt).
-// Affine (predictor) slack/multiplier directions of slot ls from its bounded QP solution
-// components (F_VA), unmasked, kept in registers for the rest of the IPM iteration:
-// at/al[2j] lower, [2j+1] upper bound of component j.  Also folds the masked directions
-// into the step-length ratio num/den.
-template <int S>
-__device__ __forceinline__ void affine_dirs(const Ctx& c, const SolveParams& p, const Stage<S>& st, int ls,
-                                            double at[6], double al[6], double& num, double& den) {
-    const int k = kof<S>(c, ls);
-    double lo[3], hi[3];
-    bnd_lohi<S>(p, st, ls, lo, hi);
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        const bool act = bnd_act(c, p, k, j);
-        const double tl = st.t(ls, 2 * j), th = st.t(ls, 2 * j + 1);
-        const double ll = st.lm(ls, 2 * j), lh = st.lm(ls, 2 * j + 1);
-        const double sl = ll * st.rt(ls, 2 * j), sh = lh * st.rt(ls, 2 * j + 1);
-        const double v = st.f(F_VA, ls, j);
-        at[2 * j] = v - lo[j] - tl;
-        at[2 * j + 1] = hi[j] - v - th;
-        al[2 * j] = qfma(-sl, at[2 * j], -ll);
-        al[2 * j + 1] = qfma(-sh, at[2 * j + 1], -lh);
-        const double dtl = act ? at[2 * j] : 0.0, dth = act ? at[2 * j + 1] : 0.0;
-        const double dll = act ? al[2 * j] : 0.0, dlh = act ? al[2 * j + 1] : 0.0;
-        if (dtl < 0.0 && tl * den < num * -dtl) { num = tl; den = -dtl; }
-        if (dth < 0.0 && th * den < num * -dth) { num = th; den = -dth; }
-        if (dll < 0.0 && ll * den < num * -dll) { num = ll; den = -dll; }
-        if (dlh < 0.0 && lh * den < num * -dlh) { num = lh; den = -dlh; }
-    }
-}
-
-// Complementarity after the affine step aa (Mehrotra's mu_aff), from the cached directions.
-template <int S>
-__device__ __forceinline__ double affine_mu_part(const Ctx& c, const SolveParams& p, const Stage<S>& st, int ls,
-                                                 const double at[6],
-                                                 const double al[6], double aa, double part) {
-    const int k = kof<S>(c, ls);
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        const bool act = bnd_act(c, p, k, j);
-        const double tl = st.t(ls, 2 * j), th = st.t(ls, 2 * j + 1);
-        const double ll = st.lm(ls, 2 * j), lh = st.lm(ls, 2 * j + 1);
-        const double dtl = act ? at[2 * j] : 0.0, dth = act ? at[2 * j + 1] : 0.0;
-        const double dll = act ? al[2 * j] : 0.0, dlh = act ? al[2 * j + 1] : 0.0;
-        part = qfma(qfma(aa, dtl, tl), qfma(aa, dll, ll), part);
-        part = qfma(qfma(aa, dth, th), qfma(aa, dlh, lh), part);
-    }
-    return part;
-}
-
-// Corrector barrier gradient change of slot ls from the cached affine directions (the
-// Hessian is the predictor's): hg[3+j] = c_h / t_h - c_l / t_l, c = sigma mu - dt_aff dl_aff.
-template <int S>
-__device__ __forceinline__ void corrector_terms(const Ctx& c, const SolveParams& p, const Stage<S>& st, int ls,
-                                                const double at[6],
-                                                const double al[6], double smu) {
-    const int k = kof<S>(c, ls);
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        const bool act = bnd_act(c, p, k, j);
-        const double cl = qfma(-at[2 * j], al[2 * j], smu), ch = qfma(-at[2 * j + 1], al[2 * j + 1], smu);
-        st.hg(ls, 3 + j) = act ? qfma(ch, st.rt(ls, 2 * j + 1), -(cl * st.rt(ls, 2 * j))) : 0.0;
-    }
-}
-
-// Corrector directions of slot ls (masked) from its bounded QP solution components (F_VN) and
-// the cached affine directions; folded into the ratio num/den and kept for the update.
-template <int S>
-__device__ __forceinline__ void corrector_dirs(const Ctx& c, const SolveParams& p, const Stage<S>& st, int ls,
-                                               const double at[6], const double al[6], double smu, double dt[6],
-                                               double dl[6], double& num, double& den) {
-    const int k = kof<S>(c, ls);
-    double lo[3], hi[3];
-    bnd_lohi<S>(p, st, ls, lo, hi);
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        const bool act = bnd_act(c, p, k, j);
-        const double tl = st.t(ls, 2 * j), th = st.t(ls, 2 * j + 1);
-        const double ll = st.lm(ls, 2 * j), lh = st.lm(ls, 2 * j + 1);
-        const double rtl = st.rt(ls, 2 * j), rth = st.rt(ls, 2 * j + 1);
-        const double sl = ll * rtl, sh = lh * rth;
-        const double v = st.f(F_VN, ls, j);
-        double dtl = v - lo[j] - tl, dth = hi[j] - v - th;
-        double dll = qfma(-sl, dtl, -ll), dlh = qfma(-sh, dth, -lh);
-        dll = qfma(qfma(-at[2 * j], al[2 * j], smu), rtl, dll);
-        dlh = qfma(qfma(-at[2 * j + 1], al[2 * j + 1], smu), rth, dlh);
-        dtl = act ? dtl : 0.0; dth = act ? dth : 0.0;
-        dll = act ? dll : 0.0; dlh = act ? dlh : 0.0;
-        if (dtl < 0.0 && tl * den < num * -dtl) { num = tl; den = -dtl; }
-        if (dth < 0.0 && th * den < num * -dth) { num = th; den = -dth; }
-        if (dll < 0.0 && ll * den < num * -dll) { num = ll; den = -dll; }
-        if (dlh < 0.0 && lh * den < num * -dlh) { num = lh; den = -dlh; }
-        dt[2 * j] = dtl; dt[2 * j + 1] = dth;
-        dl[2 * j] = dll; dl[2 * j + 1] = dlh;
-    }
-}
-
-// Step of slot ls: t += alpha dt (and its reciprocal), l += alpha dl.
-template <int S>
-__device__ __forceinline__ void apply_step(const Stage<S>& st, int ls, const double dt[6], const double dl[6],
-                                           double alpha) {
-#pragma unroll
-    for (int q = 0; q < 6; ++q) {
-        const double tn = qfma(alpha, dt[q], st.t(ls, q));
-        st.t(ls, q) = tn;
-        st.rt(ls, q) = rcp(tn);
-        st.lm(ls, q) = qfma(alpha, dl[q], st.lm(ls, q));
-    }
-}
-
+// (the slots' barrier terms, directions and step: qsp_ipm.hpp, with Stage<S> as the view)
 // Backward pass over the group (factorisation, or the corrector's difference recursion),
 // then forward pass writing the bounded components of the solution into LDS field `out`
 // (F_VA / F_VN).
@@ -1025,8 +883,6 @@ __device__ __forceinline__ void riccati_solve(const Ctx& c, const SolveParams& p
     }
 }
 
-enum QpExit : int { QP_EXIT_CONV = 0, QP_EXIT_CAP = 1, QP_EXIT_STALL = 2, QP_EXIT_DIVERGED = 3 };
-
 // Mehrotra predictor-corrector IPM on the current linearisation.  Leaves the
 // damped control step in LDS (F_DU) and the slacks/multipliers in F_T / F_LM.
 // Returns the number of iterations taken by this lane's instance and, in `exit`, why it stopped
@@ -1058,11 +914,11 @@ __device__ int qp_ipm(const Ctx& c, const SolveParams& p, Stage<S>& st, const do
     for (int ls = 0; ls < S; ++ls) {
         const int k = kof<S>(c, ls);
         double lo[3], hi[3];
-        bnd_lohi<S>(p, st, ls, lo, hi);
+        bnd_lohi(p, st, ls, lo, hi);
         double gl[3];
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
-            const bool act = bnd_act(c, p, k, j);
+            const bool act = bnd_act(p, c.N, k, j);
             const double tl = fmax(-lo[j], p.t_min), th = fmax(hi[j], p.t_min);
             if (act) r0 = fmax(r0, fmax(tl + lo[j], th - hi[j]));
             const double rl = rcp(tl), rh = rcp(th);
@@ -1117,13 +973,8 @@ __device__ int qp_ipm(const Ctx& c, const SolveParams& p, Stage<S>& st, const do
         // factorisation.  The pass in front of the break that ends the loop is computed for
         // nothing (registers only); a finished instance recomputes the terms of its frozen state.
         double hgv[S][6];
-        const double mu = group_sum_over<3 * S>(tl_sum, c.gs, [&](int q) { barrier_term<S>(c, p, st, q / 3, q % 3, hgv); }) / m;
-        // divergence first (mu non-finite or past qp_mu_max: a NaN mu would pass the stop test),
-        // then the stop test, then the stall exit (locally infeasible QP: the step length stays
-        // tiny while mu grows)
-        div = !skip && !(mu < p.qp_mu_max);
-        conv = !div && (skip || (!(mu >= p.mu_stop) && !(rscale >= rs_stop)));
-        stalled = !conv && !div && p.qp_stall_iters > 0 && stall >= p.qp_stall_iters;
+        const double mu = group_sum_over<3 * S>(tl_sum, c.gs, [&](int q) { barrier_term(p, c.N, st, q / 3, kof<S>(c, q / 3), q % 3, hgv[q / 3]); }) / m;
+        ipm_exit_test(p, mu, rscale, rs_stop, stall, skip, div, conv, stalled);
         const bool done = conv || div || stalled;
         // the cap is tested after the last step too (conv reports it), then the loop ends
         if (it == p.qp_iters || __ballot(!done) == 0ull) break;
@@ -1140,11 +991,11 @@ __device__ int qp_ipm(const Ctx& c, const SolveParams& p, Stage<S>& st, const do
         double at[S][6], al[S][6];
         double num = 1.0, den = 1.0;
 #pragma unroll
-        for (int ls = 0; ls < S; ++ls) affine_dirs<S>(c, p, st, ls, at[ls], al[ls], num, den);
+        for (int ls = 0; ls < S; ++ls) affine_dirs(p, c.N, st, ls, kof<S>(c, ls), at[ls], al[ls], num, den);
         const double aa = group_min(num / den, c.gs);
         double ma = 0.0;
 #pragma unroll
-        for (int ls = 0; ls < S; ++ls) ma = affine_mu_part<S>(c, p, st, ls, at[ls], al[ls], aa, ma);
+        for (int ls = 0; ls < S; ++ls) ma = affine_mu_part(p, c.N, st, ls, kof<S>(c, ls), at[ls], al[ls], aa, ma);
         const double mua = group_sum_flat(ma, c.gs) / m;
         const double r = mua / mu;
         const double sg = fmax(r * r * r, p.sigma_min);
@@ -1152,14 +1003,14 @@ __device__ int qp_ipm(const Ctx& c, const SolveParams& p, Stage<S>& st, const do
         SEG_NEXT(4, t_seg2);
         // ---- corrector
 #pragma unroll
-        for (int ls = 0; ls < S; ++ls) corrector_terms<S>(c, p, st, ls, at[ls], al[ls], smu);
+        for (int ls = 0; ls < S; ++ls) corrector_terms(p, c.N, st, ls, kof<S>(c, ls), at[ls], al[ls], smu);
         SEG_ADD(5, t_seg2);
         riccati_solve<S, false, ALT>(c, p, st, dx0, F_VN, M, hgv);
         SEG_T(t_seg3);
         double dt[S][6], dl[S][6];
         num = 1.0; den = p.frac;       // initial bound 1/frac
 #pragma unroll
-        for (int ls = 0; ls < S; ++ls) corrector_dirs<S>(c, p, st, ls, at[ls], al[ls], smu, dt[ls], dl[ls], num, den);
+        for (int ls = 0; ls < S; ++ls) corrector_dirs(p, c.N, st, ls, kof<S>(c, ls), at[ls], al[ls], smu, dt[ls], dl[ls], num, den);
         double alpha = p.frac * group_min(num / den, c.gs);
         alpha = fmin(alpha, 1.0);
         // a finished instance sits the rest of the wave's loop out with its state frozen
@@ -1168,14 +1019,13 @@ __device__ int qp_ipm(const Ctx& c, const SolveParams& p, Stage<S>& st, const do
             rscale *= 1.0 - alpha;
 #pragma unroll
             for (int ls = 0; ls < S; ++ls) {
-                apply_step<S>(st, ls, dt[ls], dl[ls], alpha);
-                st.du(ls, 0) = qfma(alpha, st.f(F_VN, ls, 1) - st.du(ls, 0), st.du(ls, 0));
-                st.du(ls, 1) = qfma(alpha, st.f(F_VN, ls, 2) - st.du(ls, 1), st.du(ls, 1));
+                apply_step(st, ls, dt[ls], dl[ls], alpha);
+                damp_du(st, ls, alpha);
             }
         }
         SEG_ADD(8, t_seg3);
     }
-    exit = conv ? QP_EXIT_CONV : (div ? QP_EXIT_DIVERGED : (stalled ? QP_EXIT_STALL : QP_EXIT_CAP));
+    exit = ipm_exit_code(conv, div, stalled);
     return nit;
 }
 
@@ -1321,13 +1171,11 @@ __device__ __forceinline__ void nlp_init(const SolveArgs& A, int i, bool use_pi)
         for (int q = 0; q < 4; ++q) A.wres[(size_t)i * 4 + q] = 0.0;
 }
 
-// With the stage-0 s bound in the QP (stage0_s_bound), s_0 = x0's s is a fixed quantity of
-// every QP: outside [lh_s, uh_s] every QP of the solve is infeasible.  The instance then does
-// not iterate (wdone = 3: status QSP_STATUS_QP_FAIL, sqp_iter 0, the initial guess returned),
-// as the oracle's sqp_solve.  (Called after nlp_init, which clears wdone.)
+// An instance whose s_0 makes every QP infeasible (s0_infeasible, qsp_ipm.hpp) does not iterate
+// (wdone = 3: status QSP_STATUS_QP_FAIL, sqp_iter 0, the initial guess returned), as the oracle's
+// sqp_solve.  (Called after nlp_init, which clears wdone.)
 __device__ __forceinline__ void s0_feasible(const SolveArgs& A, int i, double s0) {
-    const SolveParams& p = A.p;
-    if (p.s0_bound && A.wdone && !(s0 >= p.lh[0] && s0 <= p.uh[0])) {
+    if (A.wdone && s0_infeasible(A.p, s0)) {
         A.wdone[i] = 3;
         A.sqp_iter[i] = 0;
     }
@@ -1358,7 +1206,7 @@ __global__ void prologue_kernel(SolveArgs A) {
         s0_feasible(A, i, x0[3]);
         return;
     }
-    x0[3] = qfma(-sh.b, (x0[3] < 0.0) ? 1.0 : 0.0, mat_mod(x0[3], sh.b));   // :332
+    x0[3] = wrap_contact(sh, x0[3]);   // :332
     for (int c = 0; c < 4; ++c) A.wx0[(size_t)i * 4 + c] = x0[c];
     const bool cold = (A.warm_valid == nullptr || A.warm_valid[i] == 0);
     if (p.nlp_mode == 1) nlp_init(A, i, !cold);                             // :351-355 (PI = 0 cold)
@@ -1366,19 +1214,7 @@ __global__ void prologue_kernel(SolveArgs A) {
         U[2 * k] = cold ? p.cp.u_n_lb : A.U_in[((size_t)i * N + k) * 2];
         U[2 * k + 1] = cold ? 0.0 : A.U_in[((size_t)i * N + k) * 2 + 1];
     }
-    double xc[4] = {x0[0], x0[1], x0[2], x0[3]};
-    for (int k = 0; k <= N; ++k) {                                           // :357-380
-        for (int c = 0; c < 4; ++c) X[4 * k + c] = xc[c];
-        if (k == N) break;
-        const double vb = v_bound(sh, p.cp, xc[3]);
-        const double ut_old = U[2 * k + 1];
-        if (fabs(ut_old) > vb) {
-            const double sgn = ut_old > 0.0 ? 1.0 : -1.0;
-            U[2 * k + 1] = sgn * vb;
-            U[2 * k] = U[2 * k + 1] * U[2 * k] / ut_old;
-        }
-        euler_step(sh, p.Ts, xc, U[2 * k], U[2 * k + 1]);
-    }
+    guess_rollout(sh, p, x0, U, X);                                          // :357-380
     s0_feasible(A, i, x0[3]);
 }
 
@@ -1427,7 +1263,6 @@ __device__ bool nlp_converged(const Ctx& c, const SolveParams& p, const Stage<1>
                               double* res) {
     const int N = p.N;
     const int k = c.lig;
-    const bool stg = k < N;
     double PIk[4], LAMk[6];
 #pragma unroll
     for (int q = 0; q < 4; ++q) PIk[q] = nlp[(W_PI + q) * tot];
@@ -1437,39 +1272,8 @@ __device__ bool nlp_converged(const Ctx& c, const SolveParams& p, const Stage<1>
 #pragma unroll
     for (int q = 0; q < 4; ++q) PIp[q] = wave_from_prev(PIk[q]);   // pi_{k-1}
     double rs = 0.0, re = 0.0, ri = 0.0, rc = 0.0;
-    if (stg) {
-        const double* B = st.B[0];
-        const double* a = st.a[0];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const double r = (st.g[0][4 + i] + qfma(B[6 + i], PIk[3], qfma(B[4 + i], PIk[2], qfma(B[2 + i], PIk[1], B[i] * PIk[0])))) +
-                             (LAMk[2 * (1 + i) + 1] - LAMk[2 * (1 + i)]);
-            rs = fmax(rs, fabs(r));
-        }
-        if (k >= 1) {
-            const double at[4] = {PIk[0], PIk[1], qfma(a[2], PIk[1], a[0] * PIk[0]) + PIk[2],
-                                  qfma(a[5], PIk[3], qfma(a[4], PIk[2], qfma(a[3], PIk[1], a[1] * PIk[0])))};
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                double r = st.g[0][i] - PIp[i] + at[i];
-                if (i == 3) r += LAMk[1] - LAMk[0];
-                rs = fmax(rs, fabs(r));
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) re = fmax(re, fabs(st.bb[0][i]));
-        const double v[3] = {st.v(0, 0), st.v(0, 1), st.v(0, 2)};
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            if (j == 0 && k == 0 && !p.s0_bound) continue;
-            const double sl = v[j] - p.lh[j], sh_ = p.uh[j] - v[j];
-            ri = fmax(ri, fmax(-sl, -sh_));
-            rc = fmax(rc, fmax(fabs(LAMk[2 * j] * sl), fabs(LAMk[2 * j + 1] * sh_)));
-        }
-    } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) rs = fmax(rs, fabs(st.g[0][i] - PIp[i]));
-    }
+    const double v[3] = {st.v(0, 0), st.v(0, 1), st.v(0, 2)};
+    kkt_stage(p, k, st.a[0], st.B[0], st.g[0], st.bb[0], v, PIk, PIp, LAMk, rs, rs, rs, re, ri, rc);   // one stationarity maximum
     rs = group_max(rs, c.gs);
     re = group_max(re, c.gs);
     ri = group_max(ri, c.gs);
@@ -1514,9 +1318,10 @@ __device__ __forceinline__ bool qp_outcome(const SolveArgs& A, const Ctx& c, con
 }
 
 // ---- pieces the SQP kernels (qp_step_kernel, sqp_loop_kernel) share as functions.  The fused kernel's
-// bit identity to the per-iteration launches rests on both computing the same: the wave geometry, the
-// linearisation's stage load and dx0 are still written out in both (as functions they change the
-// instructions the compiler emits for these kernels), and must be edited together.
+// bit identity to the per-iteration launches rests on both computing the same.  The linearisation's
+// stage load and dx0 are still written out in both, and the stage load a third time in the twin's
+// load_stage: as one function it costs the SQP kernels up to 15 VGPRs (profiles/ipm_shared/README.md),
+// so the three must be edited together.
 // debug (QSP_FLAG_POISON): this thread's LDS column filled with NaN
 template <int S>
 __device__ __forceinline__ void poison_lds(double* col) {
@@ -1554,18 +1359,7 @@ __global__ void __launch_bounds__(BLOCK, QSP_MIN_WAVES) qp_step_kernel(SolveArgs
     SEG_T(t_k);
     extern __shared__ double smem[];
     const SolveParams& p = A.p;
-    Ctx c;
-    c.lane = threadIdx.x & 63;
-    c.N = p.N;
-    c.L = lanes_per_instance(p.N, S);
-    const int G = WAVE / c.L;
-    c.grp = c.lane / c.L;
-    c.lig = c.lane - c.grp * c.L;
-    c.base = c.grp * c.L;
-    c.gs.init(c.base, c.L);
-    const int wave = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
-    c.inst = wave * G + c.grp;
-    c.real = (c.grp < G) && (c.inst < A.nI);
+    const Ctx c = ctx_of<S>(threadIdx.x & 63, p.N, A.nI);
     // instances are packed into waves in the order of their previous IPM iteration count
     // (sort_by_iters_kernel), so the instances sharing a wave finish together
     const int slot = A.i0 + (c.real ? c.inst : A.nI - 1);
@@ -1940,13 +1734,11 @@ __global__ void __launch_bounds__(64) merit_ls_kernel(SolveArgs A) {
     if (stg) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            const double a = skip ? 0.0 : fabs(w[(Q_PI + q) * tot]), wq = 0.5 * (NUk[q] + a);
-            NUk[q] = a > wq ? a : wq;
+            NUk[q] = merit_weight(NUk[q], skip ? 0.0 : fabs(w[(Q_PI + q) * tot]));
         }
 #pragma unroll
         for (int q = 0; q < 6; ++q) {
-            const double a = skip ? 0.0 : fabs(w[(Q_LAM + q) * tot]), wq = 0.5 * (ETAk[q] + a);
-            ETAk[q] = a > wq ? a : wq;
+            ETAk[q] = merit_weight(ETAk[q], skip ? 0.0 : fabs(w[(Q_LAM + q) * tot]));
         }
     }
     const double* yr = A.yref + ((size_t)iv * N + ku) * 6;
@@ -2008,13 +1800,11 @@ __global__ void __launch_bounds__(64) merit_ls_kernel(SolveArgs A) {
         double* nw = A.wnlp + si;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            const double pk = nw[(W_PI + q) * tot];
-            nw[(W_PI + q) * tot] = qfma(alpha, w[(Q_PI + q) * tot] - pk, pk);
+            nw[(W_PI + q) * tot] = damp_update(alpha, w[(Q_PI + q) * tot], nw[(W_PI + q) * tot]);
         }
 #pragma unroll
         for (int q = 0; q < 6; ++q) {
-            const double lk = nw[(W_LAM + q) * tot];
-            nw[(W_LAM + q) * tot] = qfma(alpha, w[(Q_LAM + q) * tot] - lk, lk);
+            nw[(W_LAM + q) * tot] = damp_update(alpha, w[(Q_LAM + q) * tot], nw[(W_LAM + q) * tot]);
         }
 #pragma unroll
         for (int q = 0; q < 4; ++q) nw[(W_NU + q) * tot] = NUk[q];

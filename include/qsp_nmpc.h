@@ -387,7 +387,21 @@ int qsp_eval_vbound(qsp_solver* s, int32_t n, const int32_t* shape_id, const dou
  * every stage (as in the OCP).  H: nb x (6N+4) diag, g: nb x (6N+4), lo/hi: nb x N x 3,
  * stage-0 s bound as the handle's stage0_s_bound.  qp_status (optional, nb): 0 the stop test
  * was met, 1 non-finite solution, 2 stopped at the iteration cap, 3 infeasible (the fixed
- * stage-0 s = dx0's outside its bounds), 4 stall exit, 5 diverged (mu >= qp_mu_max). */
+ * stage-0 s = dx0's outside its bounds), 4 stall exit, 5 diverged (mu >= qp_mu_max).
+ * A must be the identity except a02, a03, a12, a13, a23, a33 (the pusher-slider structure).
+ * Accuracy (measured against QPs with known exact solutions): with no active
+ * bound or active input bounds only, a status-0 answer is within 4e-9 of the solution at data of
+ * order one (the stop test's truncation, mu_stop 1e-10).  The stop test tracks its residuals as
+ * r0 * prod(1 - alpha) and does not recompute them, so status 0 certifies the point only while the
+ * Newton steps are accurate.  An active STATE bound puts its barrier weight sigma = lam / t ~
+ * lam^2 / mu into the Riccati recursion, which cancels it twice: the u-stationarity of the returned
+ * point is off by ~ 3e-5 eps sigma^2 (B and bound offsets of order one, N = 20; about linear in the
+ * offsets, B's scale to the power 1 .. 2), up to the multipliers' own size.  Domain at mu_stop =
+ * 1e-10: state-bound multipliers lam <~ 1e-2 at such data (du then within 1e-4, mostly truncation);
+ * the OCP's own QPs (B = O(Ts), offsets <= 0.07) sit lower at the same multipliers (u-stationarity
+ * of 1 024 bench lanes' QPs: median 1e-13 .. 3e-7, 99th percentile 2e-3 .. 8e-3).
+ * Beyond it (lam ~ 1: du wrong by up to 1) recompute H_u du + g_u + B' pi - lam_lo + lam_hi from the
+ * returned du, pi, lam before trusting status 0. */
 int qsp_qp_solve(qsp_solver* s, int32_t nb, const double* A, const double* B, const double* b, const double* H,
                  const double* g, const double* lo, const double* hi, const double* dx0, double* dx, double* du,
                  double* pi, double* lam, int32_t* iters, int32_t* qp_status);

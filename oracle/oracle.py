@@ -198,6 +198,29 @@ class Oracle:
                                _p(dx), _p(du), _p(pi), _p(lam), _p(iters), _p(qst))
         return dict(dx=dx, du=du, pi=pi, lam=lam, iters=iters, fail=r, qp_status=qst)
 
+    def qp_ext(self, opts, A, B, b, H, g, lo, hi, act, dx0, precision="quad"):
+        """qp of the LITERAL restatement evaluated in extended precision (orx_qp_batch_l / _q:
+        "long" = long double, "quad" = __float128); double in/out, the same interface as qp."""
+        if self.twin:
+            raise ValueError("extended precision: literal restatement only")
+        N = opts.N
+        nb = A.shape[0]
+        arrs = [np.ascontiguousarray(a, np.float64) for a in (A, B, b, H, g, lo, hi)]
+        act = np.ascontiguousarray(act, np.uint8)
+        dx0 = np.ascontiguousarray(dx0, np.float64)
+        dx = np.zeros((nb, N + 1, 4))
+        du = np.zeros((nb, N, 2))
+        pi = np.zeros((nb, N, 4))
+        lam = np.zeros((nb, N, 6))
+        iters = np.zeros(nb, np.int32)
+        qst = np.zeros(nb, np.int32)
+        fn = {"long": self.L.orx_qp_batch_l, "quad": self.L.orx_qp_batch_q}[precision]
+        r = fn(C.byref(opts), C.c_int32(nb), *[_p(a) for a in arrs], _p(act), _p(dx0),
+               _p(dx), _p(du), _p(pi), _p(lam), _p(iters), _p(qst))
+        if r < 0:
+            raise ValueError("orx_qp_batch: bad arguments")
+        return dict(dx=dx, du=du, pi=pi, lam=lam, iters=iters, fail=r, qp_status=qst)
+
     def ocp_solve(self, opts, x0, yref, yref_e, X=None, U=None, PI=None, shape_id=None, nthreads=0):
         N = opts.N
         x0 = np.ascontiguousarray(x0, np.float64).reshape(-1, 4)

@@ -42,7 +42,8 @@
  * libquadmath) it is the extended-precision oracle: the same formulas evaluated 2^11 / 2^60 times
  * more finely, exported as orx_controller_solve (double in/out, converted at the boundary) to
  * adjudicate the lanes where the kernel-order twin and the double restatement disagree
- * (tests/test_extended_oracle.py). */
+ * (tests/test_extended_oracle.py), and its QP alone as orx_qp_batch
+ * (tests/test_manufactured_qp.py). */
 #if defined(OR_EXT) && OR_EXT == 2
 #include <quadmath.h>
 typedef __float128 real;
@@ -61,7 +62,7 @@ typedef long double real;
 typedef double real;
 #endif
 #ifdef OR_EXT
-#define OR_EXPORT static   /* the extended build exports orx_controller_solve only */
+#define OR_EXPORT static   /* the extended build exports orx_controller_solve and orx_qp_batch only */
 #else
 #define OR_EXPORT
 #endif
@@ -1328,8 +1329,10 @@ OR_EXPORT int or_max_n(void) { return OR_MAX_N; }
  * No model probe, no diagnostics. */
 #if OR_EXT == 2
 #define ORX_NAME orx_controller_solve_q
+#define ORX_QP_NAME orx_qp_batch_q
 #else
 #define ORX_NAME orx_controller_solve_l
+#define ORX_QP_NAME orx_qp_batch_l
 #endif
 static real *to_real(const double *a, size_t n)
 {
@@ -1360,6 +1363,33 @@ int ORX_NAME(const int32_t *n_ctrl, const double *ctrl, const double *knots, con
     from_real(u0, u, nbs * 2);
     from_real(cost, cs, nbs);
     free(c); free(k); free(pr); free(x0); free(tr); free(X); free(U); free(P); free(u); free(cs);
+    return r;
+}
+
+/* orx_qp_batch: or_qp_batch in the extended scalar type, double in/out -- the same IPM and Riccati
+ * recursion on the same QP data (converted exactly), every operation 2^11 / 2^60 times finer; the
+ * stop test and its tolerances are the options' doubles.  It separates a formula error (the extended
+ * answer is wrong too) from the double recursion's rounding (tests/test_manufactured_qp.py). */
+int ORX_QP_NAME(const or_opts *o, int32_t nb, const double *A, const double *B, const double *b,
+                const double *H, const double *g, const double *lo, const double *hi, const uint8_t *act,
+                const double *dx0, double *dx, double *du, double *pi, double *lam, int32_t *iters,
+                int32_t *qp_status)
+{
+    const size_t N = (size_t)o->N, n = (size_t)nb;
+    real *rA = to_real(A, n * N * 16), *rB = to_real(B, n * N * 8), *rb = to_real(b, n * N * 4);
+    real *rH = to_real(H, n * (6 * N + 4)), *rg = to_real(g, n * (6 * N + 4));
+    real *rlo = to_real(lo, n * N * 3), *rhi = to_real(hi, n * N * 3), *rx0 = to_real(dx0, n * 4);
+    real *rdx = (real *)calloc(n * 4 * (N + 1) + 1, sizeof(real)), *rdu = (real *)calloc(n * 2 * N + 1, sizeof(real));
+    real *rpi = (real *)calloc(n * 4 * N + 1, sizeof(real)), *rlam = (real *)calloc(n * 6 * N + 1, sizeof(real));
+    const int r = or_qp_batch(o, nb, rA, rB, rb, rH, rg, rlo, rhi, act, rx0, rdx, rdu, rpi, rlam, iters, qp_status);
+    if (r >= 0) {
+        from_real(dx, rdx, n * 4 * (N + 1));
+        from_real(du, rdu, n * 2 * N);
+        from_real(pi, rpi, n * 4 * N);
+        from_real(lam, rlam, n * 6 * N);
+    }
+    free(rA); free(rB); free(rb); free(rH); free(rg); free(rlo); free(rhi); free(rx0);
+    free(rdx); free(rdu); free(rpi); free(rlam);
     return r;
 }
 #endif

@@ -54,7 +54,15 @@ extern "C" {
 #define QSP_ERR_STATE (-3)
 #define QSP_ERR_IO (-4)
 
-/* per-lane solver status (acados meaning where one exists) */
+/* per-lane solver status (acados meaning where one exists).
+ * Precedence -- non-finite wins: a lane whose returned iterate (X, U, or the x0 it was given, all
+ * four components) holds a NaN or Inf has QSP_STATUS_NAN, whatever its QP did; QSP_STATUS_QP_FAIL
+ * means the returned iterate is finite and a QP was infeasible or diverged (a NaN in y_ref, or a
+ * finite x0 of absurd size, ends there: the iterate stays finite, the cost may not).  sqp_iter
+ * counts the completed iterations either way.  Tested, not promised beyond that: with such lanes in
+ * a batch the other lanes' outputs keep the bits they have without them, at 2 to 5 instances per
+ * wavefront, with the factor scan, the merit kernels, the fused and the per-iteration loop, and on
+ * 8192 lanes with packing and two stream parts (tests/test_gpu_bad_lanes.py). */
 #define QSP_STATUS_SUCCESS 0
 #define QSP_STATUS_NAN 1
 #define QSP_STATUS_MAXITER 2      /* QSP_NLP_SQP_MERIT: tolerances not met within sqp_iters */
@@ -388,6 +396,16 @@ int qsp_eval_vbound(qsp_solver* s, int32_t n, const int32_t* shape_id, const dou
  * stage-0 s bound as the handle's stage0_s_bound.  qp_status (optional, nb): 0 the stop test
  * was met, 1 non-finite solution, 2 stopped at the iteration cap, 3 infeasible (the fixed
  * stage-0 s = dx0's outside its bounds), 4 stall exit, 5 diverged (mu >= qp_mu_max).
+ * Non-finite wins: a lane whose returned dx or du holds a NaN or Inf reports 1 whatever else
+ * happened to it (infeasible, diverged); 3, 5 and the other codes describe finite answers only.
+ * One NaN in a lane's g, A, B, b, lo, hi or dx0 therefore gives that lane 1 and leaves every other
+ * lane's answer as it is without it.
+ * H is one set of weights for the whole call, not per-lane data ("equal on every stage"): the ten
+ * entries that are read as weights are lane 0's stage-0 entries H[0 .. 5] and lane 0's terminal
+ * entries H[6 N .. 6 N + 3]; the kernels run with these (the handle's own cost weights are not
+ * consulted).  Every other entry of every lane is only compared with them, and a differing one --
+ * a NaN differs, also from itself, so a NaN in the ten entries too -- fails the whole call with
+ * QSP_ERR_ARG before any lane is solved.  H can therefore not make a single lane non-finite.
  * A must be the identity except a02, a03, a12, a13, a23, a33 (the pusher-slider structure).
  * Accuracy (measured against QPs with known exact solutions): with no active
  * bound or active input bounds only, a status-0 answer is within 4e-9 of the solution at data of

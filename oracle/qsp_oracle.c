@@ -724,12 +724,23 @@ static real merit_eval(const or_shape *sh, const or_opts *o, const real *X, cons
     return phi;
 }
 
+/* Non-finite wins (the status rule, include/qsp_nmpc.h): a returned iterate -- X, U, or the x0 it
+ * was given -- with a NaN or Inf in it is status 1 whatever the QP did; 4 is for finite iterates. */
+static int iterate_finite(int N, const real x0[4], const real *X, const real *U)
+{
+    for (int q = 0; q < 4; ++q) if (!isfinite(x0[q])) return 0;
+    for (int q = 0; q < 4 * (N + 1); ++q) if (!isfinite(X[q])) return 0;
+    for (int q = 0; q < 2 * N; ++q) if (!isfinite(U[q])) return 0;
+    return 1;
+}
+
 /* SQP from the initial guess (X,U,PI) in place.
  *   nlp_mode 0: K full Gauss-Newton steps (the BASELINE "SQP-RTI, K iterations" metric).
  *   nlp_mode 1: acados-style SQP: KKT residual check against tol_* before each QP,
  *               merit backtracking with sufficient descent (alpha *= ls_alpha_red down
  *               to ls_alpha_min), damped multiplier update, at most sqp_iters QPs.
- * Returns status: 0 ok/converged, 1 NaN/Inf, 2 max iterations (mode 1). */
+ * Returns status: 0 ok/converged, 1 NaN/Inf in the returned iterate or x0 (wins over 4), 2 max
+ * iterations (mode 1), 4 infeasible or diverged QP on a finite iterate. */
 static int sqp_solve(const or_shape *sh, const or_opts *o, const real x0[4],
                      const real *yref, const real *yref_e,
                      real *X, real *U, real *PI, real *lam_out, int32_t *iters, or_ws *ws)
@@ -752,11 +763,12 @@ static int sqp_solve(const or_shape *sh, const or_opts *o, const real x0[4],
     ws->kkt[20] = 1e300;
     if (o->nlp_mode == 1) status = 2;
     /* stage-0 s bound: s_0 = x0's s is fixed in every QP; outside [lh_s, uh_s] all of them are
-     * infeasible and the solve stops before its first iteration (status 4, ACADOS_QP_FAILURE) */
+     * infeasible and the solve stops before its first iteration (status 4, ACADOS_QP_FAILURE; status 1
+     * where x0 -- a NaN s fails the test too -- or the initial guess is not finite: non-finite wins) */
     if (o->stage0_s_bound && !(x0[3] >= o->lh[0] && x0[3] <= o->uh[0])) {
         if (iters) *iters = 0;
         if (lam_out) memset(lam_out, 0, sizeof(real) * 6 * N);
-        return 4;
+        return iterate_finite(N, x0, X, U) ? 4 : 1;
     }
     for (it = 0; it < o->sqp_iters; ++it) {
         ws->kkt[16] = 0.0;
@@ -922,8 +934,7 @@ static int sqp_solve(const or_shape *sh, const or_opts *o, const real x0[4],
     }
     if (iters) *iters = it;
     if (lam_out) memcpy(lam_out, LAM, sizeof(real) * 6 * N);
-    for (int q = 0; q < 4 * (N + 1); ++q) if (!isfinite(X[q])) status = 1;
-    for (int q = 0; q < 2 * N; ++q) if (!isfinite(U[q])) status = 1;
+    if (!iterate_finite(N, x0, X, U)) status = 1;
     return status;
 }
 
@@ -1015,7 +1026,12 @@ OR_EXPORT int or_qp_batch(const or_opts *o, int32_t nb, const real *A, const rea
             memcpy(qp.dx0, dx0 + 4 * i, sizeof qp.dx0);
             or_qp_sol sol = {dx + (size_t)i * 4 * (N + 1), du + (size_t)i * 2 * N, pi + (size_t)i * 4 * N,
                              lam + (size_t)i * 6 * N, ws->t};
-            const int st = qp_solve(&qp, o, &sol, &ws->F, ws->work, iters ? iters + i : NULL);
+            int st = qp_solve(&qp, o, &sol, &ws->F, ws->work, iters ? iters + i : NULL);
+            /* non-finite wins at this level too (qsp_qp_solve): an infeasible or diverged QP whose
+             * returned dx or du is non-finite reports 1.  (qp_solve itself keeps 3 and 5 first: the
+             * SQP needs them to tell a QP failure on a finite iterate, status 4, from a breakdown.) */
+            for (int q = 0; q < 4 * (N + 1); ++q) if (!isfinite(sol.dx[q])) st = 1;
+            for (int q = 0; q < 2 * N; ++q) if (!isfinite(sol.du[q])) st = 1;
             if (qp_status) qp_status[i] = st;
             if (st == 1) {
                 #pragma omp atomic write

@@ -877,9 +877,12 @@ static void sqp_solve(const tw_par *p, const ShapeDev *sh, tw_ws *w, const doubl
     int bad = 0;
     for (int q = 0; q < 4 * (N + 1); ++q) bad |= !isfinite(X[q]);
     for (int q = 0; q < 2 * N; ++q) bad |= !isfinite(U[q]);
-    if (wdone == 3 || wdone == 4) o->status = 4;
-    else if (p->nlp_mode == 1) o->status = (bad || wdone == 2) ? 1 : (wdone == 1 ? 0 : 2);
-    else o->status = (bad || wdone == 2) ? 1 : 0;
+    for (int q = 0; q < 4; ++q) bad |= !isfinite(x0[q]);
+    /* non-finite wins (qsp_nmpc.h, QSP_STATUS_*) */
+    if (bad || wdone == 2) o->status = 1;
+    else if (wdone == 3 || wdone == 4) o->status = 4;
+    else if (p->nlp_mode == 1) o->status = wdone == 1 ? 0 : 2;
+    else o->status = 0;
     if (wdone == 0) o->sqp_iter = p->sqp_iters;
     if (p->nlp_mode == 1) {
         for (int k = 0; k < N; ++k) {

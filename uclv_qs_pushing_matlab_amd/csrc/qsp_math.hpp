@@ -93,6 +93,10 @@ QSP_FN double smod_model(double s, double b) {
 }
 
 // MATLAB floor-mod  mod(a,b) = a - floor(a/b)*b   (NMPC_controller.m:320,332)
+// Domain: |a / b| < 2^53.  Beyond it the quotient is an integer-valued double whose rounding error
+// exceeds one, so the result leaves [0, b) (s = 1e300: of the order of ulp(a / b) b, not of b); a NaN
+// or Inf gives NaN.  The result is a state component or an argument of spline_eval, which clamps
+// its span guess: a wrong value, never an index.
 QSP_FN double mat_mod(double a, double b) {
     const double r = qfma(-floor(a / b), b, a);
     return (r == b) ? 0.0 : r;

@@ -1172,8 +1172,9 @@ __device__ __forceinline__ void nlp_init(const SolveArgs& A, int i, bool use_pi)
 }
 
 // An instance whose s_0 makes every QP infeasible (s0_infeasible, qsp_ipm.hpp) does not iterate
-// (wdone = 3: status QSP_STATUS_QP_FAIL, sqp_iter 0, the initial guess returned), as the oracle's
-// sqp_solve.  (Called after nlp_init, which clears wdone.)
+// (wdone = 3: status QSP_STATUS_QP_FAIL -- QSP_STATUS_NAN where s_0 or the rest of the iterate is not
+// finite, epilogue_kernel --, sqp_iter 0, the initial guess returned), as the oracle's sqp_solve.
+// (Called after nlp_init, which clears wdone.)
 __device__ __forceinline__ void s0_feasible(const SolveArgs& A, int i, double s0) {
     if (A.wdone && s0_infeasible(A.p, s0)) {
         A.wdone[i] = 3;
@@ -1835,12 +1836,15 @@ __global__ void epilogue_kernel(SolveArgs A) {
     for (int q = 0; q < 4; ++q) { const double r = X[4 * N + q] - ye[q]; s = qfma(p.We[q] * r, r, s); bad |= !isfinite(X[4 * N + q]); }
     cost = qfma(0.5, s, cost);
     A.cost[i] = cost;
+    for (int q = 0; q < 4; ++q) bad |= !isfinite(A.wx0[(size_t)i * 4 + q]);   // x0 is part of the returned iterate
     // wdone: 1 converged, 2 non-finite QP solution, 3 infeasible stage-0 bound, 4 diverged QP
-    // (sqp_iter written then)
+    // (sqp_iter written then).  Non-finite wins (qsp_nmpc.h, QSP_STATUS_*): a non-finite iterate is
+    // QSP_STATUS_NAN whatever its QP did; a failed QP is QSP_STATUS_QP_FAIL only on a finite iterate.
     const int fr = A.wdone ? A.wdone[i] : 0;
-    if (fr == 3 || fr == 4) A.status[i] = QSP_STATUS_QP_FAIL;
-    else if (p.nlp_mode == 1) A.status[i] = (bad || fr == 2) ? 1 : (fr == 1 ? 0 : 2);
-    else A.status[i] = (bad || fr == 2) ? 1 : 0;
+    if (bad || fr == 2) A.status[i] = QSP_STATUS_NAN;
+    else if (fr == 3 || fr == 4) A.status[i] = QSP_STATUS_QP_FAIL;
+    else if (p.nlp_mode == 1) A.status[i] = fr == 1 ? 0 : 2;
+    else A.status[i] = 0;
     if (fr == 0) A.sqp_iter[i] = p.sqp_iters;
     A.u0[(size_t)i * 2] = U[0];
     A.u0[(size_t)i * 2 + 1] = U[1];

@@ -39,14 +39,15 @@ extern "C" {
 #define QSP_NY_E 4
 #define QSP_NH 3          /* h = [s; u_n; u_t]      (NMPC_controller.m:237) */
 #define QSP_MAX_CTRL 64   /* spline control points per shape */
-#define QSP_ABI_VERSION 8 /* 2: struct_size fields, qp_mu_max, qsp_get_qp_stalled, QP-failure exits;
+#define QSP_ABI_VERSION 9 /* 2: struct_size fields, qp_mu_max, qsp_get_qp_stalled, QP-failure exits;
                              3: qsp_options.factor_scan; 4: qsp_get_factor_walk;
                              5: qsp_rollout_cost, qsp_rollout_cost_device, qsp_cost_landscape;
                              6: qsp_eval_modes, qsp_get_modes, qsp_open_loop, qsp_open_loop_device;
                              7: qsp_set_plant_shapes, qsp_set_plant_shape_ids, qsp_set_plant_params,
                                 qsp_clear_plant, qsp_get_plant, qsp_closed_loop_metrics;
                              8: qsp_default_sim_noise, qsp_set_sim_noise, qsp_clear_sim_noise, qsp_get_sim_noise,
-                                qsp_gen_sim_noise */
+                                qsp_gen_sim_noise;
+                             9: qsp_default_waypoint_opts, qsp_gen_waypoints */
 
 #define QSP_OK 0
 #define QSP_ERR_ARG (-1)
@@ -248,6 +249,50 @@ int qsp_set_reference_trajectories(qsp_solver* s, const double* traj /* B x T x 
  * Installs the tables as with qsp_set_reference_trajectories; T_out (optional) = samples. */
 int qsp_gen_straight_lines(qsp_solver* s, const double* x0, const double* xf, double t0, double tf,
                            int32_t auto_angle, int32_t* T_out);
+/* per-lane waypoint paths generated on the device: TrajectoryGenerator.waypoints_gen
+ * (TrajectoryGenerator.m:96-143) and waypoint_gen_fixed_angle (:81-95), one polyline of n_wp[i] waypoints
+ * per lane.  The one deviation from the reference is trajectory.py's: MATLAB's waypointTrajectory (:121) is
+ * replaced by the constant-speed polyline through the waypoints, exact for two waypoints (main.m:150-164).
+ * Rows [x y yaw s_ref 0 0]; the table is B x T x 6 with T = max_i T_i, and a lane with T_i < T repeats its
+ * last row up to T, which is what get_y_ref's clamp at the end reads anyway (NMPC_controller.m:307-313).
+ * Time laws, with len_k = sqrt(dx*dx + dy*dy) and d_k = len_k / vel_k of segment k:
+ *   QSP_WP_LAW_CONSTANT_SPEED    arrival times t_0 = 0, t_{k+1} = t_k + d_k; T_i = floor(t_end/Ts + 1e-9) + 1
+ *                                samples at t = j*Ts (the colon rule of qsp_gen_straight_lines); sample j lies
+ *                                on the last segment k with t_k <= t (capped at the last one) at
+ *                                wp_k + a*(wp_{k+1} - wp_k), a = (t - t_k)/(t_{k+1} - t_k)
+ *   QSP_WP_LAW_SEGMENT_LINSPACE  row 0 is wp_0; segment k adds n_k = floor(d_k/Ts + 1e-9) rows, the count of
+ *                                (a+Ts):Ts:(a+d_k) (:88), which are linspace(wp_k, wp_{k+1}, n_k) (:90-91):
+ *                                wp_k + m*((wp_{k+1} - wp_k)/(n_k - 1)), the last one (and the only one of
+ *                                n_k = 1) wp_{k+1} itself; n_k = 0 adds none.  T_i = 1 + sum n_k
+ * Yaw of a row: the heading h_k = atan2(dy, dx) of its segment (row 0 of the linspace law: segment 0's),
+ * raw, or unwrapped along the path (y_0 = h_0, y_k = y_{k-1} + d with d = h_k - h_{k-1} reduced by
+ * 2 pi rint(d / (2 pi))), or theta[i] on every row (x0(3) of :86,92).
+ * QSP_ERR_ARG, with the installed table left as it is: struct_size, law or yaw out of range; K outside
+ * 2..QSP_MAX_WAYPOINTS; an n_wp outside 2..K; a waypoint, theta or s_ref that is not finite; a vel that is
+ * not finite and > 0; under constant speed two consecutive waypoints that are equal (or so close that the
+ * arrival time does not advance); QSP_WP_YAW_FIXED without theta; a segment duration that overflows; a path
+ * of more than 2^24 samples.
+ * Installs the tables as with qsp_set_reference_trajectories.  All arrays are host arrays. */
+#define QSP_MAX_WAYPOINTS 16
+#define QSP_WP_LAW_CONSTANT_SPEED 0   /* waypoints_gen, TrajectoryGenerator.m:96-143, as trajectory.py restates it */
+#define QSP_WP_LAW_SEGMENT_LINSPACE 1 /* waypoint_gen_fixed_angle, :81-95 */
+#define QSP_WP_YAW_HEADING 0          /* atan2 of the segment, raw */
+#define QSP_WP_YAW_HEADING_UNWRAPPED 1
+#define QSP_WP_YAW_FIXED 2            /* theta[i] on every row (x0(3) of :86,92) */
+typedef struct {
+    int32_t struct_size;      /* sizeof(qsp_waypoint_opts) (qsp_default_waypoint_opts sets it; checked as qsp_options') */
+    int32_t law;              /* QSP_WP_LAW_* */
+    int32_t yaw;              /* QSP_WP_YAW_* */
+    int32_t pad_;
+} qsp_waypoint_opts;
+void qsp_default_waypoint_opts(qsp_waypoint_opts* opts);   /* constant speed, heading */
+int qsp_gen_waypoints(qsp_solver* s, const qsp_waypoint_opts* opts, int32_t K,
+                      const double* wp      /* B x K x 2; lane i reads its first n_wp[i] rows */,
+                      const int32_t* n_wp   /* B, 2..K; NULL: K everywhere */,
+                      const double* vel     /* B x (K-1), per segment */,
+                      const double* theta   /* B, QSP_WP_YAW_FIXED only, else NULL */,
+                      const double* s_ref   /* B or NULL (0): column 3 of every row, traj row 4 of :92,:140 */,
+                      int32_t* T_out /* or NULL */, int32_t* T_lane /* B or NULL */);
 /* copy of the installed table(s): T x 6 (shared) or B x T x 6 (per lane) */
 int qsp_get_reference_trajectories(qsp_solver* s, double* traj);
 /* x0: B x 4, index_time: B (1-based, as MATLAB).  Warm start lives on the device and is

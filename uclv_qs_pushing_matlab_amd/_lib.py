@@ -12,7 +12,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 # QSP_LIB_PATH: developer override (A/B runs of differently compiled libraries)
 LIB_PATH = os.environ.get("QSP_LIB_PATH") or os.path.join(_PKG, "libqsp_nmpc.so")
 MAX_CTRL = 64
-ABI_VERSION = 8   # include/qsp_nmpc.h QSP_ABI_VERSION
+ABI_VERSION = 9   # include/qsp_nmpc.h QSP_ABI_VERSION
 
 _lib = None
 
@@ -91,6 +91,14 @@ class SimNoise(C.Structure):
                 ("lane_offset", C.c_int64), ("sigma", C.c_double * 4), ("lane_scale", C.c_void_p)]
 
 
+class WaypointOpts(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("law", C.c_int32), ("yaw", C.c_int32), ("pad_", C.c_int32)]
+
+
+WP_LAWS = {"constant_speed": 0, "segment_linspace": 1}            # QSP_WP_LAW_*
+WP_YAWS = {"heading": 0, "heading_unwrapped": 1, "fixed": 2}      # QSP_WP_YAW_*
+MAX_WAYPOINTS = 16                                                # QSP_MAX_WAYPOINTS
+
 _P = C.c_void_p
 _I = C.c_int32
 _D = C.c_double
@@ -136,6 +144,8 @@ _SIGS = {
     "qsp_set_reference_trajectory": [_P, _P, _I],
     "qsp_set_reference_trajectories": [_P, _P, _I],
     "qsp_gen_straight_lines": [_P, _P, _P, _D, _D, _I, C.POINTER(_I)],
+    "qsp_default_waypoint_opts": [C.POINTER(WaypointOpts)],
+    "qsp_gen_waypoints": [_P, C.POINTER(WaypointOpts), _I, _P, _P, _P, _P, _P, C.POINTER(_I), _P],
     "qsp_get_reference_trajectories": [_P, _P],
     "qsp_controller_solve": [_P, _P, _P],
     "qsp_controller_reset": [_P],
@@ -180,7 +190,8 @@ _SIGS = {
     "qsp_gen_sim_noise": [_P, _I, _P],
     "qsp_last_error": [],
 }
-_VOID = {"qsp_default_options", "qsp_default_rollout_opts", "qsp_default_open_loop_opts", "qsp_default_sim_noise"}
+_VOID = {"qsp_default_options", "qsp_default_rollout_opts", "qsp_default_open_loop_opts", "qsp_default_sim_noise",
+         "qsp_default_waypoint_opts"}
 EXPORTED = tuple(_SIGS)
 
 

@@ -845,6 +845,112 @@ int qsp_gen_straight_lines(qsp_solver* s, const double* x0, const double* xf, do
     return QSP_OK;
 }
 
+void qsp_default_waypoint_opts(qsp_waypoint_opts* o) {
+    std::memset(o, 0, sizeof(*o));
+    o->struct_size = (int32_t)sizeof(qsp_waypoint_opts);
+    o->law = QSP_WP_LAW_CONSTANT_SPEED;
+    o->yaw = QSP_WP_YAW_HEADING;
+}
+
+// TrajectoryGenerator.waypoints_gen / waypoint_gen_fixed_angle per lane.  Everything that is O(B K) happens
+// here, validation first, in plain IEEE operations (the library is built with -ffp-contract=off): segment
+// durations, arrival times or row counts, the yaw of each segment, the lanes' row counts.  waypoints_kernel
+// fills the B x T rows from that.
+int qsp_gen_waypoints(qsp_solver* s, const qsp_waypoint_opts* o, int32_t K, const double* wp, const int32_t* n_wp,
+                      const double* vel, const double* theta, const double* s_ref, int32_t* T_out, int32_t* T_lane) {
+    const std::string w("qsp_gen_waypoints");
+    if (!s || !o || !wp || !vel) return fail(QSP_ERR_ARG, w + ": null argument");
+    if (o->struct_size != (int32_t)sizeof(qsp_waypoint_opts))
+        return fail(QSP_ERR_ARG, w + ": qsp_waypoint_opts.struct_size != sizeof(qsp_waypoint_opts) (stale layout?)");
+    if (o->law != QSP_WP_LAW_CONSTANT_SPEED && o->law != QSP_WP_LAW_SEGMENT_LINSPACE)
+        return fail(QSP_ERR_ARG, w + ": unknown law");
+    if (o->yaw < QSP_WP_YAW_HEADING || o->yaw > QSP_WP_YAW_FIXED) return fail(QSP_ERR_ARG, w + ": unknown yaw");
+    if (K < 2 || K > QSP_MAX_WAYPOINTS) return fail(QSP_ERR_ARG, w + ": K outside 2..QSP_MAX_WAYPOINTS");
+    if (o->yaw == QSP_WP_YAW_FIXED && !theta) return fail(QSP_ERR_ARG, w + ": QSP_WP_YAW_FIXED needs theta");
+    const size_t B = s->o.batch, Ks = (size_t)K;
+    const double Ts = s->o.Ts, two_pi = 2.0 * M_PI;
+    const double max_rows = 16777216.0;   // 2^24 samples per lane: every count below is an exact int32
+    std::vector<int32_t> nw(B), brk(B * Ks, 0), Tl(B);
+    std::vector<double> knot(B * Ks, 0.0), yaw(B * Ks, 0.0);
+    int32_t T = 1;
+    for (size_t i = 0; i < B; ++i) {
+        const int32_t n = n_wp ? n_wp[i] : K;
+        if (n < 2 || n > K) return fail(QSP_ERR_ARG, w + ": n_wp outside 2..K");
+        nw[i] = n;
+        const double* p = wp + i * Ks * 2;
+        for (int32_t k = 0; k < 2 * n; ++k)
+            if (!std::isfinite(p[k])) return fail(QSP_ERR_ARG, w + ": waypoint not finite");
+        if (o->yaw == QSP_WP_YAW_FIXED && !std::isfinite(theta[i])) return fail(QSP_ERR_ARG, w + ": theta not finite");
+        if (s_ref && !std::isfinite(s_ref[i])) return fail(QSP_ERR_ARG, w + ": s_ref not finite");
+        double* tk = knot.data() + i * Ks;
+        double* yk = yaw.data() + i * Ks;
+        int32_t* ck = brk.data() + i * Ks;
+        double h_prev = 0.0;
+        for (int32_t k = 0; k + 1 < n; ++k) {
+            const double v = vel[i * (Ks - 1) + k];
+            if (!(std::isfinite(v) && v > 0.0)) return fail(QSP_ERR_ARG, w + ": vel must be finite and > 0");
+            const double dx = p[2 * k + 2] - p[2 * k], dy = p[2 * k + 3] - p[2 * k + 1];
+            const double d = std::sqrt(dx * dx + dy * dy) / v;
+            if (!std::isfinite(d)) return fail(QSP_ERR_ARG, w + ": segment duration not finite");
+            if (o->law == QSP_WP_LAW_CONSTANT_SPEED) {
+                if (dx == 0.0 && dy == 0.0)
+                    return fail(QSP_ERR_ARG, w + ": two consecutive waypoints are equal (constant speed)");
+                tk[k + 1] = tk[k] + d;
+                if (!(tk[k + 1] > tk[k]))
+                    return fail(QSP_ERR_ARG, w + ": a segment too short for its arrival time to advance");
+                if (!(tk[k + 1] / Ts < max_rows)) return fail(QSP_ERR_ARG, w + ": more than 2^24 samples");
+            } else {
+                const double rows = std::floor(d / Ts + 1e-9);   // the count of (a+Ts):Ts:(a+d)
+                if (!(rows + (double)ck[k] < max_rows)) return fail(QSP_ERR_ARG, w + ": more than 2^24 samples");
+                ck[k + 1] = ck[k] + (int32_t)rows;
+            }
+            const double h = std::atan2(dy, dx);
+            if (o->yaw == QSP_WP_YAW_FIXED) {
+                yk[k] = theta[i];
+            } else if (o->yaw == QSP_WP_YAW_HEADING || k == 0) {
+                yk[k] = h;
+            } else {
+                double dl = h - h_prev;
+                dl -= two_pi * std::rint(dl / two_pi);
+                yk[k] = yk[k - 1] + dl;
+            }
+            h_prev = h;
+        }
+        // MATLAB 0:Ts:t_end, as qsp_gen_straight_lines counts; the linspace law: row 0 and every segment's rows
+        Tl[i] = o->law == QSP_WP_LAW_CONSTANT_SPEED ? (int32_t)std::floor(tk[n - 1] / Ts + 1e-9) + 1 : 1 + ck[n - 1];
+        T = Tl[i] > T ? Tl[i] : T;
+    }
+    HIPCHK(hipSetDevice(s->o.device));
+    Staging st(s);
+    WaypointArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.B = (int32_t)B;
+    a.T = T;
+    a.K = K;
+    a.law = o->law;
+    a.Ts = Ts;
+    a.wp = st.in(wp, B * Ks * 2);
+    a.n_wp = st.in(nw.data(), B);
+    a.knot = st.in(knot.data(), B * Ks);
+    a.brk = st.in(brk.data(), B * Ks);
+    a.yaw = st.in(yaw.data(), B * Ks);
+    a.s_ref = st.in(s_ref, B);
+    a.T_lane = st.in(Tl.data(), B);
+    if (st.err) return st.err;
+    const hipError_t grown = s->traj.ensure(s->dim.traj_lanes(T));
+    if (grown != hipSuccess) s->have_traj = false;   // a failed growth has freed the table that was installed
+    HIPCHK(grown);
+    a.traj = s->traj.data();
+    HIPCHK(launch_waypoints(a, s->stream));
+    if (st.finish()) return st.err;
+    s->T = T;
+    s->have_traj = true;
+    s->traj_per_lane = true;
+    if (T_out) *T_out = T;
+    if (T_lane) std::memcpy(T_lane, Tl.data(), B * sizeof(int32_t));
+    return QSP_OK;
+}
+
 int qsp_get_reference_trajectories(qsp_solver* s, double* traj) {
     if (!s || !traj) return fail(QSP_ERR_ARG, "qsp_get_reference_trajectories: null argument");
     if (!s->have_traj) return fail(QSP_ERR_STATE, "qsp_get_reference_trajectories: no reference trajectory");

@@ -176,6 +176,21 @@ hipError_t launch_reproject(const ShapeDev* shapes, int n_shapes, const int32_t*
                             const double* py, const double* s0, double* s, hipStream_t stream);
 hipError_t launch_straight_lines(int B, int T, const double* x0, const double* xf, double t0, double tf, double Ts,
                                  int auto_angle, double* traj, hipStream_t stream);
+// Waypoint paths per lane (qsp_gen_waypoints): what the host prepared, O(B K), for the fill of B x T rows.
+struct WaypointArgs {
+    int32_t B, T, K;           // lanes, rows of the table (max T_lane), waypoint slots per lane
+    int32_t law;               // QSP_WP_LAW_*
+    double Ts;
+    const double* wp;          // B x K x 2
+    const int32_t* n_wp;       // B waypoints in use, 2..K
+    const double* knot;        // B x K   constant speed: arrival time of waypoint k (strictly increasing)
+    const int32_t* brk;        // B x K   segment linspace: rows before segment k's first, after row 0
+    const double* yaw;         // B x K   yaw of segment k's rows (K - 1 used)
+    const double* s_ref;       // B or nullptr (0)
+    const int32_t* T_lane;     // B rows of lane i, 1..T; rows T_lane..T-1 repeat row T_lane - 1
+    double* traj;              // B x T x 6
+};
+hipError_t launch_waypoints(const WaypointArgs& a, hipStream_t stream);
 // y_ref, y_ref_e of the controller step at index_time + offset, from the T x 6 (per_lane: B x T x 6) table
 hipError_t launch_stage_yref(const double* traj, int T, int per_lane, const int32_t* index_time, int offset, int D,
                              int B, int N, double* yref, double* yref_e, hipStream_t stream);

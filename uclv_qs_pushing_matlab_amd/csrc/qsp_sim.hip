@@ -7,6 +7,8 @@
 //   sim_noise_kernel                       the table of sim_noise that the loops draw with the handle's
 //                                          generator (qsp_noise.hpp);
 //   straight_lines_kernel                  TrajectoryGenerator.straight_line per lane;
+//   waypoints_kernel                       TrajectoryGenerator.waypoints_gen / waypoint_gen_fixed_angle
+//                                          per lane;
 //   stage_yref_kernel                      get_y_ref: a controller step's references out of the table;
 //   spline_, dynamics_, rk4_, vbound_kernel  one device function each (qsp_math.hpp), for the tests and
 //                                          the oracle comparison.
@@ -255,6 +257,58 @@ hipError_t launch_straight_lines(int B, int T, const double* x0, const double* x
     const size_t n = (size_t)B * T;
     hipLaunchKernelGGL(straight_lines_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, B, T, x0, xf,
                        t0, tf, Ts, auto_angle, traj);
+    return hipGetLastError();
+}
+
+// TrajectoryGenerator.waypoints_gen (TrajectoryGenerator.m:96-143, the constant-speed polyline that
+// trajectory.py restates) and waypoint_gen_fixed_angle (:81-95), one thread per (lane, sample) from the
+// lane's waypoints and what qsp_gen_waypoints prepared of them: arrival times or row counts, the yaw of
+// each segment, the lane's own row count T_i.  Rows [x y yaw s_ref 0 0]; a sample past the lane's last is
+// the last one again.  Plain quotients, products and sums (no qfma), so that numpy restates every row bit
+// for bit.
+__global__ void waypoints_kernel(WaypointArgs a) {
+    const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= (size_t)a.B * a.T) return;
+    const int i = (int)(g / a.T), Ti = a.T_lane[i];
+    int j = (int)(g - (size_t)i * a.T);
+    j = j < Ti ? j : Ti - 1;
+    const int last = a.n_wp[i] - 2;   // the last segment
+    const double* wp = a.wp + (size_t)i * a.K * 2;
+    int k = 0;
+    double x = wp[0], y = wp[1];      // row 0 of the linspace law
+    if (a.law == QSP_WP_LAW_CONSTANT_SPEED) {
+        const double* tk = a.knot + (size_t)i * a.K;
+        const double t = (double)j * a.Ts;
+        while (k < last && tk[k + 1] <= t) ++k;   // the last segment that has begun
+        const double al = (t - tk[k]) / (tk[k + 1] - tk[k]);
+        x = wp[2 * k] + al * (wp[2 * k + 2] - wp[2 * k]);
+        y = wp[2 * k + 1] + al * (wp[2 * k + 3] - wp[2 * k + 1]);
+    } else if (j > 0) {
+        const int32_t* c = a.brk + (size_t)i * a.K;
+        const int r = j - 1;                      // c[k] <= r < c[k + 1]: row m of segment k's n
+        while (k < last && c[k + 1] <= r) ++k;
+        const int m = r - c[k], n = c[k + 1] - c[k];
+        if (m == n - 1) {                         // linspace ends on the waypoint itself
+            x = wp[2 * k + 2];
+            y = wp[2 * k + 3];
+        } else {
+            x = wp[2 * k] + (double)m * ((wp[2 * k + 2] - wp[2 * k]) / (double)(n - 1));
+            y = wp[2 * k + 1] + (double)m * ((wp[2 * k + 3] - wp[2 * k + 1]) / (double)(n - 1));
+        }
+    }
+    double* out = a.traj + g * 6;
+    out[0] = x;
+    out[1] = y;
+    out[2] = a.yaw[(size_t)i * a.K + k];
+    out[3] = a.s_ref ? a.s_ref[i] : 0.0;
+    out[4] = 0.0;
+    out[5] = 0.0;
+}
+
+hipError_t launch_waypoints(const WaypointArgs& a, hipStream_t stream) {
+    const long long n = (long long)a.B * a.T, blocks = (n + 255) / 256;
+    if (a.B < 1 || a.T < 1 || a.K < 2 || blocks > 0x7fffffffll) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(waypoints_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, a);
     return hipGetLastError();
 }
 

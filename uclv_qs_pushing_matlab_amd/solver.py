@@ -529,6 +529,38 @@ class OcpSolver:
         self._traj_shape = (self.B, T.value, 6)
         return T.value
 
+    def gen_waypoints(self, wp, vel, n_wp=None, law="constant_speed", yaw="heading", theta=None, s_ref=None):
+        """Device-generated waypoint paths per lane (qsp_gen_waypoints): TrajectoryGenerator.waypoints_gen
+        (law "constant_speed") or waypoint_gen_fixed_angle ("segment_linspace").  wp (B, K, 2) or (K, 2); vel a
+        scalar, (K-1,) or (B, K-1), per segment; n_wp (B,) waypoints in use per lane (None: K); yaw "heading",
+        "heading_unwrapped" or "fixed" (then theta, a scalar or (B,)); s_ref a scalar or (B,): column 3 of every
+        row (None: 0).  Installs the (B, T, 6) tables; returns (T, T_lane): a lane with T_lane < T repeats its
+        last row."""
+        if law not in _lib.WP_LAWS or yaw not in _lib.WP_YAWS:
+            raise ValueError(f"law must be one of {sorted(_lib.WP_LAWS)} and yaw one of {sorted(_lib.WP_YAWS)}")
+        w = np.asarray(wp, np.float64)
+        if w.ndim == 2:
+            w = np.broadcast_to(w, (self.B,) + w.shape)
+        if w.ndim != 3 or w.shape[0] != self.B or w.shape[2] != 2:
+            raise ValueError(f"wp must be (B={self.B}, K, 2) or (K, 2), got {w.shape}")
+        K = w.shape[1]
+        w = f64(w)
+        v = f64(np.broadcast_to(np.asarray(vel, np.float64), (self.B, max(K - 1, 1))))
+
+        def lanes(a, dtype):
+            return None if a is None else np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype), (self.B,)))
+
+        n, th, sr = lanes(n_wp, np.int32), lanes(theta, np.float64), lanes(s_ref, np.float64)
+        o = _lib.WaypointOpts()
+        self._L.qsp_default_waypoint_opts(C.byref(o))
+        o.law, o.yaw = _lib.WP_LAWS[law], _lib.WP_YAWS[yaw]
+        T = C.c_int32()
+        Tl = np.zeros(self.B, np.int32)
+        check(self._L.qsp_gen_waypoints(self._h, C.byref(o), K, ptr(w), ptr(n), ptr(v), ptr(th), ptr(sr), C.byref(T),
+                                        ptr(Tl)), "qsp_gen_waypoints")
+        self._traj_shape = (self.B, T.value, 6)
+        return T.value, Tl
+
     def get_reference_trajectories(self):
         out = np.zeros(self._traj_shape)
         check(self._L.qsp_get_reference_trajectories(self._h, ptr(out)), "qsp_get_reference_trajectories")

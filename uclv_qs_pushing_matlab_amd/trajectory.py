@@ -5,6 +5,8 @@ uses MATLAB's Navigation Toolbox `waypointTrajectory` (not reproducible bit-exac
 here it is the constant-speed piecewise-linear path through the waypoints with the
 segment heading as yaw, sampled at the controller rate — exact for the two-waypoint
 straight line of main.m:150-164 (config 1).  Rows: [x; y; yaw; s0; 0] (:140).
+waypoint_gen_fixed_angle (:81-95) is fully specified and reproduced.  OcpSolver.gen_waypoints
+generates both per lane on the device.
 """
 import numpy as np
 
@@ -46,6 +48,30 @@ class TrajectoryGenerator:
                 ang[j] = self.x0[2] + s * da / abs(da)
             ang[len(time_angle) - 1:] = ang[len(time_angle) - 1]
             traj = np.vstack([traj[:2], ang[None], traj[3:]])
+        return time, traj
+
+    def waypoint_gen_fixed_angle(self):
+        """waypoint_gen_fixed_angle (:81-95): row 0 is the first waypoint; segment i adds the samples of
+        (time(end)+Ts):Ts:(time(end)+times(i)), floor(times(i)/Ts + 1e-9) of them, as linspace between its two
+        waypoints (MATLAB's linspace of one point is the end point); theta and s are x0(3:4) on every row.
+        Returns time, traj (5 x T)."""
+        wp = np.asarray(self.waypoints_, np.float64)
+        vel = np.broadcast_to(np.asarray(self.waypoints_velocities, np.float64).ravel(), (len(wp) - 1,))
+        d = np.diff(wp[:, :2], axis=0)
+        times = np.sqrt(d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) / vel
+        x0 = self.x0 if hasattr(self, "x0") and len(self.x0) > 3 else np.zeros(4)
+        time = [np.zeros(1)]
+        xy = [wp[:1, :2]]
+        t_end = 0.0                                   # time(end)
+        for i in range(len(wp) - 1):
+            n = int(np.floor(times[i] / self.sample_time + 1e-9))
+            time.append((t_end + self.sample_time) + self.sample_time * np.arange(n))
+            xy.append(np.linspace(wp[i, :2], wp[i + 1, :2], n) if n != 1 else wp[i + 1:i + 2, :2])
+            t_end = time[-1][-1] if n else t_end
+        time = np.concatenate(time)
+        xy = np.concatenate(xy)
+        T = len(time)
+        traj = np.vstack([xy[:, 0], xy[:, 1], np.full(T, x0[2]), np.full(T, x0[3]), np.zeros(T)])
         return time, traj
 
     def waypoints_gen(self):

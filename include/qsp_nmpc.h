@@ -47,7 +47,8 @@ extern "C" {
                                 qsp_clear_plant, qsp_get_plant, qsp_closed_loop_metrics;
                              8: qsp_default_sim_noise, qsp_set_sim_noise, qsp_clear_sim_noise, qsp_get_sim_noise,
                                 qsp_gen_sim_noise;
-                             9: qsp_default_waypoint_opts, qsp_gen_waypoints */
+                             9: qsp_default_waypoint_opts, qsp_gen_waypoints (and, without a new number, the
+                                query qsp_get_fixed_horizon) */
 
 #define QSP_OK 0
 #define QSP_ERR_ARG (-1)
@@ -174,6 +175,10 @@ int qsp_get_layout(const qsp_solver* s, int32_t* stages_per_lane, int32_t* lanes
                              stay lane walks (at two stages per lane: scans) */
 #define QSP_WALK_SCAN 2   /* factor_scan = 1 at two stages per lane: the associative scan */
 int qsp_get_factor_walk(const qsp_solver* s, int32_t* walk);
+/* The horizon the handle's per-iteration QP launches are compiled for (0: they read it at run time, as every
+ * launch of the fused loop and of the merit SQP does).  Today 20 at N = 20 on the matrix-core walk at one
+ * stage per lane, 0 with QSP_FIXED_HORIZON=0.  Results do not depend on it. */
+int qsp_get_fixed_horizon(const qsp_solver* s, int32_t* N);
 
 /* ------------------------------------------------------------- model / OCP */
 /* PLY contour -> ordered control points, knots, c_ellipse (PusherSliderModel.m:84-132, :53-55). */
@@ -415,7 +420,10 @@ int qsp_synchronize(qsp_solver* s);
  * The Riccati factorisation runs on the FP64 matrix cores at one stage per lane for 12 <= N <= 31 and at
  * two stages per lane from N = 24 (qsp_get_factor_walk reports it); environment
  * QSP_MFMA_WALK=0 at qsp_create selects the lane walk instead, a developer A/B that rounds differently
- * (the oracle twin follows the same variable). */
+ * (the oracle twin follows the same variable).
+ * At N = 20 the per-iteration QP kernel of that variant is compiled for its horizon; environment
+ * QSP_FIXED_HORIZON=0 at qsp_create launches the runtime-horizon kernel instead (developer A/B, the same
+ * bits). */
 int qsp_set_stream_parts(qsp_solver* s, int32_t parts);
 int qsp_get_stream_parts(qsp_solver* s, int32_t* parts);
 /* Per-kernel timing (acados' time_lin / time_qp split).  qsp_set_kernel_timing(s, n) pre-creates

@@ -1,7 +1,8 @@
 """Instruction-class histogram of the matrix-core factor walk's step loop (developer tool, no GPU):
     python3 scripts/isa_classes.py [source.hip ...]
 compiles each source (default: the in-tree qsp_solver.hip) with the library's flags to assembly, takes
-the headline kernel qp_step_kernel<1, false, true, true>, finds the loops that issue v_mfma_f64 and
+the runtime-horizon kernel qp_step_kernel<1, false, true, true, 0> (the one compiled for N = 20 walks in
+straight-line code, without a loop to count), finds the loops that issue v_mfma_f64 and
 prints, per walk step (a loop iteration divided by the MFMAs per step, eleven), the instructions by
 class.  The loop body is straight-line code between its label and its back branch, so the static
 counts are the issued counts per step."""
@@ -13,7 +14,7 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-KERNEL = "_ZN3qsp14qp_step_kernelILi1ELb0ELb1ELb1EEEvNS_9SolveArgsEi"
+KERNEL = "_ZN3qsp14qp_step_kernelILi1ELb0ELb1ELb1ELi0EEEvNS_9SolveArgsEi"
 CLASSES = [
     ("mfma", lambda x: x.startswith("v_mfma")),
     ("fp64 arith", lambda x: re.match(r"v_(fma|fmac|mul|add|rcp|div\w*|ldexp|frexp\w*|max|min)_f64", x)),

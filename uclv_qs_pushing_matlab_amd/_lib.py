@@ -111,6 +111,7 @@ _SIGS = {
     "qsp_version": [],
     "qsp_get_layout": [_P, C.POINTER(_I), C.POINTER(_I)],
     "qsp_get_factor_walk": [_P, C.POINTER(_I)],
+    "qsp_get_fixed_horizon": [_P, C.POINTER(_I)],
     "qsp_shape_from_ply": [C.c_char_p, _I, _D, _D, _D, _D, C.POINTER(Shape)],
     "qsp_set_shapes": [_P, C.POINTER(Shape), _I],
     "qsp_set_shape_ids": [_P, _P],

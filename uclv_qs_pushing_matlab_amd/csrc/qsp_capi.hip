@@ -85,6 +85,7 @@ struct __attribute__((visibility("hidden"))) qsp_solver {
     bool nopack = false;           // QSP_PACKING=0: instances in lane order (developer A/B of the wave packing)
     bool mfw = true;               // QSP_MFMA_WALK=0: the lane walk wherever the matrix cores would factorise
                                    // (developer A/B; rounds differently: the oracle twin reads the same variable)
+    bool fixed_n = true;           // QSP_FIXED_HORIZON=0: the runtime-horizon QP kernel at every N (developer A/B; same bits)
     int cus = 256;                 // compute units of the device (hipDeviceProp multiProcessorCount)
 
     // streams and events here, on the handle's device; the buffers free themselves after this body
@@ -264,6 +265,7 @@ static SolveArgs make_args(qsp_solver* s) {
     a.wqp = s->wqp.data();
     a.wperm = s->nopack ? nullptr : s->wperm.data();
     if (s->poison) a.flags |= QSP_FLAG_POISON;
+    if (!s->fixed_n) a.flags |= QSP_FLAG_RUNTIME_N;
     a.wnit = s->wnit.data();
     a.whist = s->whist.data();
     a.wadj = s->wadj.data();
@@ -444,6 +446,7 @@ int qsp_create(const qsp_options* o, qsp_solver** out) {
     if (const char* mw = std::getenv("QSP_MFMA_WALK")) s->mfw = mw[0] != '0';
     s->p.mfma_walk = s->mfw ? 1 : 0;
     mfw_prepare(s->p);
+    if (const char* fh = std::getenv("QSP_FIXED_HORIZON")) s->fixed_n = fh[0] != '0';
     const char* pz = std::getenv("QSP_DEBUG_POISON");
     s->poison = pz && pz[0] == '1';
     s->dim = Dims{(size_t)o->batch, (size_t)o->N};
@@ -516,6 +519,12 @@ int qsp_get_layout(const qsp_solver* s, int32_t* S, int32_t* L) {
 int qsp_get_factor_walk(const qsp_solver* s, int32_t* walk) {
     if (!s || !walk) return fail(QSP_ERR_ARG, "qsp_get_factor_walk: null argument");
     *walk = factor_walk_kind(s->p, s->S);
+    return QSP_OK;
+}
+
+int qsp_get_fixed_horizon(const qsp_solver* s, int32_t* N) {
+    if (!s || !N) return fail(QSP_ERR_ARG, "qsp_get_fixed_horizon: null argument");
+    *N = qp_fixed_horizon(s->p, s->S, s->fixed_n ? 0u : QSP_FLAG_RUNTIME_N);
     return QSP_OK;
 }
 

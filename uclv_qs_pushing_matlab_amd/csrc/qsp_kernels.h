@@ -9,6 +9,7 @@
 #define QSP_FLAG_CONTROLLER 1u  // NMPC_controller.solve prologue: s pre-wrap, cold/warm start, clip, Euler rollout
 #define QSP_FLAG_SHIFT 2u       // write the warm start shifted by one stage (NMPC_controller.m:397-399)
 #define QSP_FLAG_POISON 4u      // debug (QSP_DEBUG_POISON=1): QP kernels fill their LDS with NaN first
+#define QSP_FLAG_RUNTIME_N 8u   // developer A/B (QSP_FIXED_HORIZON=0): never the kernels compiled for one horizon (host only)
 
 namespace qsp {
 
@@ -88,6 +89,7 @@ __device__ __forceinline__ const ShapeDev& shape_clamped(const ShapeDev* shapes,
 
 // QSP_WALK_* of a handle's QP kernels (the launchers' own choice: factor_alt, mfw_use)
 int factor_walk_kind(const SolveParams& p, int S);
+int qp_fixed_horizon(const SolveParams& p, int S, uint32_t flags);   // compiled horizon of the per-iteration QP launches (0: none)
 void mfw_prepare(SolveParams& p);   // SolveParams::mfw_on / mfw_is from N and mfma_walk
 // Multi-stream split of the SQP loop (SqpStreams::parts = P > 1): the instances are cut into
 // P parts and each part runs its own (sort, qp_step) sequence on its own stream (part 0 on

@@ -226,6 +226,7 @@ struct Stage {
 
 struct Ctx {
     int lane, L, grp, lig, base, N;
+    int mis;   // compiled horizon: doubles between the instances' factor-walk records (else -1: SolveParams::mfw_is)
     bool real;
     int inst;
     GroupScan gs;
@@ -233,13 +234,19 @@ struct Ctx {
 
 // Wave geometry of a thread (qsp_layout.h): its group of L lanes, its place in it, and the instance
 // of the launch's range [0, nI) the group holds (real: there is one).
-template <int S>
+// NC > 0: the horizon as a compile-time constant (the caller launches such a kernel only at
+// p.N == NC, launch_qp_any).  Everything derived from it -- L, G, the IPM's m, the factor walk's phase
+// split and record stride, every walk's trip count and the form of the group sums -- then folds, where
+// the kernel of a runtime horizon (NC = 0) recomputes it, holds it in registers or spills it.
+template <int S, int NC = 0>
 __device__ __forceinline__ Ctx ctx_of(int lane, int N, int nI) {
     Ctx c;
+    if (NC) N = NC;
     c.lane = lane;
     c.N = N;
     c.L = lanes_per_instance(N, S);
     const int G = WAVE / c.L;
+    c.mis = NC ? mfw_stride(mfw_records(NC), instances_per_wave(NC, S)) : -1;
     c.grp = c.lane / c.L;
     c.lig = c.lane - c.grp * c.L;
     c.base = c.grp * c.L;
@@ -341,7 +348,7 @@ __device__ __forceinline__ void factor_walk_mfma(const Ctx& c, const SolveParams
                                                  const double (&hu)[S][2], const double (&gx3)[S], const double (&gu)[S][2]) {
     const int N = c.N, G = WAVE / c.L;
     const int H = mfw_split(N);                   // phase split (CM = mfw_records(N) records per instance and phase)
-    const int IS = p.mfw_is[S - 1];               // doubles from one instance's records to the next's (mfw_prepare)
+    const int IS = c.mis >= 0 ? c.mis : p.mfw_is[S - 1];   // doubles from one instance's records to the next's (mfw_prepare)
     double* const reg = st.lds - (threadIdx.x & 63) + F_VA * S * BLOCK;
     // block-lane geometry and the record slot of each operand element (-1: structural constant)
     // (an opaque lane id: derived from c.lane, the geometry would be hoisted out of the IPM loop and
@@ -592,7 +599,15 @@ __device__ __forceinline__ void velem_read(const VElem& e, int src, VElem& f) {
 // Backward pass over the group (factorisation, or the corrector's difference recursion),
 // then forward pass writing the bounded components of the solution into LDS field `out`
 // (F_VA / F_VN).
-template <int S, bool FACTOR, bool ALT = false>
+// NC: the horizon where it is compiled in (ctx_of).  The closed-loop lane walks (S = 1) then have constant
+// trip counts and run QSP_WALK_UNROLL steps per loop iteration: a rolled step pays two branches and the
+// loop counter beside its 16 FMA and 8 DPP moves.  Measured at N = 20 (profiles/fixed_horizon/README.md):
+// 2 +1.2 %, 4 +2.0 % over the rolled walks, both at the rolled kernel's 253 VGPRs; 5 (+2.2 %) and the full
+// unroll (+1.9 %) take 256 VGPRs, 10 takes 264 (one wave per SIMD).  NC = 0 keeps the rolled loops (count 1).
+#ifndef QSP_WALK_UNROLL
+#define QSP_WALK_UNROLL 4
+#endif
+template <int S, bool FACTOR, bool ALT = false, int NC = 0>
 __device__ __forceinline__ void riccati_solve(const Ctx& c, const SolveParams& p, Stage<S>& st, const double dx0[4],
                                               int out, double (&M)[S][16], const double (&hgv)[S][6]) {
     SEG_T(t_rs);
@@ -642,6 +657,7 @@ __device__ __forceinline__ void riccati_solve(const Ctx& c, const SolveParams& p
         // whose source lane j+1 sits the step out, keeps its old value (a DPP read from a
         // disabled lane returns `old`) — so every lane ends holding the dp that reached it.
         // (step 0 would only form dp_0, which nothing reads: lane 0 holds dp_1 after step 1)
+#pragma clang loop unroll_count(NC ? QSP_WALK_UNROLL : 1)
         for (int j = c.L - 2; j >= 1; --j) {
             if (c.lig <= j) {
                 double n[4];
@@ -819,6 +835,7 @@ __device__ __forceinline__ void riccati_solve(const Ctx& c, const SolveParams& p
         // Step j runs on lanes j <= lig < L-1 only (the terminal lane never steps, so the
         // next group's first lane reads a disabled source): lane j+1 takes lane j's value and
         // lane j keeps its own, so every lane ends holding the dx of its stage.
+#pragma clang loop unroll_count(NC ? QSP_WALK_UNROLL : 1)
         for (int j = 0; j < c.L - 1; ++j) {
             if (c.lig >= j && c.lig < c.L - 1) {
                 double n[4];
@@ -902,7 +919,7 @@ __device__ __forceinline__ void riccati_solve(const Ctx& c, const SolveParams& p
 // (1 - alpha), so each is its start value times prod(1 - alpha) (tracked, not recomputed:
 // r0 = bound residual of the floored slacks, rg0 = max|g + C' lam|, rb0 = max(|dx0|, |b|)); the
 // test r * prod < tol is applied as prod < min(tol / r) over the three.
-template <int S, bool ALT = false>
+template <int S, bool ALT = false, int NC = 0>
 __device__ int qp_ipm(const Ctx& c, const SolveParams& p, Stage<S>& st, const double dx0[4], int& exit,
                       bool skip = false) {
     SEG_T(t_ipm);
@@ -985,7 +1002,7 @@ __device__ int qp_ipm(const Ctx& c, const SolveParams& p, Stage<S>& st, const do
         SEG_NEXT(0, t_seg);   // with the predictor's barrier terms (segment 1, theirs alone, is gone)
         // ---- predictor
         double M[S][16];   // closed-loop matrices A + B K (S = 1), shared by both forward walks
-        riccati_solve<S, true, ALT>(c, p, st, dx0, F_VA, M, hgv);
+        riccati_solve<S, true, ALT, NC>(c, p, st, dx0, F_VA, M, hgv);
         SEG_T(t_seg2);
         // affine directions: computed once, kept in registers through the corrector
         double at[S][6], al[S][6];
@@ -1005,7 +1022,7 @@ __device__ int qp_ipm(const Ctx& c, const SolveParams& p, Stage<S>& st, const do
 #pragma unroll
         for (int ls = 0; ls < S; ++ls) corrector_terms(p, c.N, st, ls, kof<S>(c, ls), at[ls], al[ls], smu);
         SEG_ADD(5, t_seg2);
-        riccati_solve<S, false, ALT>(c, p, st, dx0, F_VN, M, hgv);
+        riccati_solve<S, false, ALT, NC>(c, p, st, dx0, F_VN, M, hgv);
         SEG_T(t_seg3);
         double dt[S][6], dl[S][6];
         num = 1.0; den = p.frac;       // initial bound 1/frac
@@ -1355,17 +1372,18 @@ __device__ __forceinline__ void iterate_update(const SolveArgs& A, const Ctx& c,
     }
 }
 
-template <int S, bool MERIT = false, bool LIN = false, bool ALT = false>
+// NC: the horizon compiled in (0: read from p.N; see ctx_of and QSP_FIXED_HORIZONS)
+template <int S, bool MERIT = false, bool LIN = false, bool ALT = false, int NC = 0>
 __global__ void __launch_bounds__(BLOCK, QSP_MIN_WAVES) qp_step_kernel(SolveArgs A, int it) {
     SEG_T(t_k);
     extern __shared__ double smem[];
     const SolveParams& p = A.p;
-    const Ctx c = ctx_of<S>(threadIdx.x & 63, p.N, A.nI);
+    const Ctx c = ctx_of<S, NC>(threadIdx.x & 63, p.N, A.nI);
     // instances are packed into waves in the order of their previous IPM iteration count
     // (sort_by_iters_kernel), so the instances sharing a wave finish together
     const int slot = A.i0 + (c.real ? c.inst : A.nI - 1);
     const int iv = A.wperm ? A.wperm[slot] : slot;
-    const int N = p.N;
+    const int N = c.N;
     const size_t tot = (size_t)A.B * (N + 1);
     Stage<S> st;
     st.lds = smem + threadIdx.x;
@@ -1470,7 +1488,7 @@ __global__ void __launch_bounds__(BLOCK, QSP_MIN_WAVES) qp_step_kernel(SolveArgs
     }
     int exit;
     SEG_NEXT(10, t_k);
-    const int nit = qp_ipm<S, ALT>(c, p, st, dx0, exit, skip);
+    const int nit = qp_ipm<S, ALT, NC>(c, p, st, dx0, exit, skip);
     SEG_NEXT(11, t_k);
     qp_rollout<S>(c, st, dx0);
     const bool failed = qp_outcome<S>(A, c, st, iv, it, exit, skip);
@@ -1936,9 +1954,27 @@ int sqp_fused_auto(int B, int N, int S, int nlp_mode, int cus) {
     return (nlp_mode == 0 && (S == 1 || S == 2) && waves <= 4L * cus) ? 1 : 0;
 }
 
+// The horizons qp_step_kernel is also compiled for, one X(N) each (one stage per lane on the matrix
+// cores, with and without the linearisation).  A handle's horizon is fixed at its creation, so at
+// these the kernel need not carry N as data (ctx_of); every other horizon, variant and kernel takes the
+// runtime-horizon code.  Results are the same bits either way; QSP_FIXED_HORIZON=0 forces the latter.
+#define QSP_FIXED_HORIZONS(X) X(20)
+
 // lin: the SQP iteration's linearisation runs inside the QP kernel (nlp_mode 0); without it the
 // kernel reads the stage data the workspace holds (qsp_qp_solve).
+// The compiled horizon the per-iteration QP launches of a handle take (0: the runtime-horizon kernel):
+// p.N where QSP_FIXED_HORIZONS lists it, on the one-stage matrix-core variant, unless the switch forbids it.
+int qp_fixed_horizon(const SolveParams& p, int S, uint32_t flags) {
+    if (S != 1 || !factor_alt(p, 1) || (flags & QSP_FLAG_RUNTIME_N)) return 0;
+#define QSP_FIXED_IS(n) if (p.N == n) return n;
+    QSP_FIXED_HORIZONS(QSP_FIXED_IS)
+#undef QSP_FIXED_IS
+    return 0;
+}
+
+static hipError_t launch_qp_fixed(const SolveArgs& a, int it, hipStream_t stream, bool lin);
 static hipError_t launch_qp_any(const SolveArgs& a, int S, int it, hipStream_t stream, bool lin) {
+    if (qp_fixed_horizon(a.p, S, a.flags)) return launch_qp_fixed(a, it, stream, lin);   // the kernel compiled for it (same bits)
     return with_variant(a.p, S, [&](auto s, auto alt) {
         return lin ? launch_qp_waves<qp_step_kernel<s(), false, true, alt()>, s()>(a, stream, it)
                    : launch_qp_waves<qp_step_kernel<s(), false, false, alt()>, s()>(a, stream, it);
@@ -2076,6 +2112,22 @@ hipError_t launch_qp(const SolveArgs& a, int S, hipStream_t stream) {
     as.i0 = 0;
     as.nI = a.B;
     return launch_qp_any(as, S, a.p.sqp_iters - 1, stream, false);
+}
+
+// The kernels compiled for a horizon (a.p.N == qp_fixed_horizon(...) != 0).  Defined last, so these
+// instantiations follow every other kernel in the code object and the others keep the places they have
+// without them.
+static hipError_t launch_qp_fixed(const SolveArgs& a, int it, hipStream_t stream, bool lin) {
+    switch (a.p.N) {
+#define QSP_FIXED_CASE(n)                                                                            \
+    case n:                                                                                          \
+        static_assert(mfw_fits(n, 1), "a compiled horizon takes the one-stage matrix-core variant"); \
+        return lin ? launch_qp_waves<qp_step_kernel<1, false, true, true, n>, 1>(a, stream, it)      \
+                   : launch_qp_waves<qp_step_kernel<1, false, false, true, n>, 1>(a, stream, it);
+        QSP_FIXED_HORIZONS(QSP_FIXED_CASE)
+#undef QSP_FIXED_CASE
+        default: return hipErrorInvalidValue;
+    }
 }
 
 }  // namespace qsp

@@ -109,6 +109,12 @@ class OcpSolver:
         check(self._L.qsp_get_factor_walk(self._h, C.byref(w)), "qsp_get_factor_walk")
         return self.FACTOR_WALKS[w.value]
 
+    def fixed_horizon(self):
+        """The horizon the per-iteration QP launches are compiled for (qsp_get_fixed_horizon; 0: none)."""
+        n = C.c_int32()
+        check(self._L.qsp_get_fixed_horizon(self._h, C.byref(n)), "qsp_get_fixed_horizon")
+        return n.value
+
     # --------------------------------------------------------------- model
     def set_shapes(self, shapes, shape_id=None):
         arr = (_lib.Shape * len(shapes))(*shapes)

@@ -17,8 +17,11 @@
  * Division of labour.  The lane-local arithmetic -- qfma, rcp, sin_cos, the span-based
  * de Boor, the dynamics with its hand-derived Jacobian, RK4, the contact re-projection, the structured
  * Riccati step, the scans' maps and elements, the adjoint and merit stage terms, the IPM's barrier
- * terms, directions, step and exit test, the merit SQP's KKT residuals and updates, the controller's
- * guess roll-out -- is NOT restated here: this file compiles the kernels' own headers
+ * terms, directions, step and exit test, the merit SQP's KKT residuals and updates -- and the per-lane code
+ * around the solve -- the shape table's entries, the parameters from the options, which factorisation a
+ * handle takes, get_y_ref's staging, the controller's prologue, status rule, shifted warm start and cost,
+ * the closed loop's disturbance, delay prediction and input buffers, the building blocks' output layout,
+ * the QP-level entry's mapping and status -- are NOT restated here: this file compiles the kernels' own headers
  * (csrc/qsp_fp.hpp, qsp_math.hpp, qsp_riccati.hpp, qsp_ipm.hpp) for the host, with
  * -ffp-contract=off as the library.  What it restates, as plain sequential loops, is the
  * ORCHESTRATION the device runs in DPP moves, LDS records and matrix-core instructions: which lane
@@ -27,8 +30,8 @@
  * Still written out here as in the kernels, each for a measured reason (profiles/ipm_shared/README.md
  * section B): qp_ipm's t.lm sum and centring scalar and load_stage (as shared functions they cost the
  * SQP kernels registers), qp_ipm's start point (registers equal, but 0.4 % slower on the headline
- * workload), merit_ls's directional-derivative term and epilogue_cost (their kernels' instruction
- * counts move by more than 1 %).  The operations are IEEE-exact on
+ * workload), merit_ls's directional-derivative term (its kernel's instruction count
+ * moves by more than 1 %).  The operations are IEEE-exact on
  * both sides (checked on the device by scripts/ubench/fp_exact.hip), so this twin reproduces the
  * library's results BIT FOR BIT, lane by lane, including lanes where the fixed-K SQP is chaotic:
  * the comparison proves that the GPU's compiler and hardware evaluate the shared source as x86 does
@@ -46,8 +49,7 @@
 #endif
 
 #include "or_opts.h"
-#include "qsp_nmpc.h"      /* QSP_WALK_* (tw_factor_walk) */
-#include "qsp_layout.h"    /* the library's own layout rules: stages per lane, lanes per instance, mfw_fits */
+#include "qsp_layout.h"    /* the library's own layout rules: stages per lane, lanes per instance, factor_walk_of */
 #include "qsp_math.hpp"    /* the library's own lane arithmetic: qsp_fp.hpp, the model ... */
 #include "qsp_riccati.hpp" /* ... the QP's per-lane steps ... */
 #include "qsp_ipm.hpp"     /* ... and the per-stage arithmetic of the interior point and the SQP */
@@ -61,28 +63,8 @@ using namespace qsp;
 static void make_shape(ShapeDev *d, const int32_t *n_ctrl, const double *ctrl, const double *knots,
                        const double *params, int max_ctrl, int id, double xwidth)
 {
-    memset(d, 0, sizeof *d);
-    const int nc = n_ctrl[id];
-    const double *S = knots + (size_t)id * (max_ctrl + 4), *P = ctrl + (size_t)id * max_ctrl * 2;
-    d->n = nc;
-    d->b = params[3 * id];
-    d->c = params[3 * id + 1];
-    d->mu = params[3 * id + 2];
-    d->xwidth = xwidth;
-    for (int i = 0; i < nc + 4; ++i) d->knots[i] = S[i];
-    for (int i = 0; i < 2 * nc; ++i) d->ctrl[i] = P[i];
-    const double h0 = S[4] - S[3];
-    d->inv_h = h0 > 0.0 ? 1.0 / h0 : 0.0;
-    for (int i = 1; i < nc; ++i) {
-        const double den = d->knots[i + 3] - d->knots[i];
-        for (int c = 0; c < 2; ++c)
-            d->dctrl[2 * i + c] = den != 0.0 ? 3.0 * ((d->ctrl[2 * i + c] - d->ctrl[2 * (i - 1) + c]) / den) : 0.0;
-    }
-    for (int i = 2; i < nc; ++i) {
-        const double den = d->knots[i + 2] - d->knots[i];
-        for (int c = 0; c < 2; ++c)
-            d->ddctrl[2 * i + c] = den != 0.0 ? 2.0 * ((d->dctrl[2 * i + c] - d->dctrl[2 * (i - 1) + c]) / den) : 0.0;
-    }
+    shape_entry(*d, n_ctrl[id], ctrl + (size_t)id * max_ctrl * 2, knots + (size_t)id * (max_ctrl + 4), params[3 * id],
+                params[3 * id + 1], params[3 * id + 2], xwidth);
 }
 
 /* ================================================================== the QP (qp_ipm) */
@@ -107,40 +89,26 @@ struct tw_view {
     double &du(int, int i) const { return s->du[i]; }
 };
 
-/* the solve parameters the kernels read, plus the layout they imply.  mfma_walk is the twin's own
- * decision here (mfw_on / mfw_is, the kernels' record layout, stay unset) */
+/* the solve parameters the kernels read, plus the layout and the factorisation (FactorWalk) they imply
+ * (mfw_on / mfw_is, the kernels' record layout, stay unset) */
 struct tw_par : SolveParams {
-    int S, L;
+    int S, L, walk;
 };
 
 static void make_par(tw_par *p, const or_opts *o)
 {
     *p = tw_par{};
-    p->N = o->N;
+    params_from_options(*p, *o);
     p->S = stages_per_lane(o->N, o->nlp_mode, o->stages_per_lane);
     p->L = lanes_per_instance(p->N, p->S);
-    p->nlp_mode = o->nlp_mode;
-    p->sqp_iters = o->sqp_iters;
-    p->qp_iters = o->qp_iters;
-    p->qp_stall_iters = o->qp_stall_iters;
-    p->s0_bound = o->stage0_s_bound ? 1 : 0;
-    p->factor_scan = o->factor_scan ? 1 : 0;
-    /* the kernels factorise on the matrix cores where one instance per 16-lane block and a phase's
-     * stage records fit (mfw_fits, the library's own rule), unless the library's developer switch
-     * QSP_MFMA_WALK=0 selects the lane walk there too */
-    const char *mw = getenv("QSP_MFMA_WALK");
-    p->mfma_walk = mfw_fits(p->N, p->S) && !(mw && mw[0] == '0') && !o->lane_walk;
-    p->Ts = o->Ts;
+    /* the library's developer switch, and the twin's own to the lane walk's order */
+    p->mfma_walk = mfma_walk_default() && !o->lane_walk;
+    p->walk = factor_walk_of(p->N, p->S, p->mfma_walk, p->factor_scan);
     p->tau = o->tau;
     memcpy(p->W, o->W, sizeof p->W);
     memcpy(p->We, o->We, sizeof p->We);
     memcpy(p->lh, o->lh, sizeof p->lh);
     memcpy(p->uh, o->uh, sizeof p->uh);
-    p->mu0 = o->mu0; p->t_min = o->t_min; p->frac = o->frac; p->sigma_min = o->sigma_min; p->mu_stop = o->mu_stop;
-    p->res_stop = o->res_stop; p->qp_tol_stat = o->qp_tol_stat; p->qp_tol_eq = o->qp_tol_eq;
-    p->qp_stall_alpha = o->qp_stall_alpha; p->qp_mu_max = o->qp_mu_max;
-    p->tol_stat = o->tol_stat; p->tol_eq = o->tol_eq; p->tol_ineq = o->tol_ineq; p->tol_comp = o->tol_comp;
-    p->ls_alpha_min = o->ls_alpha_min; p->ls_alpha_red = o->ls_alpha_red; p->ls_eps = o->ls_eps;
     p->cp = CtrlParams{o->v_alpha, o->d_v, o->t_angle0, o->u_n_lb, o->u_t_ub};
 }
 
@@ -150,8 +118,7 @@ extern "C" int tw_factor_walk(const or_opts *o)
 {
     tw_par p;
     make_par(&p, o);
-    if (p.S == 2 && p.factor_scan) return QSP_WALK_SCAN;
-    return p.mfma_walk ? QSP_WALK_MFMA : QSP_WALK_LANE;
+    return p.walk;
 }
 
 /* group_sum: the kernel's log-step shuffle tree towards the group's first lane */
@@ -481,9 +448,9 @@ static void riccati_solve(const tw_par *p, tw_stage *st, const double dx0[4], in
         }
     } else if (S == 2 && !factor) {
         delta_scan_s2(p, st, gx3, gu);
-    } else if (S == 2 && factor && p->factor_scan) {
+    } else if (factor && p->walk == WALK_SCAN) {
         factor_scan_s2(p, st, hx3, hu, gx3, gu);
-    } else if (factor && p->mfma_walk) {
+    } else if (factor && p->walk == WALK_MFMA) {
         factor_walk_mfma(p, st, hx3, hu, gx3, gu);
     } else {   /* the factorisation by the lane walk (both difference passes are taken above) */
         double P[10], pv[4];
@@ -859,11 +826,7 @@ static void sqp_solve(const tw_par *p, const ShapeDev *sh, tw_ws *w, const doubl
         if (failed) continue;
         double pik[TW_MAX_N * 4];
         qp_adjoint(p, w->st, pik);
-        for (int k = 0; k < N; ++k) {
-            const int dst = shift ? (k >= 1 ? k - 1 : -1) : k;
-            if (dst >= 0) memcpy(PI_out + 4 * dst, pik + 4 * k, sizeof(double) * 4);
-        }
-        if (shift) memcpy(PI_out + 4 * (N - 1), pik + 4 * (N - 1), sizeof(double) * 4);
+        shift_rows<4>(N, shift, pik, 4, 1, PI_out);   /* adjoint_from_record's rows */
         o->pi_written = 1;
         for (int k = 0; k <= N; ++k)
             for (int q = 0; q < 4; ++q) X[4 * k + q] += w->st[k].dxs[q];
@@ -874,38 +837,11 @@ static void sqp_solve(const tw_par *p, const ShapeDev *sh, tw_ws *w, const doubl
         o->qp_iter += nit;
     }
     /* epilogue_kernel (status; cost and outputs by the callers) */
-    int bad = 0;
-    for (int q = 0; q < 4 * (N + 1); ++q) bad |= !isfinite(X[q]);
-    for (int q = 0; q < 2 * N; ++q) bad |= !isfinite(U[q]);
-    for (int q = 0; q < 4; ++q) bad |= !isfinite(x0[q]);
-    /* non-finite wins (qsp_nmpc.h, QSP_STATUS_*) */
-    if (bad || wdone == 2) o->status = 1;
-    else if (wdone == 3 || wdone == 4) o->status = 4;
-    else if (p->nlp_mode == 1) o->status = wdone == 1 ? 0 : 2;
-    else o->status = 0;
-    if (wdone == 0) o->sqp_iter = p->sqp_iters;
+    o->status = solve_status(*p, iterate_nonfinite(N, X, U, x0), wdone, o->sqp_iter);
     if (p->nlp_mode == 1) {
-        for (int k = 0; k < N; ++k) {
-            const int src = shift ? (k + 1 < N ? k + 1 : N - 1) : k;
-            memcpy(PI_out + 4 * k, w->nlpPI + 4 * src, sizeof(double) * 4);
-        }
+        shift_rows<4>(N, shift, w->nlpPI, 4, 1, PI_out);
         o->pi_written = 1;
     }
-}
-
-static double epilogue_cost(const tw_par *p, const double *X, const double *U, const double *yref, const double *ye)
-{
-    const int N = p->N;
-    double cost = 0.0;
-    for (int k = 0; k < N; ++k) {
-        double s = 0.0;
-        for (int q = 0; q < 4; ++q) { const double r = X[4 * k + q] - yref[6 * k + q]; s = qfma(p->W[q] * r, r, s); }
-        for (int q = 0; q < 2; ++q) { const double r = U[2 * k + q] - yref[6 * k + 4 + q]; s = qfma(p->W[4 + q] * r, r, s); }
-        cost = qfma(0.5 * p->tau, s, cost);
-    }
-    double s = 0.0;
-    for (int q = 0; q < 4; ++q) { const double r = X[4 * N + q] - ye[q]; s = qfma(p->We[q] * r, r, s); }
-    return qfma(0.5, s, cost);
 }
 
 /* ================================================================== exported API (as qsp_oracle.c) */
@@ -935,15 +871,8 @@ int tw_dynamics(const int32_t *n_ctrl, const double *ctrl, const double *knots, 
         make_shape(&sh, n_ctrl, ctrl, knots, params, max_ctrl, shape_id[i], 0.0);
         DynOut d;
         dynamics<true>(sh, x[4 * i + 2], x[4 * i + 3], u[2 * i], u[2 * i + 1], d);
-        for (int r = 0; r < 4; ++r) {
-            f[4 * i + r] = d.f[r];
-            if (J) {
-                double *Jr = J + (size_t)24 * i + 6 * r;
-                Jr[0] = 0.0; Jr[1] = 0.0;
-                Jr[2] = r < 2 ? d.Jth[r] : 0.0;
-                Jr[3] = d.Js[r]; Jr[4] = d.Jun[r]; Jr[5] = d.Jut[r];
-            }
-        }
+        double Jn[24];   /* a caller without J */
+        pack_dynamics(d, f + 4 * i, J ? J + (size_t)24 * i : Jn);
     }
     return 0;
 }
@@ -958,10 +887,7 @@ int tw_rk4(const int32_t *n_ctrl, const double *ctrl, const double *knots, const
         make_shape(&sh, n_ctrl, ctrl, knots, params, max_ctrl, shape_id[i], 0.0);
         Lin L;
         rk4<true>(sh, h, x + 4 * i, u + 2 * i, L);
-        const double Af[16] = {1.0, 0.0, L.a[0], L.a[1], 0.0, 1.0, L.a[2], L.a[3], 0.0, 0.0, 1.0, L.a[4], 0.0, 0.0, 0.0, L.a[5]};
-        memcpy(A + (size_t)16 * i, Af, sizeof Af);
-        memcpy(B + (size_t)8 * i, L.B, sizeof L.B);
-        memcpy(xn + 4 * i, L.xn, sizeof L.xn);
+        pack_lin(L, xn + 4 * i, A + (size_t)16 * i, B + (size_t)8 * i);
     }
     return 0;
 }
@@ -977,10 +903,9 @@ int tw_vbound(const int32_t *n_ctrl, const double *ctrl, const double *knots, co
     return 0;
 }
 
-/* QP level (qsp_qp_solve): the same mapping onto the kernel's parameters -- tau = 1, W = the stage
- * Hessian, We = the terminal one, lh = 0, uh = hi - lo of the first lane's first stage, the bounded
- * components v = -lo through X/U, x0 = dx0 + X_0.  qp_status: 0 stop test met, 1 non-finite,
- * 2 cap, 3 infeasible stage-0 s, 4 stall, 5 diverged. */
+/* QP level (qsp_qp_solve): the library's own mapping onto the kernel's parameters and iterate
+ * (qp_level_params, qp_level_iterate) and its qp_status (qp_level_status: 0 stop test met, 1 non-finite,
+ * 2 cap, 3 infeasible stage-0 s, 4 stall, 5 diverged), qsp_ipm.hpp. */
 int tw_qp_batch(const or_opts *o, int32_t nb, const double *A, const double *B, const double *b,
                 const double *H, const double *g, const double *lo, const double *hi, const uint8_t *act,
                 const double *dx0, double *dx, double *du, double *pi, double *lam, int32_t *iters, int32_t *qp_status)
@@ -990,10 +915,7 @@ int tw_qp_batch(const or_opts *o, int32_t nb, const double *A, const double *B, 
     if (N > TW_MAX_N) return -1;
     tw_par p;
     make_par(&p, o);
-    p.tau = 1.0;
-    for (int i = 0; i < 6; ++i) p.W[i] = H[i];
-    for (int i = 0; i < 4; ++i) p.We[i] = H[6 * N + i];
-    for (int j = 0; j < 3; ++j) { p.lh[j] = 0.0; p.uh[j] = hi[j] - lo[j]; }
+    qp_level_params(p, H, lo, hi);
     int fail = 0;
     #pragma omp parallel
     {
@@ -1001,6 +923,9 @@ int tw_qp_batch(const or_opts *o, int32_t nb, const double *A, const double *B, 
         #pragma omp for schedule(dynamic, 4)
         for (int32_t l = 0; l < nb; ++l) {
             const int L = p.L, S = p.S;
+            const double *lol = lo + (size_t)l * N * 3, *hil = hi + (size_t)l * N * 3;
+            double X[(TW_MAX_N + 1) * 4], U[TW_MAX_N * 2], x0w[4], d0[4];
+            qp_level_iterate(N, lol, dx0 + 4 * l, X, U, x0w);
             for (int k = 0; k < L * S; ++k) {
                 tw_stage *s = w->st + k;
                 const int kc = k <= N ? k : N, ku = k < N ? k : N - 1;
@@ -1015,16 +940,12 @@ int tw_qp_batch(const or_opts *o, int32_t nb, const double *A, const double *B, 
                 } else {
                     memcpy(s->g, g + (size_t)l * (6 * N + 4) + 6 * N, sizeof(double) * 4);
                 }
-                /* v through the workspace X (s of stage kc; X_N's s is 0) and U (stage ku) */
-                s->v[0] = kc < N ? -lo[((size_t)l * N + kc) * 3] : 0.0;
-                s->v[1] = -lo[((size_t)l * N + ku) * 3 + 1];
-                s->v[2] = -lo[((size_t)l * N + ku) * 3 + 2];
+                /* v through the workspace X (s of stage kc; X_N's s is 0) and U (stage ku), as load_stage */
+                s->v[0] = X[4 * kc + 3];
+                s->v[1] = U[2 * ku];
+                s->v[2] = U[2 * ku + 1];
             }
-            double x0w[4], d0[4];
-            memcpy(x0w, dx0 + 4 * l, sizeof x0w);
-            const double X0s = -lo[(size_t)l * N * 3];
-            x0w[3] += X0s;
-            for (int q = 0; q < 4; ++q) d0[q] = x0w[q] - (q == 3 ? X0s : 0.0);
+            for (int q = 0; q < 4; ++q) d0[q] = x0w[q] - X[q];   /* the kernels' dx0 = wx0 - X_0 */
             int exit;
             const int nit = qp_ipm(&p, w->st, d0, &exit, 0);
             qp_rollout(&p, w->st, d0);
@@ -1035,13 +956,10 @@ int tw_qp_batch(const or_opts *o, int32_t nb, const double *A, const double *B, 
             }
             qp_adjoint(&p, w->st, pi + (size_t)l * N * 4);
             if (iters) iters[l] = nit;
-            int fin = 1;
-            for (int q = 0; q < (N + 1) * 4; ++q) fin = fin && isfinite(dx[(size_t)l * (N + 1) * 4 + q]);
-            for (int q = 0; q < N * 2; ++q) fin = fin && isfinite(du[(size_t)l * N * 2 + q]);
-            const int infeas = p.s0_bound && (dx0[4 * l + 3] < lo[(size_t)l * N * 3] || dx0[4 * l + 3] > hi[(size_t)l * N * 3]);
-            const int kst = exit == QP_EXIT_CONV ? 0 : (exit == QP_EXIT_CAP ? 2 : (exit == QP_EXIT_STALL ? 4 : 5));
-            if (qp_status) qp_status[l] = !fin ? 1 : (infeas ? 3 : kst);
-            if (!fin) {
+            const int qs = qp_level_status(p, dx + (size_t)l * (N + 1) * 4, du + (size_t)l * N * 2, lol, hil, dx0 + 4 * l,
+                                           qp_exit_status(exit));
+            if (qp_status) qp_status[l] = qs;
+            if (qs == 1) {   /* 1 = non-finite only: qp_exit_status never returns it (0, 2, 4, 5), nor the infeasible 3 */
                 #pragma omp atomic write
                 fail = 1;
             }
@@ -1090,30 +1008,11 @@ int tw_ocp_solve(const int32_t *n_ctrl, const double *ctrl, const double *knots,
                 if (p.nlp_mode == 1) memcpy(lam + (size_t)i * 6 * N, w->LAM, sizeof(double) * 6 * N);
                 else memset(lam + (size_t)i * 6 * N, 0, sizeof(double) * 6 * N);
             }
-            cost[i] = epilogue_cost(&p, Xi, Ui, yr, ye);
+            cost[i] = solve_cost(p, Xi, Ui, yr, ye);
         }
         free(w);
     }
     return 0;
-}
-
-/* stage_yref_kernel: column index_time + k (1-based) of the table as set_reference_trajectory
- * builds it (D zero columns prepended, their u_t row copied from the first real column), clamped */
-static void stage_yref(const double *traj, int32_t T, int32_t D, int32_t index_time, int N, double *yref, double *ye)
-{
-    for (int k = 0; k < N; ++k) {
-        int idx = index_time + k;
-        if (idx > T + D) idx = T + D;
-        if (idx < 1) idx = 1;
-        double *out = yref + 6 * k;
-        if (idx <= D) {
-            for (int c = 0; c < 5; ++c) out[c] = 0.0;
-            out[5] = traj[5];
-        } else {
-            for (int c = 0; c < 6; ++c) out[c] = traj[(size_t)(idx - D - 1) * 6 + c];
-        }
-    }
-    for (int c = 0; c < 4; ++c) ye[c] = yref[6 * (N - 1) + c];
 }
 
 /* NMPC_controller.solve on one lane (prologue_kernel in controller mode, the SQP, the epilogue's
@@ -1126,28 +1025,17 @@ static int ctrl_lane(const tw_par *p, const ShapeDev *sh, tw_ws *w, const double
     double yref[TW_MAX_N * 6], ye[4], X[(TW_MAX_N + 1) * 4], U[TW_MAX_N * 2];
     stage_yref(traj, T, D, index_time, N, yref, ye);
     double x0[4] = {x0_in[0], x0_in[1], x0_in[2], x0_in[3]};
-    x0[3] = wrap_contact(*sh, x0[3]);
     const int cold = !*valid;
-    for (int k = 0; k < N; ++k) {
-        U[2 * k] = cold ? p->cp.u_n_lb : Uw[2 * k];
-        U[2 * k + 1] = cold ? 0.0 : Uw[2 * k + 1];
-    }
-    guess_rollout(*sh, *p, x0, U, X);   /* with the handle's controller parameters */
+    controller_guess(*sh, *p, cold, Uw, x0, U, X);   /* with the handle's controller parameters */
     double PIin[TW_MAX_N * 4];
     memcpy(PIin, PIw, sizeof(double) * 4 * N);
     const int w0 = s0_infeasible(*p, x0[3]) ? 3 : 0;
     sqp_solve(p, sh, w, x0, yref, ye, X, U, cold ? NULL : PIin, PIw, 1, w0, out);
-    if (cost) *cost = epilogue_cost(p, X, U, yref, ye);
+    if (cost) *cost = solve_cost(*p, X, U, yref, ye);
     u0[0] = U[0];
     u0[1] = U[1];
-    for (int k = 0; k <= N; ++k) {
-        const int src = (k + 1 <= N) ? k + 1 : N;
-        memcpy(Xw + 4 * k, X + 4 * src, sizeof(double) * 4);
-    }
-    for (int k = 0; k < N; ++k) {
-        const int src = (k + 1 < N) ? k + 1 : N - 1;
-        memcpy(Uw + 2 * k, U + 2 * src, sizeof(double) * 2);
-    }
+    shift_rows<4>(N + 1, 1, X, 4, 1, Xw);
+    shift_rows<2>(N, 1, U, 2, 1, Uw);
     *valid = 1;
     return out->status;
 }
@@ -1242,41 +1130,22 @@ int tw_closed_loop(const int32_t *n_ctrl, const double *ctrl, const double *knot
             for (int32_t t = 0; t < n_steps; ++t) {
                 /* closed_loop_pre_kernel */
                 if (dist_step > 0 && t + 1 == dist_step) {
-                    const double amp = dist_amp ? dist_amp[i] : 0.0;
-                    x[1] += amp;
-                    SplineEval e;
-                    spline_eval(sh, mat_mod(x[3], sh.b), e);
-                    const double sn = reproject_contact(sh, -0.5 * sh.xwidth, e.C[1] - amp, 0.0);
-                    x[3] = wrap_contact(sh, sn);
+                    disturb_contact(sh, dist_amp ? dist_amp[i] : 0.0, x);
                 }
                 if (noise)
                     for (int c = 0; c < 4; ++c) x[c] += noise[((size_t)t * nb + i) * 4 + c];
                 memcpy(Xtraj + ((size_t)i * (n_steps + 1) + t) * 4, x, sizeof x);
                 double xs[4];
                 memcpy(xs, x, sizeof xs);
-                for (int k = 1; k <= delay_cols; ++k) {
-                    const double *u = ubc + 2 * (delay_cols - k);
-                    euler_step(sh, p.Ts, xs, u[0], u[1]);
-                }
+                delay_predict(sh, ShapeCM{}, p.Ts, delay_cols, ubc, xs);
                 if (Xsim) memcpy(Xsim + ((size_t)i * n_steps + t) * 4, xs, sizeof xs);
                 double u[2];
                 tw_out out;
                 const int st = ctrl_lane(&p, &sh, w, xs, traj, T, delay_cols, index0[i] + t + delay_cols, Xw, Uw, PIw,
                                          &valid, u, &out, NULL);
                 /* plant_kernel */
-                if (delay_cols > 0) {
-                    for (int k = delay_cols - 1; k >= 1; --k) { ubc[2 * k] = ubc[2 * (k - 1)]; ubc[2 * k + 1] = ubc[2 * (k - 1) + 1]; }
-                    ubc[0] = u[0];
-                    ubc[1] = u[1];
-                }
-                double ua[2] = {u[0], u[1]};
-                if (plant_delay_cols > 0) {
-                    ua[0] = ubp[2 * (plant_delay_cols - 1)];
-                    ua[1] = ubp[2 * (plant_delay_cols - 1) + 1];
-                    for (int k = plant_delay_cols - 1; k >= 1; --k) { ubp[2 * k] = ubp[2 * (k - 1)]; ubp[2 * k + 1] = ubp[2 * (k - 1) + 1]; }
-                    ubp[0] = u[0];
-                    ubp[1] = u[1];
-                }
+                double ua[2];
+                buffers_step(ubc, delay_cols, ubp, plant_delay_cols, u, ua);
                 euler_step(sh, p.Ts, x, ua[0], ua[1]);
                 memcpy(Utraj + ((size_t)i * n_steps + t) * 2, u, sizeof u);
                 if (Straj) Straj[(size_t)i * n_steps + t] = st;

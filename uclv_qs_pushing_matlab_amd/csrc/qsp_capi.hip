@@ -10,6 +10,7 @@
 
 #include "../../include/qsp_nmpc.h"
 #include "qsp_devbuf.hpp"
+#include "qsp_ipm.hpp"
 #include "qsp_kernels.h"
 
 using namespace qsp;
@@ -83,8 +84,8 @@ struct __attribute__((visibility("hidden"))) qsp_solver {
     int parts_req = 0;
     int fused_req = -1;            // QSP_FUSED_LOOP (-1: auto)
     bool nopack = false;           // QSP_PACKING=0: instances in lane order (developer A/B of the wave packing)
-    bool mfw = true;               // QSP_MFMA_WALK=0: the lane walk wherever the matrix cores would factorise
-                                   // (developer A/B; rounds differently: the oracle twin reads the same variable)
+    bool mfw = true;               // QSP_MFMA_WALK=0: the lane walk wherever the matrix cores would factorise (developer
+                                   // A/B; rounds differently: the oracle twin reads it by the same mfma_walk_default)
     bool fixed_n = true;           // QSP_FIXED_HORIZON=0: the runtime-horizon QP kernel at every N (developer A/B; same bits)
     int cus = 256;                 // compute units of the device (hipDeviceProp multiProcessorCount)
 
@@ -138,34 +139,10 @@ static int kernel_times_of(qsp_solver* s, double* ms, int32_t* launches);
 
 static void fill_params(qsp_solver* s) {
     SolveParams& p = s->p;
-    p.N = s->o.N;
-    p.nlp_mode = s->o.nlp_mode;
-    p.sqp_iters = s->o.sqp_iters;
-    p.qp_iters = s->o.qp_iters;
-    p.Ts = s->o.Ts;
+    params_from_options(p, s->o);   // (qsp_ipm.hpp: the fields the twin's options name alike)
     p.tau = s->o.cost_scale_Ts ? s->o.Ts : 1.0;
-    p.mu0 = s->o.mu0;
-    p.t_min = s->o.t_min;
-    p.frac = s->o.frac;
-    p.sigma_min = s->o.sigma_min;
-    p.mu_stop = s->o.mu_stop;
-    p.res_stop = s->o.res_stop;
-    p.qp_tol_stat = s->o.qp_tol_stat;
-    p.qp_tol_eq = s->o.qp_tol_eq;
-    p.s0_bound = s->o.stage0_s_bound ? 1 : 0;
-    p.factor_scan = s->o.factor_scan ? 1 : 0;
     p.mfma_walk = s->mfw ? 1 : 0;
     mfw_prepare(p);
-    p.qp_stall_iters = s->o.qp_stall_iters;
-    p.qp_stall_alpha = s->o.qp_stall_alpha;
-    p.qp_mu_max = s->o.qp_mu_max;
-    p.tol_stat = s->o.tol_stat;
-    p.tol_eq = s->o.tol_eq;
-    p.tol_ineq = s->o.tol_ineq;
-    p.tol_comp = s->o.tol_comp;
-    p.ls_alpha_min = s->o.ls_alpha_min;
-    p.ls_alpha_red = s->o.ls_alpha_red;
-    p.ls_eps = s->o.ls_eps;
 }
 
 // Binary little-endian PLY with float32 vertex properties (the reference's cad_models/*.ply).
@@ -423,6 +400,7 @@ int qsp_create(const qsp_options* o, qsp_solver** out) {
         if (hipGetDeviceProperties(&prop, o->device) == hipSuccess && prop.multiProcessorCount > 0)
             s->cus = prop.multiProcessorCount;
     }
+    s->mfw = mfma_walk_default() != 0;
     fill_params(s);
     // reference defaults (main.m:82-90, NMPC_controller.m:16-26, 98-100, 251-252)
     const double W[6] = {1.0, 1.0, 1e-3, 0.0, 1e-3, 1e-3};
@@ -443,9 +421,6 @@ int qsp_create(const qsp_options* o, qsp_solver** out) {
     }
     if (const char* fl = std::getenv("QSP_FUSED_LOOP")) s->fused_req = (fl[0] == '1') ? 1 : (fl[0] == '0' ? 0 : -1);
     if (const char* pk = std::getenv("QSP_PACKING")) s->nopack = pk[0] == '0';
-    if (const char* mw = std::getenv("QSP_MFMA_WALK")) s->mfw = mw[0] != '0';
-    s->p.mfma_walk = s->mfw ? 1 : 0;
-    mfw_prepare(s->p);
     if (const char* fh = std::getenv("QSP_FIXED_HORIZON")) s->fixed_n = fh[0] != '0';
     const char* pz = std::getenv("QSP_DEBUG_POISON");
     s->poison = pz && pz[0] == '1';
@@ -598,30 +573,8 @@ static int upload_shapes(qsp_solver* s, const char* who, const qsp_shape* shapes
         const qsp_shape& in = shapes[q];
         if (in.struct_size != (int32_t)sizeof(qsp_shape))
             return fail(QSP_ERR_ARG, w + ": qsp_shape.struct_size != sizeof(qsp_shape) (stale layout?)");
-        ShapeDev& d = h[q];
-        std::memset(&d, 0, sizeof d);
-        const int nc = in.n_ctrl;
-        if (nc < 5 || nc > QSP_MAX_CTRL) return fail(QSP_ERR_ARG, w + ": n_ctrl out of range");
-        d.n = nc;
-        d.b = in.b;
-        d.c = in.c_ellipse;
-        d.mu = in.mu_sp;
-        for (int i = 0; i < nc + 4; ++i) d.knots[i] = in.knots[i];
-        for (int i = 0; i < nc; ++i) { d.ctrl[2 * i] = in.ctrl[i][0]; d.ctrl[2 * i + 1] = in.ctrl[i][1]; }
-        const double h0 = in.knots[4] - in.knots[3];
-        d.inv_h = h0 > 0.0 ? 1.0 / h0 : 0.0;
-        d.xwidth = in.xwidth;
-        // derivative-spline coefficients (bspline_shape.m:92-99 with zero-denominator guard :93)
-        for (int i = 1; i < nc; ++i) {
-            const double den = d.knots[i + 3] - d.knots[i];
-            for (int c = 0; c < 2; ++c)
-                d.dctrl[2 * i + c] = den != 0.0 ? 3.0 * ((d.ctrl[2 * i + c] - d.ctrl[2 * (i - 1) + c]) / den) : 0.0;
-        }
-        for (int i = 2; i < nc; ++i) {
-            const double den = d.knots[i + 2] - d.knots[i];
-            for (int c = 0; c < 2; ++c)
-                d.ddctrl[2 * i + c] = den != 0.0 ? 2.0 * ((d.dctrl[2 * i + c] - d.dctrl[2 * (i - 1) + c]) / den) : 0.0;
-        }
+        if (in.n_ctrl < 5 || in.n_ctrl > QSP_MAX_CTRL) return fail(QSP_ERR_ARG, w + ": n_ctrl out of range");
+        shape_entry(h[q], in.n_ctrl, &in.ctrl[0][0], in.knots, in.b, in.c_ellipse, in.mu_sp, in.xwidth);
     }
     return h2d_grow(s, s->*table, h.data(), h.size());
 }
@@ -1386,11 +1339,7 @@ int qsp_qp_solve(qsp_solver* s, int32_t nb, const double* A, const double* B, co
         return fail(QSP_ERR_ARG, "qsp_qp_solve: bad argument");
     const int N = s->o.N;
     SolveParams p = s->p;
-    p.tau = 1.0;
-    for (int i = 0; i < 6; ++i) p.W[i] = H[i];
-    for (int i = 0; i < 4; ++i) p.We[i] = H[6 * N + i];
-    // bounds in step space lo = lh - v, hi = uh - v with lh = 0, uh = width, v = -lo
-    for (int j = 0; j < 3; ++j) { p.lh[j] = 0.0; p.uh[j] = hi[j] - lo[j]; }
+    qp_level_params(p, H, lo, hi);   // bounds in step space lo = lh - v, hi = uh - v with lh = 0, uh = width, v = -lo
     for (int l = 0; l < nb; ++l) {
         for (int k = 0; k < N; ++k) {
             for (int i = 0; i < 6; ++i)
@@ -1413,7 +1362,7 @@ int qsp_qp_solve(qsp_solver* s, int32_t nb, const double* A, const double* B, co
     // pack the workspace on the host: stage data SoA, v = -lo through X/U, x0 - X_0 = dx0
     const Dims qd{(size_t)nb, (size_t)N};   // the QPs' own batch
     const size_t tot = qd.stages();
-    std::vector<double> lin(qd.lin(), 0.0), X(qd.X(), 0.0), U(qd.U(), 0.0), x0(dx0, dx0 + qd.x0());
+    std::vector<double> lin(qd.lin(), 0.0), X(qd.X()), U(qd.U()), x0(qd.x0());
     for (int l = 0; l < nb; ++l) {
         for (int k = 0; k <= N; ++k) {
             const size_t gi = (size_t)l * (N + 1) + k;
@@ -1424,15 +1373,13 @@ int qsp_qp_solve(qsp_solver* s, int32_t nb, const double* A, const double* B, co
                 for (int f = 0; f < 8; ++f) lin[(L_B + f) * tot + gi] = B[((size_t)l * N + k) * 8 + f];
                 for (int f = 0; f < 4; ++f) lin[(L_BB + f) * tot + gi] = b[((size_t)l * N + k) * 4 + f];
                 for (int f = 0; f < 6; ++f) lin[(L_G + f) * tot + gi] = g[(size_t)l * (6 * N + 4) + 6 * k + f];
-                X[gi * 4 + 3] = -lo[((size_t)l * N + k) * 3 + 0];
-                U[((size_t)l * N + k) * 2 + 0] = -lo[((size_t)l * N + k) * 3 + 1];
-                U[((size_t)l * N + k) * 2 + 1] = -lo[((size_t)l * N + k) * 3 + 2];
             } else {
                 for (int f = 0; f < 4; ++f) lin[(L_G + f) * tot + gi] = g[(size_t)l * (6 * N + 4) + 6 * N + f];
             }
         }
         // dx0 = wx0 - X_0 with X_0 = (0, 0, 0, -lo_s(0))  ->  wx0 = dx0 + X_0
-        x0[(size_t)l * 4 + 3] += X[(size_t)l * (N + 1) * 4 + 3];
+        qp_level_iterate(N, lo + (size_t)l * N * 3, dx0 + (size_t)l * 4, X.data() + (size_t)l * (N + 1) * 4,
+                         U.data() + (size_t)l * N * 2, x0.data() + (size_t)l * 4);
     }
     HIPCHK(hipSetDevice(s->o.device));
     Staging st(s);
@@ -1455,15 +1402,9 @@ int qsp_qp_solve(qsp_solver* s, int32_t nb, const double* A, const double* B, co
     HIPCHK(launch_qp(a, s->S, s->stream));
     if (st.finish()) return st.err;
     if (qp_status) {
-        for (int l = 0; l < nb; ++l) {
-            bool fin = true;
-            for (int q = 0; q < (N + 1) * 4; ++q) fin = fin && std::isfinite(dx[(size_t)l * (N + 1) * 4 + q]);
-            for (int q = 0; q < N * 2; ++q) fin = fin && std::isfinite(du[(size_t)l * N * 2 + q]);
-            // the stage-0 s is fixed (dx_0 = dx0): outside its bounds the QP is infeasible
-            const bool infeas = s->p.s0_bound && (dx0[(size_t)l * 4 + 3] < lo[(size_t)l * N * 3] ||
-                                                  dx0[(size_t)l * 4 + 3] > hi[(size_t)l * N * 3]);
-            qp_status[l] = !fin ? 1 : (infeas ? 3 : qst[l]);
-        }
+        for (int l = 0; l < nb; ++l)
+            qp_status[l] = qp_level_status(p, dx + (size_t)l * (N + 1) * 4, du + (size_t)l * N * 2, lo + (size_t)l * N * 3,
+                                           hi + (size_t)l * N * 3, dx0 + (size_t)l * 4, qst[l]);
     }
     return QSP_OK;
 }

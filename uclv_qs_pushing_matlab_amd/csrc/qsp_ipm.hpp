@@ -1,7 +1,9 @@
 // qsp_ipm.hpp — the per-stage arithmetic of the interior point and of the SQP around it: the bound
 // pairs of a slot (barrier terms, predictor and corrector directions, step), the IPM iteration's
-// exit test, the KKT residuals, merit weights and multiplier update of the merit SQP, the
-// controller's initial guess and its stage-0 feasibility rule.  As qsp_riccati.hpp: straight-line
+// exit test, the KKT residuals, merit weights and multiplier update of the merit SQP; and the per-lane
+// code around a solve: the reference staging, the controller's prologue with its initial guess and
+// stage-0 feasibility rule, the epilogue's cost, status rule and warm-start shift, the parameters from
+// the options and the QP-level entry's mapping and status.  As qsp_riccati.hpp: straight-line
 // functions of one lane's own data, compiled by hipcc into the kernels and by a plain C++ compiler
 // into the CPU twin (oracle/qsp_twin.cpp), which restates only the orchestration around them
 // (the qualifier macro: qsp_fp.hpp).
@@ -251,5 +253,139 @@ QSP_FN void guess_rollout(const ShapeDev& sh, const SolveParams& p, const double
 // With the stage-0 s bound in the QP (stage0_s_bound), s_0 = x0's s is a fixed quantity of every
 // QP: outside [lh_s, uh_s] every QP of the solve is infeasible, and the instance does not iterate.
 QSP_FN bool s0_infeasible(const SolveParams& p, double s0) { return p.s0_bound && !(s0 >= p.lh[0] && s0 <= p.uh[0]); }
+
+// get_y_ref (NMPC_controller.m:307-313) for one controller step of one lane: stage k takes column
+// index_time + k (1-based) of the lane's table (T x 6) as set_reference_trajectory (:425-431) builds it --
+// D = delay_buff_comp zero columns prepended, their u_t-reference row copied from the first real column --
+// clamped to the last column; the terminal reference is the last stage's (:348)
+QSP_FN void stage_yref(const double* traj, int T, int D, int index_time, int N, double* yref, double* ye) {
+    for (int k = 0; k < N; ++k) {
+        int idx = index_time + k;
+        if (idx > T + D) idx = T + D;
+        if (idx < 1) idx = 1;
+        double* out = yref + 6 * k;
+        if (idx <= D) {
+            for (int c = 0; c < 5; ++c) out[c] = 0.0;
+            out[5] = traj[5];
+        } else {
+            for (int c = 0; c < 6; ++c) out[c] = traj[(size_t)(idx - D - 1) * 6 + c];
+        }
+    }
+    for (int c = 0; c < 4; ++c) ye[c] = yref[6 * (N - 1) + c];
+}
+
+// NMPC_controller.solve's prologue (NMPC_controller.m:332-380): x0's contact wrapped into [-b, b), the
+// input guess (cold: u_n at its lower bound, u_t = 0; else the warm start Uw), the state guess rolled out
+QSP_FN void controller_guess(const ShapeDev& sh, const SolveParams& p, bool cold, const double* Uw, double x0[4],
+                             double* U, double* X) {
+    x0[3] = wrap_contact(sh, x0[3]);
+    for (int k = 0; k < p.N; ++k) {
+        U[2 * k] = cold ? p.cp.u_n_lb : Uw[2 * k];
+        U[2 * k + 1] = cold ? 0.0 : Uw[2 * k + 1];
+    }
+    guess_rollout(sh, p, x0, U, X);
+}
+
+// ------------------------------------------------------------------ epilogue
+// 0.5 tau sum_k |y_k - yref_k|^2_W + 0.5 |x_N - ye|^2_We of the returned iterate
+QSP_FN double solve_cost(const SolveParams& p, const double* X, const double* U, const double* yref, const double* ye) {
+    const int N = p.N;
+    double cost = 0.0;
+    for (int k = 0; k < N; ++k) {
+        double s = 0.0;
+        for (int q = 0; q < 4; ++q) { const double r = X[4 * k + q] - yref[6 * k + q]; s = qfma(p.W[q] * r, r, s); }
+        for (int q = 0; q < 2; ++q) { const double r = U[2 * k + q] - yref[6 * k + 4 + q]; s = qfma(p.W[4 + q] * r, r, s); }
+        cost = qfma(0.5 * p.tau, s, cost);
+    }
+    double s = 0.0;
+    for (int q = 0; q < 4; ++q) { const double r = X[4 * N + q] - ye[q]; s = qfma(p.We[q] * r, r, s); }
+    return qfma(0.5, s, cost);
+}
+
+// Is any word of the returned iterate (X, U, and the x0 it was given) not finite?
+QSP_FN bool iterate_nonfinite(int N, const double* X, const double* U, const double x0[4]) {
+    bool bad = false;
+    for (int q = 0; q < 4 * (N + 1); ++q) bad |= !isfinite(X[q]);
+    for (int q = 0; q < 2 * N; ++q) bad |= !isfinite(U[q]);
+    for (int q = 0; q < 4; ++q) bad |= !isfinite(x0[q]);
+    return bad;
+}
+
+// A lane's status (QSP_STATUS_*, qsp_nmpc.h) from its iterate and the SQP's record fr: 0 ran to the end,
+// 1 converged, 2 non-finite QP solution, 3 infeasible stage-0 bound, 4 diverged QP (sqp_iter was written
+// when it stopped; an instance that never stopped counts all of them).  Non-finite wins: a non-finite
+// iterate is QSP_STATUS_NAN (1) whatever its QP did; a failed QP is QSP_STATUS_QP_FAIL (4) only on a
+// finite iterate; the merit SQP that ran to the end is QSP_STATUS_MAXITER (2).
+enum SolveStatus : int { ST_SUCCESS = 0, ST_NAN = 1, ST_MAXITER = 2, ST_QP_FAIL = 4 };   // = QSP_STATUS_* (qsp_solver.hip asserts it)
+QSP_FN int solve_status(const SolveParams& p, bool bad, int fr, int& sqp_iter) {
+    if (fr == 0) sqp_iter = p.sqp_iters;
+    if (bad || fr == 2) return ST_NAN;
+    if (fr == 3 || fr == 4) return ST_QP_FAIL;
+    return (p.nlp_mode == 1 && fr != 1) ? ST_MAXITER : ST_SUCCESS;
+}
+
+// out row k (W doubles) = in row min(k + sh, n - 1): the warm start's shift (NMPC_controller.m:397-399,
+// sh = 1, the last row repeated) or a plain copy (sh = 0).  in's word (row, q) lies at row * rs + q * cs.
+template <int W>
+QSP_FN void shift_rows(int n, int sh, const double* in, size_t rs, size_t cs, double* out) {
+    for (int k = 0; k < n; ++k) {
+        const int src = (k + sh < n) ? k + sh : n - 1;
+        for (int q = 0; q < W; ++q) out[W * k + q] = in[src * rs + q * cs];
+    }
+}
+
+// ------------------------------------------------------------------ options and the QP level (host)
+// The parameters that the library's options (qsp_options) and the twin's (or_opts) name alike.  The
+// caller sets what differs: tau, W, We, lh, uh, cp, mfma_walk.
+template <class O>
+QSP_HD_FN void params_from_options(SolveParams& p, const O& o) {
+    p.N = o.N;
+    p.nlp_mode = o.nlp_mode;
+    p.sqp_iters = o.sqp_iters;
+    p.qp_iters = o.qp_iters;
+    p.Ts = o.Ts;
+    p.mu0 = o.mu0; p.t_min = o.t_min; p.frac = o.frac; p.sigma_min = o.sigma_min; p.mu_stop = o.mu_stop;
+    p.res_stop = o.res_stop; p.qp_tol_stat = o.qp_tol_stat; p.qp_tol_eq = o.qp_tol_eq;
+    p.s0_bound = o.stage0_s_bound ? 1 : 0;
+    p.factor_scan = o.factor_scan ? 1 : 0;
+    p.qp_stall_iters = o.qp_stall_iters; p.qp_stall_alpha = o.qp_stall_alpha; p.qp_mu_max = o.qp_mu_max;
+    p.tol_stat = o.tol_stat; p.tol_eq = o.tol_eq; p.tol_ineq = o.tol_ineq; p.tol_comp = o.tol_comp;
+    p.ls_alpha_min = o.ls_alpha_min; p.ls_alpha_red = o.ls_alpha_red; p.ls_eps = o.ls_eps;
+}
+
+// The QP-level entry on the kernels' parameters: a QP min sum 0.5 z'Hz + g'z, lo <= (ds, du) <= hi is the
+// SQP's QP at tau = 1, W = the stage Hessian, We = the terminal one (H: 6 N + 4 diagonal entries), lh = 0,
+// uh = hi - lo of the first stage (lo, hi: N x 3), around an iterate whose bounded components are v = -lo
+QSP_HD_FN void qp_level_params(SolveParams& p, const double* H, const double* lo, const double* hi) {
+    p.tau = 1.0;
+    for (int i = 0; i < 6; ++i) p.W[i] = H[i];
+    for (int i = 0; i < 4; ++i) p.We[i] = H[6 * p.N + i];
+    for (int j = 0; j < 3; ++j) { p.lh[j] = 0.0; p.uh[j] = hi[j] - lo[j]; }
+}
+// ... that iterate: X (N + 1 x 4) zero but for s_k = -lo_s(k), k < N; U = -lo_u; x0 = dx0 + X_0
+QSP_HD_FN void qp_level_iterate(int N, const double* lo, const double dx0[4], double* X, double* U, double x0[4]) {
+    for (int q = 0; q < 4 * (N + 1); ++q) X[q] = 0.0;
+    for (int k = 0; k < N; ++k) {
+        X[4 * k + 3] = -lo[3 * k];
+        U[2 * k] = -lo[3 * k + 1];
+        U[2 * k + 1] = -lo[3 * k + 2];
+    }
+    for (int q = 0; q < 4; ++q) x0[q] = dx0[q];
+    x0[3] += X[3];
+}
+// the exit's qp_status: 0 stop test met, 2 cap, 4 stall (min step), 5 diverged
+QSP_FN int qp_exit_status(int exit) {
+    return exit == QP_EXIT_CONV ? 0 : (exit == QP_EXIT_CAP ? 2 : (exit == QP_EXIT_STALL ? 4 : 5));
+}
+// ... and the entry's: 1 for a non-finite solution (dx: N + 1 x 4, du: N x 2); else 3 for an infeasible QP
+// (the stage-0 s is fixed, dx_0 = dx0: outside its bounds with s0_bound); else the exit's
+QSP_HD_FN int qp_level_status(const SolveParams& p, const double* dx, const double* du, const double* lo,
+                              const double* hi, const double dx0[4], int exit_status) {
+    bool fin = true;
+    for (int q = 0; q < (p.N + 1) * 4; ++q) fin = fin && __builtin_isfinite(dx[q]);   // (host and device alike)
+    for (int q = 0; q < p.N * 2; ++q) fin = fin && __builtin_isfinite(du[q]);
+    const bool infeas = p.s0_bound && (dx0[3] < lo[0] || dx0[3] > hi[0]);
+    return !fin ? 1 : (infeas ? 3 : exit_status);
+}
 
 }  // namespace qsp

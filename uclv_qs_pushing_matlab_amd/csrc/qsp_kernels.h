@@ -87,7 +87,7 @@ __device__ __forceinline__ const ShapeDev& shape_clamped(const ShapeDev* shapes,
     return shapes[shape_clamp(sid ? sid[i] : 0, n_shapes)];
 }
 
-// QSP_WALK_* of a handle's QP kernels (the launchers' own choice: factor_alt, mfw_use)
+// QSP_WALK_* of a handle's QP kernels (factor_walk_of, qsp_layout.h: the launchers select by it, factor_alt)
 int factor_walk_kind(const SolveParams& p, int S);
 int qp_fixed_horizon(const SolveParams& p, int S, uint32_t flags);   // compiled horizon of the per-iteration QP launches (0: none)
 void mfw_prepare(SolveParams& p);   // SolveParams::mfw_on / mfw_is from N and mfma_walk

@@ -1,12 +1,15 @@
 /* qsp_layout.h — the QP kernels' layout rules, in one place: how instances map onto wavefronts,
- * how many stages a lane holds, the LDS fields of a lane, and which horizons factorise on the
- * matrix cores.  Plain integer arithmetic that compiles as C99 and as HIP C++ (host and device):
+ * how many stages a lane holds, the LDS fields of a lane, which horizons factorise on the
+ * matrix cores and which factorisation a handle takes.  Plain integer arithmetic that compiles as C99 and
+ * as HIP C++ (host and device) -- with one exception, mfma_walk_default at the end: a host-only read of an
+ * environment variable (hence <stdlib.h>), here because the library and the twin must read it alike:
  * qsp_solver.hip and qsp_capi.hip include it, and so does the CPU twin that checks the kernels bit
  * for bit (test infrastructure may read a product header; the product never reads the twin).  The
- * twin reads three more on the same terms, C++ only: qsp_fp.hpp, qsp_math.hpp and qsp_riccati.hpp,
- * the lane-local arithmetic. */
+ * twin reads four more on the same terms, C++ only: qsp_fp.hpp, qsp_math.hpp, qsp_riccati.hpp and
+ * qsp_ipm.hpp, the lane-local arithmetic. */
 #ifndef QSP_LAYOUT_H
 #define QSP_LAYOUT_H
+#include <stdlib.h>
 
 #ifdef __HIPCC__
 #define QSP_LAYOUT_FN __host__ __device__ constexpr
@@ -101,6 +104,21 @@ QSP_LAYOUT_FN int mfw_stride(int CM, int G) {
 QSP_LAYOUT_FN int mfw_fits(int N, int S) {
     const int G = instances_per_wave(N, S), CM = mfw_records(N);
     return G <= 4 && (G - 1) * mfw_stride(CM, G) + CM * MFW_REC + C_COUNT <= mfw_region(S) && (S == 2 || N <= 31);
+}
+/* The factorisation a handle's QP kernels take, in the public QSP_WALK_* coding (qsp_nmpc.h): at two
+ * stages per lane the associative scan where factor_scan asks for it, else the matrix cores where
+ * mfma_walk allows them and the records fit, else the lane walk.  The kernels' launchers select by it
+ * (factor_alt, qsp_solver.hip) and the twin emulates what it names. */
+enum FactorWalk { WALK_LANE = 0, WALK_MFMA = 1, WALK_SCAN = 2 };
+QSP_LAYOUT_FN int factor_walk_of(int N, int S, int mfma_walk, int factor_scan) {
+    return (S != 1 && S != 2) ? WALK_LANE : (S == 2 && factor_scan) ? WALK_SCAN
+         : (mfma_walk && mfw_fits(N, S)) ? WALK_MFMA : WALK_LANE;
+}
+/* SolveParams::mfma_walk of a new handle (host): on, unless the developer switch QSP_MFMA_WALK=0
+ * selects the lane walk wherever the matrix cores would factorise (an A/B that rounds differently) */
+static inline int mfma_walk_default(void) {
+    const char *mw = getenv("QSP_MFMA_WALK");
+    return !(mw && mw[0] == '0');
 }
 
 #ifdef __cplusplus

@@ -456,4 +456,91 @@ QSP_FN void rk4(const ShapeDev& sh, double h, const double x[4], const double u[
     }
 }
 
+// ---------------------------------------------------------------- around the model
+// What the library and the twin both do with the model outside a solve, stated once: the shape table's
+// entries, the closed loop's per-lane steps around the controller (helper.m:195-322) and the
+// building-block entries' output layout.
+
+// A shape table entry from its nc control points P (x, y pairs), nc + 4 knots S and constants: the
+// derivative-spline coefficients (bspline_shape.m:92-99 with the zero-denominator guard :93).  Host.
+QSP_HD_FN void shape_entry(ShapeDev& d, int nc, const double* P, const double* S, double b, double c, double mu,
+                           double xwidth) {
+    d = ShapeDev{};
+    d.n = nc;
+    d.b = b;
+    d.c = c;
+    d.mu = mu;
+    d.xwidth = xwidth;
+    for (int i = 0; i < nc + 4; ++i) d.knots[i] = S[i];
+    for (int i = 0; i < 2 * nc; ++i) d.ctrl[i] = P[i];
+    const double h0 = S[4] - S[3];
+    d.inv_h = h0 > 0.0 ? 1.0 / h0 : 0.0;
+    for (int i = 1; i < nc; ++i) {
+        const double den = d.knots[i + 3] - d.knots[i];
+        for (int c2 = 0; c2 < 2; ++c2)
+            d.dctrl[2 * i + c2] = den != 0.0 ? 3.0 * ((d.ctrl[2 * i + c2] - d.ctrl[2 * (i - 1) + c2]) / den) : 0.0;
+    }
+    for (int i = 2; i < nc; ++i) {
+        const double den = d.knots[i + 2] - d.knots[i];
+        for (int c2 = 0; c2 < 2; ++c2)
+            d.ddctrl[2 * i + c2] = den != 0.0 ? 2.0 * ((d.dctrl[2 * i + c2] - d.dctrl[2 * (i - 1) + c2]) / den) : 0.0;
+    }
+}
+
+// The disturbance (helper.m:224-234): y += amp; the new contact is the spline point nearest
+// (-xwidth/2, C_y(s) - amp), searched from s0_spline = 0 (one disturbance per run), wrapped into [-b, b)
+QSP_FN void disturb_contact(const ShapeDev& sh, double amp, double x[4]) {
+    x[1] += amp;
+    SplineEval e;
+    spline_eval(sh, mat_mod(x[3], sh.b), e);
+    const double sn = reproject_contact(sh, -0.5 * sh.xwidth, e.C[1] - amp, 0.0);
+    x[3] = wrap_contact(sh, sn);
+}
+
+// delay_buffer_sim (NMPC_controller.m:112-120): D Euler steps of x with the buffered inputs b (D x 2,
+// column 0 the newest), the oldest (u_buff_contr(:, end)) first
+template <class CM>
+QSP_FN void delay_predict(const ShapeDev& sh, const CM& cm, double Ts, int D, const double* b, double x[4]) {
+    for (int k = 1; k <= D; ++k) euler_step_cm(sh, cm, Ts, x, b[2 * (D - k)], b[2 * (D - k) + 1]);
+}
+
+// b = [u, b(:, 1:end-1)] on an input buffer of D >= 1 columns
+QSP_FN void buffer_push(double* b, int D, const double u[2]) {
+    for (int k = D - 1; k >= 1; --k) { b[2 * k] = b[2 * (k - 1)]; b[2 * k + 1] = b[2 * (k - 1) + 1]; }
+    b[0] = u[0];
+    b[1] = u[1];
+}
+
+// The input buffers after a solve (helper.m:255, :289-307): the controller's (D columns) takes u; the plant
+// applies ua = u, or with a delay of its own (Dp columns) the oldest column of its buffer, which then takes u
+QSP_FN void buffers_step(double* ubc, int D, double* ubp, int Dp, const double u[2], double ua[2]) {
+    if (D > 0) buffer_push(ubc, D, u);
+    ua[0] = u[0];
+    ua[1] = u[1];
+    if (Dp > 0) {
+        ua[0] = ubp[2 * (Dp - 1)];
+        ua[1] = ubp[2 * (Dp - 1) + 1];
+        buffer_push(ubp, Dp, u);
+    }
+}
+
+// Output layout of the dynamics entry: f (4) and J (4 x 6, columns x y theta s u_n u_t)
+QSP_FN void pack_dynamics(const DynOut& d, double* f, double* J) {
+    for (int r = 0; r < 4; ++r) {
+        f[r] = d.f[r];
+        double* Jr = J + 6 * r;
+        Jr[0] = 0.0; Jr[1] = 0.0;
+        Jr[2] = r < 2 ? d.Jth[r] : 0.0;
+        Jr[3] = d.Js[r]; Jr[4] = d.Jun[r]; Jr[5] = d.Jut[r];
+    }
+}
+
+// ... and of the integrator entry: x+ (4), the full A (4 x 4, row-major) from its six free entries, B (4 x 2)
+QSP_FN void pack_lin(const Lin& L, double* xn, double* A, double* B) {
+    const double Af[16] = {1.0, 0.0, L.a[0], L.a[1], 0.0, 1.0, L.a[2], L.a[3], 0.0, 0.0, 1.0, L.a[4], 0.0, 0.0, 0.0, L.a[5]};
+    for (int q = 0; q < 16; ++q) A[q] = Af[q];
+    for (int q = 0; q < 8; ++q) B[q] = L.B[q];
+    for (int q = 0; q < 4; ++q) xn[q] = L.xn[q];
+}
+
 }  // namespace qsp

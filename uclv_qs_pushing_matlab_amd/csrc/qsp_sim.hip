@@ -19,7 +19,7 @@
 #include <stdint.h>
 
 #include "../../include/qsp_nmpc.h"
-#include "qsp_math.hpp"
+#include "qsp_ipm.hpp"
 #include "qsp_kernels.h"
 #include "qsp_noise.hpp"
 
@@ -48,15 +48,6 @@ __device__ __forceinline__ PlantModel plant_of(const ClosedLoopArgs& a, int i) {
     return PlantModel{&sh, LaneCM{a.pc ? a.pc[i] : sh.c, a.pmu ? a.pmu[i] : sh.mu}};
 }
 
-// delay_buffer_sim (NMPC_controller.m:112-120): D Euler steps of lane i's x with the buffered inputs,
-// oldest (u_buff_contr(:, end)) first
-__device__ __forceinline__ void delay_predict(const ClosedLoopArgs& a, const PlantModel& pm, int i, double x[4]) {
-    for (int k = 1; k <= a.D; ++k) {
-        const double* u = a.ubc + ((size_t)i * a.D + (a.D - k)) * 2;
-        euler_step_cm(*pm.sh, pm.cm, a.Ts, x, u[0], u[1]);
-    }
-}
-
 __global__ void closed_loop_pre_kernel(ClosedLoopArgs a, int t) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.B) return;
@@ -64,14 +55,7 @@ __global__ void closed_loop_pre_kernel(ClosedLoopArgs a, int t) {
     const ShapeDev& sh = *pm.sh;
     double x[4] = {a.x[(size_t)i * 4], a.x[(size_t)i * 4 + 1], a.x[(size_t)i * 4 + 2], a.x[(size_t)i * 4 + 3]};
     if (a.dist_step > 0 && t + 1 == a.dist_step) {
-        // y += amplitude; new contact: the spline point nearest (-xwidth/2, C_y(s) - amplitude),
-        // from s0_spline = 0 (one disturbance per run), wrapped into [-b, b) (:224-234)
-        const double amp = a.dist_amp ? a.dist_amp[i] : 0.0;
-        x[1] += amp;
-        SplineEval e;
-        spline_eval(sh, mat_mod(x[3], sh.b), e);
-        const double sn = reproject_contact(sh, -0.5 * sh.xwidth, e.C[1] - amp, 0.0);
-        x[3] = wrap_contact(sh, sn);
+        disturb_contact(sh, a.dist_amp ? a.dist_amp[i] : 0.0, x);   // :224-234
     }
     if (a.noise) {
         for (int c = 0; c < 4; ++c) x[c] += a.noise[((size_t)t * a.B + i) * 4 + c];
@@ -84,7 +68,7 @@ __global__ void closed_loop_pre_kernel(ClosedLoopArgs a, int t) {
         a.x[(size_t)i * 4 + c] = x[c];
         if (a.Xtraj) a.Xtraj[((size_t)i * (a.n_steps + 1) + t) * 4 + c] = x[c];
     }
-    delay_predict(a, pm, i, x);
+    delay_predict(*pm.sh, pm.cm, a.Ts, a.D, a.ubc + (size_t)i * a.D * 2, x);   // delay_buffer_sim
     for (int c = 0; c < 4; ++c) a.xs[(size_t)i * 4 + c] = x[c];
     if (a.Xsim)
         for (int c = 0; c < 4; ++c) a.Xsim[((size_t)i * a.n_steps + t) * 4 + c] = x[c];
@@ -129,22 +113,8 @@ __global__ void plant_kernel(ClosedLoopArgs a, int t) {
     const PlantModel pm = plant_of(a, i);
     double xi[4] = {a.x[(size_t)i * 4], a.x[(size_t)i * 4 + 1], a.x[(size_t)i * 4 + 2], a.x[(size_t)i * 4 + 3]};
     const double u[2] = {a.u0[(size_t)i * 2], a.u0[(size_t)i * 2 + 1]};
-    // u_buff_contr = [u, u_buff_contr(:, 1:end-1)]
-    if (a.D > 0) {
-        double* b = a.ubc + (size_t)i * a.D * 2;
-        for (int k = a.D - 1; k >= 1; --k) { b[2 * k] = b[2 * (k - 1)]; b[2 * k + 1] = b[2 * (k - 1) + 1]; }
-        b[0] = u[0];
-        b[1] = u[1];
-    }
-    double ua[2] = {u[0], u[1]};
-    if (a.Dp > 0) {   // the plant applies u_buff_plant(:, end), then pushes u
-        double* b = a.ubp + (size_t)i * a.Dp * 2;
-        ua[0] = b[2 * (a.Dp - 1)];
-        ua[1] = b[2 * (a.Dp - 1) + 1];
-        for (int k = a.Dp - 1; k >= 1; --k) { b[2 * k] = b[2 * (k - 1)]; b[2 * k + 1] = b[2 * (k - 1) + 1]; }
-        b[0] = u[0];
-        b[1] = u[1];
-    }
+    double ua[2];   // u_buff_contr takes u; the plant applies u or u_buff_plant(:, end), which then takes u
+    buffers_step(a.ubc + (size_t)i * a.D * 2, a.D, a.ubp + (size_t)i * a.Dp * 2, a.Dp, u, ua);
     double xn[4] = {xi[0], xi[1], xi[2], xi[3]};   // the metrics read the state before the step too
     euler_step_cm(*pm.sh, pm.cm, a.Ts, xn, ua[0], ua[1]);
     for (int c = 0; c < 4; ++c) {
@@ -165,7 +135,7 @@ __global__ void delay_sim_kernel(ClosedLoopArgs a) {
     if (i >= a.B) return;
     const PlantModel pm = plant_of(a, i);
     double x[4] = {a.x[(size_t)i * 4], a.x[(size_t)i * 4 + 1], a.x[(size_t)i * 4 + 2], a.x[(size_t)i * 4 + 3]};
-    delay_predict(a, pm, i, x);
+    delay_predict(*pm.sh, pm.cm, a.Ts, a.D, a.ubc + (size_t)i * a.D * 2, x);   // delay_buffer_sim
     for (int c = 0; c < 4; ++c) a.xs[(size_t)i * 4 + c] = x[c];
 }
 
@@ -332,13 +302,7 @@ __global__ void dynamics_kernel(const ShapeDev* shapes, const int32_t* sid, int 
     const ShapeDev& sh = shapes[sid[i]];
     DynOut d;
     dynamics<true>(sh, x[4 * i + 2], x[4 * i + 3], u[2 * i], u[2 * i + 1], d);
-    for (int r = 0; r < 4; ++r) {
-        f[4 * i + r] = d.f[r];
-        double* Jr = J + (size_t)24 * i + 6 * r;
-        Jr[0] = 0.0; Jr[1] = 0.0;
-        Jr[2] = r < 2 ? d.Jth[r] : 0.0;
-        Jr[3] = d.Js[r]; Jr[4] = d.Jun[r]; Jr[5] = d.Jut[r];
-    }
+    pack_dynamics(d, f + 4 * i, J + (size_t)24 * i);
 }
 
 __global__ void rk4_kernel(const ShapeDev* shapes, const int32_t* sid, int n, double h, const double* x, const double* u,
@@ -350,12 +314,7 @@ __global__ void rk4_kernel(const ShapeDev* shapes, const int32_t* sid, int n, do
     double ui[2] = {u[2 * i], u[2 * i + 1]};
     Lin L;
     rk4<true>(sh, h, xi, ui, L);
-    double* Ai = Aout + (size_t)16 * i;
-    const double Afull[16] = {1.0, 0.0, L.a[0], L.a[1], 0.0, 1.0, L.a[2], L.a[3],
-                              0.0, 0.0, 1.0, L.a[4], 0.0, 0.0, 0.0, L.a[5]};
-    for (int q = 0; q < 16; ++q) Ai[q] = Afull[q];
-    for (int q = 0; q < 8; ++q) Bout[(size_t)8 * i + q] = L.B[q];
-    for (int q = 0; q < 4; ++q) xn[4 * i + q] = L.xn[q];
+    pack_lin(L, xn + 4 * i, Aout + (size_t)16 * i, Bout + (size_t)8 * i);
 }
 
 __global__ void vbound_kernel(const ShapeDev* shapes, const int32_t* sid, int n, CtrlParams cp, const double* s,
@@ -396,23 +355,7 @@ __global__ void stage_yref_kernel(const double* traj, int T, int per_lane, const
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= B) return;
     if (per_lane) traj += (size_t)i * T * 6;
-    // column index_time+k (1-based) of the table as set_reference_trajectory (:425-431) builds it --
-    // D = delay_buff_comp zero columns prepended, their u_t-reference row copied from the first real
-    // column -- clamped to the last column
-    for (int k = 0; k < N; ++k) {
-        int idx = index_time[i] + offset + k;
-        if (idx > T + D) idx = T + D;
-        if (idx < 1) idx = 1;
-        double* out = yref + ((size_t)i * N + k) * 6;
-        if (idx <= D) {
-            for (int c = 0; c < 5; ++c) out[c] = 0.0;
-            out[5] = traj[5];
-        } else {
-            for (int c = 0; c < 6; ++c) out[c] = traj[(size_t)(idx - D - 1) * 6 + c];
-        }
-    }
-    // terminal reference = last stage reference (:348)
-    for (int c = 0; c < 4; ++c) yref_e[(size_t)i * 4 + c] = yref[((size_t)i * N + N - 1) * 6 + c];
+    qsp::stage_yref(traj, T, D, index_time[i] + offset, N, yref + (size_t)i * N * 6, yref_e + (size_t)i * 4);
 }
 
 hipError_t qsp::launch_stage_yref(const double* traj, int T, int per_lane, const int32_t* index_time, int offset, int D,

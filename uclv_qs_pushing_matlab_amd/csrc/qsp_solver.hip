@@ -1224,15 +1224,10 @@ __global__ void prologue_kernel(SolveArgs A) {
         s0_feasible(A, i, x0[3]);
         return;
     }
-    x0[3] = wrap_contact(sh, x0[3]);   // :332
-    for (int c = 0; c < 4; ++c) A.wx0[(size_t)i * 4 + c] = x0[c];
     const bool cold = (A.warm_valid == nullptr || A.warm_valid[i] == 0);
+    controller_guess(sh, p, cold, A.U_in + (size_t)i * N * 2, x0, U, X);    // :332, :351-380
+    for (int c = 0; c < 4; ++c) A.wx0[(size_t)i * 4 + c] = x0[c];
     if (p.nlp_mode == 1) nlp_init(A, i, !cold);                             // :351-355 (PI = 0 cold)
-    for (int k = 0; k < N; ++k) {                                            // :351-355
-        U[2 * k] = cold ? p.cp.u_n_lb : A.U_in[((size_t)i * N + k) * 2];
-        U[2 * k + 1] = cold ? 0.0 : A.U_in[((size_t)i * N + k) * 2 + 1];
-    }
-    guess_rollout(sh, p, x0, U, X);                                          // :357-380
     s0_feasible(A, i, x0[3]);
 }
 
@@ -1339,7 +1334,11 @@ __device__ __forceinline__ bool qp_outcome(const SolveArgs& A, const Ctx& c, con
 // bit identity to the per-iteration launches rests on both computing the same.  The linearisation's
 // stage load and dx0 are still written out in both, and the stage load a third time in the twin's
 // load_stage: as one function it costs the SQP kernels up to 15 VGPRs (profiles/ipm_shared/README.md),
-// so the three must be edited together.
+// so the three must be edited together.  Written out in the kernels and in the twin besides, for the
+// reasons measured there: qp_ipm's start point, its t.lm sum and centring scalar (twin: qp_ipm), and
+// merit_ls_kernel's directional-derivative term (twin: merit_ls).  Everything else per-lane around the
+// solve -- prologue, status, shift, cost, staging, the closed loop's steps -- is one function in
+// qsp_math.hpp or qsp_ipm.hpp that both sides call (profiles/wrapper_shared/README.md).
 // debug (QSP_FLAG_POISON): this thread's LDS column filled with NaN
 template <int S>
 __device__ __forceinline__ void poison_lds(double* col) {
@@ -1534,9 +1533,7 @@ __global__ void __launch_bounds__(BLOCK, QSP_MIN_WAVES) qp_step_kernel(SolveArgs
                 for (int q = 0; q < 6; ++q) A.qp_lam[((size_t)iv * N + k) * 6 + q] = st.lm(ls, q);
             }
             if (k == 0) A.qp_iter[iv] = nit;
-            // QP status: 0 stop test met, 2 cap, 4 stall (min step), 5 diverged (qsp_qp_solve)
-            if (k == 0 && A.qp_capped)
-                A.qp_capped[iv] = exit == QP_EXIT_CONV ? 0 : (exit == QP_EXIT_CAP ? 2 : (exit == QP_EXIT_STALL ? 4 : 5));
+            if (k == 0 && A.qp_capped) A.qp_capped[iv] = qp_exit_status(exit);   // (qsp_qp_solve)
         }
         return;
     }
@@ -1833,6 +1830,8 @@ __global__ void __launch_bounds__(64) merit_ls_kernel(SolveArgs A) {
 }
 
 // status, cost, u0 and the (optionally shifted, NMPC_controller.m:397-399) outputs.
+static_assert(QSP_STATUS_SUCCESS == ST_SUCCESS && QSP_STATUS_NAN == ST_NAN && QSP_STATUS_MAXITER == ST_MAXITER &&
+              QSP_STATUS_QP_FAIL == ST_QP_FAIL, "solve_status (qsp_ipm.hpp) returns the public QSP_STATUS_*");
 __global__ void epilogue_kernel(SolveArgs A) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= A.B) return;
@@ -1842,49 +1841,19 @@ __global__ void epilogue_kernel(SolveArgs A) {
     const double* U = A.wU + (size_t)i * N * 2;
     const double* yref = A.yref + (size_t)i * N * 6;
     const double* ye = A.yref_e + (size_t)i * 4;
-    bool bad = false;
-    double cost = 0.0;
-    for (int k = 0; k < N; ++k) {
-        double s = 0.0;
-        for (int q = 0; q < 4; ++q) { const double r = X[4 * k + q] - yref[6 * k + q]; s = qfma(p.W[q] * r, r, s); bad |= !isfinite(X[4 * k + q]); }
-        for (int q = 0; q < 2; ++q) { const double r = U[2 * k + q] - yref[6 * k + 4 + q]; s = qfma(p.W[4 + q] * r, r, s); bad |= !isfinite(U[2 * k + q]); }
-        cost = qfma(0.5 * p.tau, s, cost);
-    }
-    double s = 0.0;
-    for (int q = 0; q < 4; ++q) { const double r = X[4 * N + q] - ye[q]; s = qfma(p.We[q] * r, r, s); bad |= !isfinite(X[4 * N + q]); }
-    cost = qfma(0.5, s, cost);
-    A.cost[i] = cost;
-    for (int q = 0; q < 4; ++q) bad |= !isfinite(A.wx0[(size_t)i * 4 + q]);   // x0 is part of the returned iterate
-    // wdone: 1 converged, 2 non-finite QP solution, 3 infeasible stage-0 bound, 4 diverged QP
-    // (sqp_iter written then).  Non-finite wins (qsp_nmpc.h, QSP_STATUS_*): a non-finite iterate is
-    // QSP_STATUS_NAN whatever its QP did; a failed QP is QSP_STATUS_QP_FAIL only on a finite iterate.
-    const int fr = A.wdone ? A.wdone[i] : 0;
-    if (bad || fr == 2) A.status[i] = QSP_STATUS_NAN;
-    else if (fr == 3 || fr == 4) A.status[i] = QSP_STATUS_QP_FAIL;
-    else if (p.nlp_mode == 1) A.status[i] = fr == 1 ? 0 : 2;
-    else A.status[i] = 0;
-    if (fr == 0) A.sqp_iter[i] = p.sqp_iters;
+    A.cost[i] = solve_cost(p, X, U, yref, ye);
+    // x0 is part of the returned iterate; the SQP's record wdone: solve_status (qsp_ipm.hpp)
+    const bool bad = iterate_nonfinite(N, X, U, A.wx0 + (size_t)i * 4);
+    A.status[i] = solve_status(p, bad, A.wdone ? A.wdone[i] : 0, A.sqp_iter[i]);
     A.u0[(size_t)i * 2] = U[0];
     A.u0[(size_t)i * 2 + 1] = U[1];
     const int sh = (A.flags & QSP_FLAG_SHIFT) ? 1 : 0;
-    double* Xo = A.X_out + (size_t)i * (N + 1) * 4;
-    double* Uo = A.U_out + (size_t)i * N * 2;
-    for (int k = 0; k <= N; ++k) {
-        const int src = (k + sh <= N) ? k + sh : N;
-        for (int q = 0; q < 4; ++q) Xo[4 * k + q] = X[4 * src + q];
-    }
-    for (int k = 0; k < N; ++k) {
-        const int src = (k + sh < N) ? k + sh : N - 1;
-        for (int q = 0; q < 2; ++q) Uo[2 * k + q] = U[2 * src + q];
-    }
+    shift_rows<4>(N + 1, sh, X, 4, 1, A.X_out + (size_t)i * (N + 1) * 4);
+    shift_rows<2>(N, sh, U, 2, 1, A.U_out + (size_t)i * N * 2);
     if (p.nlp_mode == 1) {
         // dynamics multipliers of the NLP iterate (shifted like X/U in controller mode)
         const size_t tot = (size_t)A.B * (N + 1);
-        double* Po = A.PI_out + (size_t)i * N * 4;
-        for (int k = 0; k < N; ++k) {
-            const int src = (k + sh < N) ? k + sh : N - 1;
-            for (int q = 0; q < 4; ++q) Po[4 * k + q] = A.wnlp[(W_PI + q) * tot + (size_t)i * (N + 1) + src];
-        }
+        shift_rows<4>(N, sh, A.wnlp + W_PI * tot + (size_t)i * (N + 1), 1, tot, A.PI_out + (size_t)i * N * 4);
     }
     if (p.nlp_mode == 0 && A.wadjv && A.wadjv[i] != 0) {
         // dynamics multipliers of the last successful QP, once per solve; an instance without
@@ -1922,14 +1891,11 @@ static hipError_t launch_qp_waves(const SolveArgs& a, hipStream_t stream, Extra.
 // The kernel variant of a handle.  ALT is the alternative factorisation of the stage count: at one
 // stage per lane the walk on the matrix cores (mfw_use), at two the associative scan
 // (SolveParams::factor_scan); two stages per lane take the matrix cores inside the kernel (mfw_use).
-// Every launcher selects through factor_alt / with_variant, and factor_walk_kind reports from it.
-static bool factor_alt(const SolveParams& p, int S) { return S == 1 ? mfw_use(p, 1) : p.factor_scan != 0; }
-
-int factor_walk_kind(const SolveParams& p, int S) {
-    if (S != 1 && S != 2) return QSP_WALK_LANE;
-    if (factor_alt(p, S)) return S == 1 ? QSP_WALK_MFMA : QSP_WALK_SCAN;
-    return mfw_use(p, S) ? QSP_WALK_MFMA : QSP_WALK_LANE;
-}
+// Which factorisation that is: factor_walk_of (qsp_layout.h), the rule the twin follows too.  Every launcher
+// selects through factor_alt / with_variant.
+static_assert(QSP_WALK_LANE == WALK_LANE && QSP_WALK_MFMA == WALK_MFMA && QSP_WALK_SCAN == WALK_SCAN, "QSP_WALK_*");
+int factor_walk_kind(const SolveParams& p, int S) { return factor_walk_of(p.N, S, p.mfma_walk, p.factor_scan); }
+static bool factor_alt(const SolveParams& p, int S) { return factor_walk_kind(p, S) == (S == 1 ? WALK_MFMA : WALK_SCAN); }
 
 // f(S, ALT) with the handle's variant as compile-time constants
 template <class F>

@@ -66,6 +66,13 @@ enum LdsField {
  * A record, row-major in the order the block lanes read it: */
 enum MfwSlot { R_G = 0, R_A = 12, R_GX = 18, R_HX3 = 22, R_HU = 23, R_GU = 25, MFW_REC = 27 };
 enum MfwOut { O_K = 0, O_Z = 8, O_COUNT = 16 };   /* K (2 x 4), rows 0, 1 of Z = [R~ | r~ | .] */
+/* Where the block lane of matrix row r, column cc stores its element of K and of Z in its stage's record.
+ * Rows 0, 1 hold the outputs and store them to their slots.  Rows 2, 3 hold nothing the stage lane collects;
+ * at one stage per lane they store too, so that the step's stores run on the whole wave without a change of
+ * the exec mask, to dump slots O_COUNT .. O_COUNT + 7: operand slots of the same record, which the walk read
+ * one step ahead and reads never again, and which the record's next publish rewrites with the rest of it. */
+QSP_LAYOUT_FN int mfw_store_k(int r, int cc) { return r < 2 ? O_K + 4 * r + cc : O_COUNT + 4 * (r - 2) + cc; }
+QSP_LAYOUT_FN int mfw_store_z(int r, int cc) { return r < 2 ? O_Z + 4 * r + cc : O_COUNT + 4 * (r - 2) + cc; }
 /* the operand constants (A's ones and zeros, the zero column of [B | b | 0], Hx's fixed diagonal),
  * at the end of the region */
 enum MfwConst { C_ONE = 0, C_ZERO = 1, C_HX = 2, C_COUNT = 5 };

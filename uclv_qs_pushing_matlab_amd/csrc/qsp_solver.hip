@@ -356,8 +356,7 @@ __device__ __forceinline__ void factor_walk_mfma(const Ctx& c, const SolveParams
     int l = c.lane;
     asm volatile("" : "+v"(l));
     const int b = (l >> 2) & 3, r = l >> 4, cc = l & 3;
-    const int bg = b < G ? b : G - 1;
-    const bool wr = b < G;
+    const int bg = b < G ? b : G - 1;   // a block beyond the wave's instances walks the last one again, bit for bit
     // each operand element's record slot (-1: a structural constant, read from the constant slots instead)
     int ao = -1;
     if (cc >= 2 && r < 2) ao = R_A + 2 * r + (cc - 2);
@@ -439,10 +438,22 @@ __device__ __forceinline__ void factor_walk_mfma(const Ctx& c, const SolveParams
             pv = cc == 2 ? rb[(N - kb) * MFW_REC + R_GX + r] : 0.0;   // p_N = g_N (column 2)
         }
         const int kf = ph == 0 ? N - 1 : H - 1;
+        // Where a lane stores its element of K and of Z in the phase's first record (mfw_store_k, mfw_store_z:
+        // qsp_layout.h).  At one stage per lane every lane stores: the stores need no exec mask and the closing
+        // products are free to pass them: rows 0, 1 to the output slots; rows 2, 3 to dump slots among the
+        // record's operand slots 16 .. 23, dead by then (all of record k is read one step before step k runs, by
+        // the prefetch below, and only slots 0 .. 15 are read again, by the collect; the terminal record, whose
+        // p_N is read above, is never stored to); a duplicate block (b >= G) to the addresses of the block it
+        // repeats, with the same values.
+        // (indexed by the step's offset, constant where the horizon is compiled in: pointers stepping one record
+        // down per step make the compiler roll that kernel's walk again.  Two stages per lane keep the lane
+        // test: that kernel's registers are full, and each form of the full-wave stores tried costs
+        // qp_step_kernel<2, false, true, false> 68 bytes of scratch -- scripts/kres.sh)
+        double* const wk = reg + bg * IS + mfw_store_k(r, cc);
+        double* const wz = reg + bg * IS + mfw_store_z(r, cc);
         // one step of the walk from its operand elements (Am: A, G2: [B | b | 0], CH and CZ: the C operands
         // of Q and Z, gq: gx); p lives in column 2 of pv, zero in the others, so T2 takes it as its C operand
         auto step = [&](int k, double Am, double G2, double CH, double CZ, double gq) {
-            double* rk = reg + bg * IS + (k - kb) * MFW_REC;
             const double T1 = mfma4(P, Am, 0.0);                    // P'A
             const double T2 = mfma4(P, G2, pv);                     // P'[B | b | 0] + [0 | 0 | p | 0]
             const double Y = mfma4(G2, T1, 0.0);                    // rows 0, 1: S~ = B'P'A
@@ -465,9 +476,15 @@ __device__ __forceinline__ void factor_walk_mfma(const Ctx& c, const SolveParams
             const double Kf = Ka * (r < 2 ? idet : 0.0);            // rows 0, 1: K; rows 2, 3: 0
             // (rows 2, 3 hold no R~: their idet is not finite, and Kf's zero rows enter P and p)
             // stage k's K and [R~ | r~] over the record's first slots (its operands are already read)
-            if (wr && r < 2) {
-                rk[O_K + 4 * r + cc] = Kf;
-                rk[O_Z + 4 * r + cc] = Z;
+            if constexpr (S == 1) {
+                wk[(k - kb) * MFW_REC] = Kf;
+                wz[(k - kb) * MFW_REC] = Z;
+            } else {
+                double* rk = reg + bg * IS + (k - kb) * MFW_REC;
+                if (b < G && r < 2) {
+                    rk[O_K + 4 * r + cc] = Kf;
+                    rk[O_Z + 4 * r + cc] = Z;
+                }
             }
             if (k > 0) {   // P_k, p_k (nothing reads P_0, p_0)
                 // P keeps its upper triangle and takes the lower one from the transposed products

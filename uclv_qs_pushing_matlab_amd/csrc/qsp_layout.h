@@ -121,6 +121,83 @@ QSP_LAYOUT_FN int factor_walk_of(int N, int S, int mfma_walk, int factor_scan) {
     return (S != 1 && S != 2) ? WALK_LANE : (S == 2 && factor_scan) ? WALK_SCAN
          : (mfma_walk && mfw_fits(N, S)) ? WALK_MFMA : WALK_LANE;
 }
+/* ------------------------------------------------------------------ lane masks
+ * Which lanes of a wavefront pass each geometric test of the QP kernels, as a 64-bit mask (bit l: lane l).
+ * Where the horizon is compiled in, the kernel takes these constants as scalar exec masks instead of
+ * comparing per lane.  Every mask restates today's per-lane expression with lig = lane - (lane / L) L, on
+ * the padding lanes behind the last whole instance (lane / L == G) as well: they get what the
+ * expression gives them.  tests/test_lane_masks.py compares each with its predicate on all 64 lanes. */
+typedef unsigned long long lane_mask_t;
+/* lo <= lig <= hi */
+QSP_LAYOUT_FN lane_mask_t lane_mask_lig_in(int N, int S, int lo, int hi) {
+    lane_mask_t m = 0;
+    for (int l = 0; l < WAVE; ++l) {
+        const int lig = l % lanes_per_instance(N, S);
+        if (lig >= lo && lig <= hi) m |= 1ull << l;
+    }
+    return m;
+}
+QSP_LAYOUT_FN lane_mask_t lane_mask_lig_eq(int N, int S, int j) { return lane_mask_lig_in(N, S, j, j); }
+/* the backward lane walks' step j: lig <= j */
+QSP_LAYOUT_FN lane_mask_t lane_mask_lig_le(int N, int S, int j) { return lane_mask_lig_in(N, S, 0, j); }
+/* the forward lane walks' step j: j <= lig < L - 1 */
+QSP_LAYOUT_FN lane_mask_t lane_mask_walk_fwd(int N, int S, int j) {
+    return lane_mask_lig_in(N, S, j, lanes_per_instance(N, S) - 2);
+}
+/* From one step of a walk to the next the lanes with lig == j leave: mask(j -+ 1) = mask(j) & ~eq(j), and
+ * eq(j) = eq(0) << j for j <= L - 1 (a group's bit stays inside the group; the padding lanes' falls off the
+ * wave where they have no such lane) -- two scalar operations per step, none where j is a constant. */
+QSP_LAYOUT_FN lane_mask_t lane_mask_leave(lane_mask_t m, lane_mask_t first, int j) { return m & ~(first << j); }
+/* the sum tree's level off: lig + off < L */
+QSP_LAYOUT_FN lane_mask_t lane_mask_tree(int N, int S, int off) {
+    return lane_mask_lig_in(N, S, 0, lanes_per_instance(N, S) - 1 - off);
+}
+/* stage roles at one stage per lane: lig == 0; lig < N (a stage with a control) */
+QSP_LAYOUT_FN lane_mask_t lane_mask_first(int N, int S) { return lane_mask_lig_eq(N, S, 0); }
+QSP_LAYOUT_FN lane_mask_t lane_mask_stage(int N, int S) { return lane_mask_lig_in(N, S, 0, N - 1); }
+/* the lanes of the wave's whole instances: lane / L < G */
+QSP_LAYOUT_FN lane_mask_t lane_mask_instances(int N, int S) {
+    const int n = instances_per_wave(N, S) * lanes_per_instance(N, S);
+    return n >= WAVE ? ~0ull : (1ull << n) - 1;
+}
+/* GroupScan's flags (qsp_solver.hip), i = 0 .. 5: the row shifts by 1, 2, 4, 8 and the row broadcasts of
+ * lanes 15 and 31, each taken where the source lane lies in the same group */
+enum { SCAN_FLAGS = 6 };
+QSP_LAYOUT_FN lane_mask_t lane_mask_scan(int N, int S, int i) {
+    lane_mask_t m = 0;
+    for (int l = 0; l < WAVE; ++l) {
+        const int lig = l % lanes_per_instance(N, S), col = l & 15, row = l >> 4;
+        const int take = i < 4 ? (col >= (1 << i) && lig >= (1 << i))
+                       : i == 4 ? ((row & 1) && lig > col) : (row >= 2 && lig >= l - 31);
+        if (take) m |= 1ull << l;
+    }
+    return m;
+}
+/* the factor walk's phase ph at one stage per lane: the stage lanes that publish a record (stages kb .. ke
+ * of the whole instances), and those that collect factors from it (the stages k < N among them) */
+QSP_LAYOUT_FN lane_mask_t lane_mask_mfw_publish(int N, int ph) {
+    const int H = mfw_split(N);
+    return lane_mask_lig_in(N, 1, ph == 0 ? H : 0, ph == 0 ? N : H - 1) & lane_mask_instances(N, 1);
+}
+QSP_LAYOUT_FN lane_mask_t lane_mask_mfw_collect(int N, int ph) {
+    return lane_mask_mfw_publish(N, ph) & lane_mask_stage(N, 1);
+}
+/* the factor walk's block lanes: lane l holds element (r, cc) = (l >> 4, l & 3) of its block's 4 x 4 operands.
+ * Roles by matrix row and column (rows, cols: bit sets of the rows and the columns that take the role), the
+ * diagonal r == cc and the upper triangle r <= cc */
+QSP_LAYOUT_FN lane_mask_t lane_mask_mfw_role(int rows, int cols) {
+    lane_mask_t m = 0;
+    for (int l = 0; l < WAVE; ++l)
+        if (((rows >> (l >> 4)) & 1) && ((cols >> (l & 3)) & 1)) m |= 1ull << l;
+    return m;
+}
+QSP_LAYOUT_FN lane_mask_t lane_mask_mfw_diag(void) {
+    return lane_mask_mfw_role(1, 1) | lane_mask_mfw_role(2, 2) | lane_mask_mfw_role(4, 4) | lane_mask_mfw_role(8, 8);
+}
+QSP_LAYOUT_FN lane_mask_t lane_mask_mfw_upper(void) {
+    return lane_mask_mfw_role(1, 0xf) | lane_mask_mfw_role(2, 0xe) | lane_mask_mfw_role(4, 0xc) | lane_mask_mfw_role(8, 8);
+}
+
 /* SolveParams::mfma_walk of a new handle (host): on, unless the developer switch QSP_MFMA_WALK=0
  * selects the lane walk wherever the matrix cores would factorise (an A/B that rounds differently) */
 static inline int mfma_walk_default(void) {

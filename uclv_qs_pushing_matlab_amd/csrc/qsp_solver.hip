@@ -86,6 +86,16 @@ __device__ __forceinline__ double dpp_move(double v) {
     return __hiloint2double(hi, lo);
 }
 
+// Lane masks of a compiled horizon (NC > 0; lane_mask_*: qsp_layout.h).  A lane test whose outcome is known
+// when the kernel is built is taken from the 64-bit constant: the scalar pair is the region's exec mask as it
+// stands, where the per-lane form pays a v_cmp, holds the mask in scalar registers through the IPM loop and
+// spills it (fetched back by v_readlane).  Taken so: the closed-loop lane walks' steps, the stage role
+// lig < N and the factor walk's publish and collect regions.  Measured and not taken: the group reductions'
+// levels and scan flags, the factor walk's block-lane roles (profiles/lane_masks/README.md).
+__device__ __forceinline__ bool lanes_in(lane_mask_t m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
+template <lane_mask_t M>   // a mask the build knows: a literal, never evaluated on the device
+__device__ __forceinline__ bool lanes_of() { return lanes_in(M); }
+
 // Which scan steps a lane takes (its source lane lies in the same group); computed once.
 struct GroupScan {
     bool s1, s2, s4, s8, b15, b31;
@@ -343,7 +353,9 @@ void mfw_prepare(SolveParams& p) {
     }
 }
 
-template <int S>
+// (NC: the horizon where it is compiled in, one stage per lane; the publish and collect regions' lanes are
+// then lane_mask_mfw_publish's and lane_mask_mfw_collect's constants)
+template <int S, int NC = 0>
 __device__ __forceinline__ void factor_walk_mfma(const Ctx& c, const SolveParams& p, Stage<S>& st, const double (&hx3)[S],
                                                  const double (&hu)[S][2], const double (&gx3)[S], const double (&gu)[S][2]) {
     const int N = c.N, G = WAVE / c.L;
@@ -377,9 +389,10 @@ __device__ __forceinline__ void factor_walk_mfma(const Ctx& c, const SolveParams
         // publish: the stage lanes write the records of their slots' stages (one stage per lane written
         // as the lane test: the slot loop, the same test, costs the S = 1 kernel 2 % in issue order)
         if constexpr (S == 1) {
-            if (c.grp < G && c.lig >= kb && c.lig <= ke) {
+            if (NC ? (ph == 0 ? lanes_of<lane_mask_mfw_publish(NC, 0)>() : lanes_of<lane_mask_mfw_publish(NC, 1)>())
+                   : (c.grp < G && c.lig >= kb && c.lig <= ke)) {
                 double* rw = reg + c.grp * IS + (c.lig - kb) * MFW_REC;
-                if (c.lig < N) {
+                if (NC ? lanes_of<lane_mask_stage(NC, 1)>() : c.lig < N) {
 #pragma unroll
                     for (int q = 0; q < 6; ++q) rw[R_A + q] = st.a[0][q];
 #pragma unroll
@@ -523,7 +536,8 @@ __device__ __forceinline__ void factor_walk_mfma(const Ctx& c, const SolveParams
         wave_lds_sync();
         // collect: the stage lanes take their slots' factors (stages k < N)
         if constexpr (S == 1) {
-            if (c.grp < G && c.lig >= kb && c.lig <= ke && c.lig < N) {
+            if (NC ? (ph == 0 ? lanes_of<lane_mask_mfw_collect(NC, 0)>() : lanes_of<lane_mask_mfw_collect(NC, 1)>())
+                   : (c.grp < G && c.lig >= kb && c.lig <= ke && c.lig < N)) {
                 const double* rr = reg + c.grp * IS + (c.lig - kb) * MFW_REC;
 #pragma unroll
                 for (int q = 0; q < 8; ++q) st.K[0][q] = rr[O_K + q];
@@ -564,7 +578,7 @@ __device__ __forceinline__ void factor_walk_mfma(const Ctx& c, const SolveParams
     // (one stage per lane: written as the lane test, which keeps the kernel within two waves per SIMD
     // (249 registers); the unrolled slot loop, the same test, costs it the second wave)
     if constexpr (S == 1) {
-        if (c.lig >= N) {
+        if (NC ? !lanes_of<lane_mask_stage(NC, 1)>() : c.lig >= N) {
 #pragma unroll
             for (int q = 0; q < 3; ++q) {
                 st.f(F_VA, 0, q) = 0.0;
@@ -621,8 +635,11 @@ __device__ __forceinline__ void velem_read(const VElem& e, int src, VElem& f) {
 // loop counter beside its 16 FMA and 8 DPP moves.  Measured at N = 20 (profiles/fixed_horizon/README.md):
 // 2 +1.2 %, 4 +2.0 % over the rolled walks, both at the rolled kernel's 253 VGPRs; 5 (+2.2 %) and the full
 // unroll (+1.9 %) take 256 VGPRs, 10 takes 264 (one wave per SIMD).  NC = 0 keeps the rolled loops (count 1).
+// With the steps' exec masks as constants (below) the masks no longer spill and the counts were measured again
+// (profiles/lane_masks/README.md): 4 and 5 at 245 VGPRs, written out in full (every step's mask a literal) at
+// 246 and the fastest, +0.2 % over 4.  32 covers every horizon at one stage per lane (L - 1 <= 31 steps).
 #ifndef QSP_WALK_UNROLL
-#define QSP_WALK_UNROLL 4
+#define QSP_WALK_UNROLL 32
 #endif
 template <int S, bool FACTOR, bool ALT = false, int NC = 0>
 __device__ __forceinline__ void riccati_solve(const Ctx& c, const SolveParams& p, Stage<S>& st, const double dx0[4],
@@ -674,19 +691,42 @@ __device__ __forceinline__ void riccati_solve(const Ctx& c, const SolveParams& p
         // whose source lane j+1 sits the step out, keeps its old value (a DPP read from a
         // disabled lane returns `old`) — so every lane ends holding the dp that reached it.
         // (step 0 would only form dp_0, which nothing reads: lane 0 holds dp_1 after step 1)
-#pragma clang loop unroll_count(NC ? QSP_WALK_UNROLL : 1)
-        for (int j = c.L - 2; j >= 1; --j) {
-            if (c.lig <= j) {
+        // Compiled horizon: the step's exec mask is the constant lane_mask_lig_le(j), carried in a scalar pair
+        // from step to step (the lanes lig == j leave: lane_mask_leave), no per-lane compare in the loop.
+        // (the step a second time, as a closure: written so the compiled kernel stands at 245 VGPRs against 253
+        // with one loop for both, and the runtime-horizon kernels keep their code to the instruction)
+        if constexpr (NC > 0) {
+            auto step = [&]() {
                 double n[4];
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
                     n[i] = qfma(M[0][12 + i], pv[3], qfma(M[0][8 + i], pv[2], qfma(M[0][4 + i], pv[1], qfma(M[0][i], pv[0], e[i]))));
 #pragma unroll
                 for (int i = 0; i < 4; ++i) pv[i] = wave_from_next(pv[i], n[i]);
+            };
+            constexpr int L = lanes_per_instance(NC, 1);
+            constexpr lane_mask_t act0 = lane_mask_lig_le(NC, 1, L - 2), first = lane_mask_first(NC, 1);
+            lane_mask_t act = act0;
+#pragma clang loop unroll_count(QSP_WALK_UNROLL)
+            for (int j = L - 2; j >= 1; --j) {
+                if (lanes_in(act)) step();
+                act = lane_mask_leave(act, first, j);
+            }
+        } else {
+#pragma clang loop unroll_count(1)
+            for (int j = c.L - 2; j >= 1; --j) {
+                if (c.lig <= j) {
+                    double n[4];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+                        n[i] = qfma(M[0][12 + i], pv[3], qfma(M[0][8 + i], pv[2], qfma(M[0][4 + i], pv[1], qfma(M[0][i], pv[0], e[i]))));
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) pv[i] = wave_from_next(pv[i], n[i]);
+                }
             }
         }
         const double* dpk = pv;
-        if (c.lig < c.N) {
+        if (NC ? lanes_of<lane_mask_stage(NC, 1)>() : c.lig < c.N) {
             const double* B = st.B[0];
             const double* Rn = st.Rn[0];
             double rt[2];
@@ -784,7 +824,7 @@ __device__ __forceinline__ void riccati_solve(const Ctx& c, const SolveParams& p
             }
         }
     } else if constexpr (S == 1 && FACTOR && ALT) {
-        factor_walk_mfma<1>(c, p, st, hx3, hu, gx3, gu);
+        factor_walk_mfma<1, NC>(c, p, st, hx3, hu, gx3, gu);
     } else {   // the factorisation (both difference passes are taken above): matrix cores or lane walk
     static_assert(FACTOR, "the corrector's difference pass is a closed-loop walk (S = 1) or a scan (S = 2)");
     bool walked = false;
@@ -852,19 +892,39 @@ __device__ __forceinline__ void riccati_solve(const Ctx& c, const SolveParams& p
         // Step j runs on lanes j <= lig < L-1 only (the terminal lane never steps, so the
         // next group's first lane reads a disabled source): lane j+1 takes lane j's value and
         // lane j keeps its own, so every lane ends holding the dx of its stage.
-#pragma clang loop unroll_count(NC ? QSP_WALK_UNROLL : 1)
-        for (int j = 0; j < c.L - 1; ++j) {
-            if (c.lig >= j && c.lig < c.L - 1) {
+        // (compiled horizon: the constant lane_mask_walk_fwd(j), advanced as in the difference walk)
+        if constexpr (NC > 0) {
+            auto step = [&]() {
                 double n[4];
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
                     n[i] = qfma(M[0][4 * i + 3], dx[3], qfma(M[0][4 * i + 2], dx[2], qfma(M[0][4 * i + 1], dx[1], qfma(M[0][4 * i], dx[0], cv[i]))));
 #pragma unroll
                 for (int i = 0; i < 4; ++i) dx[i] = wave_from_prev(dx[i], n[i]);
+            };
+            constexpr int L = lanes_per_instance(NC, 1);
+            constexpr lane_mask_t act0 = lane_mask_walk_fwd(NC, 1, 0), first = lane_mask_first(NC, 1);
+            lane_mask_t act = act0;
+#pragma clang loop unroll_count(QSP_WALK_UNROLL)
+            for (int j = 0; j < L - 1; ++j) {
+                if (lanes_in(act)) step();
+                act = lane_mask_leave(act, first, j);
+            }
+        } else {
+#pragma clang loop unroll_count(1)
+            for (int j = 0; j < c.L - 1; ++j) {
+                if (c.lig >= j && c.lig < c.L - 1) {
+                    double n[4];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+                        n[i] = qfma(M[0][4 * i + 3], dx[3], qfma(M[0][4 * i + 2], dx[2], qfma(M[0][4 * i + 1], dx[1], qfma(M[0][4 * i], dx[0], cv[i]))));
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) dx[i] = wave_from_prev(dx[i], n[i]);
+                }
             }
         }
         const double* dxk = dx;
-        if (c.lig < c.N) {
+        if (NC ? lanes_of<lane_mask_stage(NC, 1)>() : c.lig < c.N) {
             const double* K = st.K[0];
             st.f(out, 0, 0) = dxk[3];
             st.f(out, 0, 1) = qfma(K[3], dxk[3], qfma(K[2], dxk[2], qfma(K[1], dxk[1], qfma(K[0], dxk[0], st.kk[0][0]))));

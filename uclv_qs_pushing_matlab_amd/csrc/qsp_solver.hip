@@ -95,6 +95,17 @@ __device__ __forceinline__ double dpp_move(double v) {
 __device__ __forceinline__ bool lanes_in(lane_mask_t m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
 template <lane_mask_t M>   // a mask the build knows: a literal, never evaluated on the device
 __device__ __forceinline__ bool lanes_of() { return lanes_in(M); }
+// A lane test that some lane of every wave reaching it passes (by the wave's geometry or the enclosing loop's
+// exit condition), used directly as the `if` condition.  The compiler guards a divergent region with a branch
+// around it for the wave in which no lane enters (s_cbranch_execz); told that the region is always entered it
+// drops that branch, which such a wave never takes and resolves all the same at every pass.  The hint changes no
+// result: a region run under an empty exec mask does nothing.  (A macro, not a function: the weight belongs to
+// the branch it is written on, and is lost through an inlined function; [[likely]] on the statement gives the
+// same code.)  Taken so: the steps of the compiled kernel's three lane walks, and the runtime-horizon kernels'
+// lane tests (walk steps, stage role, factor-walk publish and collect, the scans' take).  Measured and not
+// taken: the compiled kernel's constant stage-role, publish and collect regions (profiles/skip_branches/README.md).
+// Never on a test that data decides (a frozen instance, the ratio tests, bnd_act): such a region can be empty.
+#define QSP_SOME_LANE(cond) __builtin_expect_with_probability((cond), true, 1.0)
 
 // Which scan steps a lane takes (its source lane lies in the same group); computed once.
 struct GroupScan {
@@ -390,9 +401,9 @@ __device__ __forceinline__ void factor_walk_mfma(const Ctx& c, const SolveParams
         // as the lane test: the slot loop, the same test, costs the S = 1 kernel 2 % in issue order)
         if constexpr (S == 1) {
             if (NC ? (ph == 0 ? lanes_of<lane_mask_mfw_publish(NC, 0)>() : lanes_of<lane_mask_mfw_publish(NC, 1)>())
-                   : (c.grp < G && c.lig >= kb && c.lig <= ke)) {
+                   : QSP_SOME_LANE(c.grp < G && c.lig >= kb && c.lig <= ke)) {
                 double* rw = reg + c.grp * IS + (c.lig - kb) * MFW_REC;
-                if (NC ? lanes_of<lane_mask_stage(NC, 1)>() : c.lig < N) {
+                if (NC ? lanes_of<lane_mask_stage(NC, 1)>() : QSP_SOME_LANE(c.lig < N)) {
 #pragma unroll
                     for (int q = 0; q < 6; ++q) rw[R_A + q] = st.a[0][q];
 #pragma unroll
@@ -418,7 +429,7 @@ __device__ __forceinline__ void factor_walk_mfma(const Ctx& c, const SolveParams
     #pragma unroll
             for (int ls = 0; ls < S; ++ls) {
                 const int k = kof<S>(c, ls);
-                if (c.grp < G && k >= kb && k <= ke) {
+                if (QSP_SOME_LANE(c.grp < G && k >= kb && k <= ke)) {
                     double* rw = reg + c.grp * IS + (k - kb) * MFW_REC;
                     if (k < N) {
     #pragma unroll
@@ -537,7 +548,7 @@ __device__ __forceinline__ void factor_walk_mfma(const Ctx& c, const SolveParams
         // collect: the stage lanes take their slots' factors (stages k < N)
         if constexpr (S == 1) {
             if (NC ? (ph == 0 ? lanes_of<lane_mask_mfw_collect(NC, 0)>() : lanes_of<lane_mask_mfw_collect(NC, 1)>())
-                   : (c.grp < G && c.lig >= kb && c.lig <= ke && c.lig < N)) {
+                   : QSP_SOME_LANE(c.grp < G && c.lig >= kb && c.lig <= ke && c.lig < N)) {
                 const double* rr = reg + c.grp * IS + (c.lig - kb) * MFW_REC;
 #pragma unroll
                 for (int q = 0; q < 8; ++q) st.K[0][q] = rr[O_K + q];
@@ -555,7 +566,7 @@ __device__ __forceinline__ void factor_walk_mfma(const Ctx& c, const SolveParams
     #pragma unroll
             for (int ls = 0; ls < S; ++ls) {
                 const int k = kof<S>(c, ls);
-                if (c.grp < G && k >= kb && k <= ke && k < N) {
+                if (QSP_SOME_LANE(c.grp < G && k >= kb && k <= ke && k < N)) {
                     const double* rr = reg + c.grp * IS + (k - kb) * MFW_REC;
     #pragma unroll
                     for (int q = 0; q < 8; ++q) st.K[ls][q] = rr[O_K + q];
@@ -709,13 +720,13 @@ __device__ __forceinline__ void riccati_solve(const Ctx& c, const SolveParams& p
             lane_mask_t act = act0;
 #pragma clang loop unroll_count(QSP_WALK_UNROLL)
             for (int j = L - 2; j >= 1; --j) {
-                if (lanes_in(act)) step();
+                if (QSP_SOME_LANE(lanes_in(act))) step();
                 act = lane_mask_leave(act, first, j);
             }
         } else {
 #pragma clang loop unroll_count(1)
             for (int j = c.L - 2; j >= 1; --j) {
-                if (c.lig <= j) {
+                if (QSP_SOME_LANE(c.lig <= j)) {
                     double n[4];
 #pragma unroll
                     for (int i = 0; i < 4; ++i)
@@ -726,7 +737,7 @@ __device__ __forceinline__ void riccati_solve(const Ctx& c, const SolveParams& p
             }
         }
         const double* dpk = pv;
-        if (NC ? lanes_of<lane_mask_stage(NC, 1)>() : c.lig < c.N) {
+        if (NC ? lanes_of<lane_mask_stage(NC, 1)>() : QSP_SOME_LANE(c.lig < c.N)) {
             const double* B = st.B[0];
             const double* Rn = st.Rn[0];
             double rt[2];
@@ -752,7 +763,7 @@ __device__ __forceinline__ void riccati_solve(const Ctx& c, const SolveParams& p
             const bool take = c.lig + off < c.L;
             Aff f;
             aff_read(d, take ? c.lane + off : c.lane, f);
-            if (take) aff_compose(d, f);
+            if (QSP_SOME_LANE(take)) aff_compose(d, f);
         }
         // dp_{2j+2}: the next lane's suffix map applied to dp_N = 0 (its constant); then each slot's
         // dkk from the dp reaching it, slot 1 first (ric_delta_step also steps dp to the slot)
@@ -796,7 +807,7 @@ __device__ __forceinline__ void riccati_solve(const Ctx& c, const SolveParams& p
             const bool take = c.lig + off < c.L;
             VElem f;
             velem_read(e, take ? c.lane + off : c.lane, f);
-            if (take) velem_combine(e, f);
+            if (QSP_SOME_LANE(take)) velem_combine(e, f);
         }
         {
             VElem f;
@@ -840,7 +851,7 @@ __device__ __forceinline__ void riccati_solve(const Ctx& c, const SolveParams& p
         // mask); lanes below j compute a throw-away step that their own turn overwrites.
         // Writing the factors in place this way needs no per-step selects.
         // The hand-over runs inside the same region: lane j-1 (active) reads lane j (active).
-        if (c.lig <= j) {
+        if (QSP_SOME_LANE(c.lig <= j)) {
             double Pc[10], pvc[4];
 #pragma unroll
             for (int i = 0; i < 10; ++i) Pc[i] = P[i];
@@ -907,13 +918,13 @@ __device__ __forceinline__ void riccati_solve(const Ctx& c, const SolveParams& p
             lane_mask_t act = act0;
 #pragma clang loop unroll_count(QSP_WALK_UNROLL)
             for (int j = 0; j < L - 1; ++j) {
-                if (lanes_in(act)) step();
+                if (QSP_SOME_LANE(lanes_in(act))) step();
                 act = lane_mask_leave(act, first, j);
             }
         } else {
 #pragma clang loop unroll_count(1)
             for (int j = 0; j < c.L - 1; ++j) {
-                if (c.lig >= j && c.lig < c.L - 1) {
+                if (QSP_SOME_LANE(c.lig >= j && c.lig < c.L - 1)) {
                     double n[4];
 #pragma unroll
                     for (int i = 0; i < 4; ++i)
@@ -924,7 +935,7 @@ __device__ __forceinline__ void riccati_solve(const Ctx& c, const SolveParams& p
             }
         }
         const double* dxk = dx;
-        if (NC ? lanes_of<lane_mask_stage(NC, 1)>() : c.lig < c.N) {
+        if (NC ? lanes_of<lane_mask_stage(NC, 1)>() : QSP_SOME_LANE(c.lig < c.N)) {
             const double* K = st.K[0];
             st.f(out, 0, 0) = dxk[3];
             st.f(out, 0, 1) = qfma(K[3], dxk[3], qfma(K[2], dxk[2], qfma(K[1], dxk[1], qfma(K[0], dxk[0], st.kk[0][0]))));
@@ -949,7 +960,7 @@ __device__ __forceinline__ void riccati_solve(const Ctx& c, const SolveParams& p
             const bool take = c.lig >= off;
             Aff f;
             aff_read(e, take ? c.lane - off : c.lane, f);
-            if (take) aff_compose(e, f);
+            if (QSP_SOME_LANE(take)) aff_compose(e, f);
         }
         double dx[4];
         {

@@ -89,7 +89,7 @@ __device__ __forceinline__ double dpp_move(double v) {
 // Lane masks of a compiled horizon (NC > 0; lane_mask_*: qsp_layout.h).  A lane test whose outcome is known
 // when the kernel is built is taken from the 64-bit constant: the scalar pair is the region's exec mask as it
 // stands, where the per-lane form pays a v_cmp, holds the mask in scalar registers through the IPM loop and
-// spills it (fetched back by v_readlane).  Taken so: the closed-loop lane walks' steps, the stage role
+// spills it (fetched back by v_readlane).  Taken so: the closed-loop lane walks' one region each, the stage role
 // lig < N and the factor walk's publish and collect regions.  Measured and not taken: the group reductions'
 // levels and scan flags, the factor walk's block-lane roles (profiles/lane_masks/README.md).
 __device__ __forceinline__ bool lanes_in(lane_mask_t m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
@@ -101,9 +101,10 @@ __device__ __forceinline__ bool lanes_of() { return lanes_in(M); }
 // drops that branch, which such a wave never takes and resolves all the same at every pass.  The hint changes no
 // result: a region run under an empty exec mask does nothing.  (A macro, not a function: the weight belongs to
 // the branch it is written on, and is lost through an inlined function; [[likely]] on the statement gives the
-// same code.)  Taken so: the steps of the compiled kernel's three lane walks, and the runtime-horizon kernels'
-// lane tests (walk steps, stage role, factor-walk publish and collect, the scans' take).  Measured and not
-// taken: the compiled kernel's constant stage-role, publish and collect regions (profiles/skip_branches/README.md).
+// same code.)  Taken so: the regions of the three closed-loop lane walks, and the runtime-horizon kernels'
+// lane tests (lane-walk factorisation steps, stage role, factor-walk publish and collect, the scans' take).
+// Measured and not taken: the compiled kernel's constant stage-role, publish and collect regions
+// (profiles/skip_branches/README.md).
 // Never on a test that data decides (a frozen instance, the ratio tests, bnd_act): such a region can be empty.
 #define QSP_SOME_LANE(cond) __builtin_expect_with_probability((cond), true, 1.0)
 
@@ -646,9 +647,11 @@ __device__ __forceinline__ void velem_read(const VElem& e, int src, VElem& f) {
 // loop counter beside its 16 FMA and 8 DPP moves.  Measured at N = 20 (profiles/fixed_horizon/README.md):
 // 2 +1.2 %, 4 +2.0 % over the rolled walks, both at the rolled kernel's 253 VGPRs; 5 (+2.2 %) and the full
 // unroll (+1.9 %) take 256 VGPRs, 10 takes 264 (one wave per SIMD).  NC = 0 keeps the rolled loops (count 1).
-// With the steps' exec masks as constants (below) the masks no longer spill and the counts were measured again
+// With the steps' exec masks as constants the masks no longer spilled and the counts were measured again
 // (profiles/lane_masks/README.md): 4 and 5 at 245 VGPRs, written out in full (every step's mask a literal) at
 // 246 and the fastest, +0.2 % over 4.  32 covers every horizon at one stage per lane (L - 1 <= 31 steps).
+// Each walk now runs under one exec mask for all its steps (below; profiles/walk_regions/README.md), written out
+// in full as before.
 #ifndef QSP_WALK_UNROLL
 #define QSP_WALK_UNROLL 32
 #endif
@@ -698,15 +701,20 @@ __device__ __forceinline__ void riccati_solve(const Ctx& c, const SolveParams& p
         double e[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) e[i] = qfma(K[4 + i], gu[0][1], qfma(K[i], gu[0][0], i == 3 ? gx3[0] : 0.0));
-        // Step j runs on lanes lig <= j only: lane j-1 takes lane j's value, while lane j,
-        // whose source lane j+1 sits the step out, keeps its old value (a DPP read from a
-        // disabled lane returns `old`) — so every lane ends holding the dp that reached it.
-        // (step 0 would only form dp_0, which nothing reads: lane 0 holds dp_1 after step 1)
-        // Compiled horizon: the step's exec mask is the constant lane_mask_lig_le(j), carried in a scalar pair
-        // from step to step (the lanes lig == j leave: lane_mask_leave), no per-lane compare in the loop.
-        // (the step a second time, as a closure: written so the compiled kernel stands at 245 VGPRs against 253
-        // with one loop for both, and the runtime-horizon kernels keep their code to the instruction)
-        if constexpr (NC > 0) {
+        // The walk is a pipeline under one exec mask, lig <= L - 2, for all of its L - 2 steps: every enabled lane
+        // forms n = e + M' pv from its own loop-invariant M, e and its current pv, and takes its next lane's n.
+        // - The terminal lanes (lig == L - 1) are disabled throughout, as sources and as destinations, so
+        //   nothing crosses an instance boundary (a padding lane at the wave's end has no source at all).
+        // - The first lane of the chain, lig == L - 2, is thereby pinned: a DPP read from a disabled or missing
+        //   lane leaves `old`, so it holds dp_N = 0 at every step and hands the same dp_{N-1} on each time.
+        // - So the pipeline is idempotent: by induction the lanes lig >= L - 2 - t hold the dp that reaches them
+        //   after step t, and every later step hands them the same bits again (the same operations on the same
+        //   inputs).  After L - 2 steps lane 0 holds dp_1; dp_0 is read by nothing.
+        // - Nothing may read pv before the last step: the lanes the wavefront has not reached hold throw-away
+        //   values, possibly non-finite, which later steps overwrite.
+        // (Per-step masks lig <= j, under which the finished lanes sat out, gave every lane the same bits at six
+        // scalar instructions per step to rebuild the mask: profiles/walk_regions/README.md.)
+        {
             auto step = [&]() {
                 double n[4];
 #pragma unroll
@@ -715,37 +723,32 @@ __device__ __forceinline__ void riccati_solve(const Ctx& c, const SolveParams& p
 #pragma unroll
                 for (int i = 0; i < 4; ++i) pv[i] = wave_from_next(pv[i], n[i]);
             };
-            constexpr int L = lanes_per_instance(NC, 1);
-            constexpr lane_mask_t act0 = lane_mask_lig_le(NC, 1, L - 2), first = lane_mask_first(NC, 1);
-            lane_mask_t act = act0;
+            // dkk behind the walk, after its last step, in the walk's region: at one stage per lane the stage role
+            // lig < N is the walk's mask (measured against a region of its own: profiles/walk_regions/README.md)
+            auto update = [&]() {
+                const double* dpk = pv;
+                const double* B = st.B[0];
+                const double* Rn = st.Rn[0];
+                double rt[2];
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+                    rt[i] = qfma(B[6 + i], dpk[3], qfma(B[4 + i], dpk[2], qfma(B[2 + i], dpk[1], qfma(B[i], dpk[0], gu[0][i]))));
+                st.kk[0][0] = qfma(Rn[1], rt[1], qfma(Rn[0], rt[0], st.kk[0][0]));
+                st.kk[0][1] = qfma(Rn[2], rt[1], qfma(Rn[1], rt[0], st.kk[0][1]));
+            };
+            if constexpr (NC > 0) {
+                constexpr int L = lanes_per_instance(NC, 1);
+                static_assert(lane_mask_stage(NC, 1) == lane_mask_lig_le(NC, 1, L - 2), "lig < N is the walk's mask");
+                if (QSP_SOME_LANE(lanes_of<lane_mask_lig_le(NC, 1, L - 2)>())) {
 #pragma clang loop unroll_count(QSP_WALK_UNROLL)
-            for (int j = L - 2; j >= 1; --j) {
-                if (QSP_SOME_LANE(lanes_in(act))) step();
-                act = lane_mask_leave(act, first, j);
-            }
-        } else {
-#pragma clang loop unroll_count(1)
-            for (int j = c.L - 2; j >= 1; --j) {
-                if (QSP_SOME_LANE(c.lig <= j)) {
-                    double n[4];
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-                        n[i] = qfma(M[0][12 + i], pv[3], qfma(M[0][8 + i], pv[2], qfma(M[0][4 + i], pv[1], qfma(M[0][i], pv[0], e[i]))));
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) pv[i] = wave_from_next(pv[i], n[i]);
+                    for (int j = L - 2; j >= 1; --j) step();
+                    update();
                 }
+            } else if (QSP_SOME_LANE(c.lig <= c.L - 2)) {
+#pragma clang loop unroll_count(1)
+                for (int j = c.L - 2; j >= 1; --j) step();
+                update();
             }
-        }
-        const double* dpk = pv;
-        if (NC ? lanes_of<lane_mask_stage(NC, 1)>() : QSP_SOME_LANE(c.lig < c.N)) {
-            const double* B = st.B[0];
-            const double* Rn = st.Rn[0];
-            double rt[2];
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-                rt[i] = qfma(B[6 + i], dpk[3], qfma(B[4 + i], dpk[2], qfma(B[2 + i], dpk[1], qfma(B[i], dpk[0], gu[0][i]))));
-            st.kk[0][0] = qfma(Rn[1], rt[1], qfma(Rn[0], rt[0], st.kk[0][0]));
-            st.kk[0][1] = qfma(Rn[2], rt[1], qfma(Rn[1], rt[0], st.kk[0][1]));
         }
     } else if constexpr (S == 2 && !FACTOR) {
         // corrector difference pass as a suffix scan of the lanes' backward maps, dp_N = 0: lane j's
@@ -900,11 +903,17 @@ __device__ __forceinline__ void riccati_solve(const Ctx& c, const SolveParams& p
 #pragma unroll
         for (int i = 0; i < 4; ++i) cv[i] = qfma(st.B[0][2 * i + 1], st.kk[0][1], qfma(st.B[0][2 * i], st.kk[0][0], st.bb[0][i]));
         double dx[4] = {dx0[0], dx0[1], dx0[2], dx0[3]};
-        // Step j runs on lanes j <= lig < L-1 only (the terminal lane never steps, so the
-        // next group's first lane reads a disabled source): lane j+1 takes lane j's value and
-        // lane j keeps its own, so every lane ends holding the dx of its stage.
-        // (compiled horizon: the constant lane_mask_walk_fwd(j), advanced as in the difference walk)
-        if constexpr (NC > 0) {
+        // The same pipeline as the difference walk, forwards, under the one exec mask 0 <= lig <= L - 2 for all
+        // of its L - 2 steps: every enabled lane forms n = M dx + cv and takes its previous lane's n.
+        // - The terminal lanes (lig == L - 1) are disabled throughout, as sources and as destinations.
+        // - The first lane, lig == 0, is thereby pinned at dx0: its source is the previous instance's terminal
+        //   lane, disabled, or missing (lane 0 of the wave), and such a DPP read leaves `old`.
+        // - So the pipeline is idempotent: the lanes lig <= t hold the dx of their stage after step t, and every
+        //   later step hands them the same bits again.  After L - 2 steps lane L - 2 holds dx_{N-1}, the last
+        //   one read (a step L - 1 would move nothing: its only lane's source would be finished and disabled).
+        // - Nothing may read dx before the last step: the lanes ahead of the wavefront hold throw-away values,
+        //   possibly non-finite, which later steps overwrite.
+        {
             auto step = [&]() {
                 double n[4];
 #pragma unroll
@@ -913,33 +922,28 @@ __device__ __forceinline__ void riccati_solve(const Ctx& c, const SolveParams& p
 #pragma unroll
                 for (int i = 0; i < 4; ++i) dx[i] = wave_from_prev(dx[i], n[i]);
             };
-            constexpr int L = lanes_per_instance(NC, 1);
-            constexpr lane_mask_t act0 = lane_mask_walk_fwd(NC, 1, 0), first = lane_mask_first(NC, 1);
-            lane_mask_t act = act0;
+            // du = kk + K dx and the out stores behind the walk, after its last step, in the walk's region (the
+            // stage role lig < N is the walk's mask, as at the difference walk)
+            auto store = [&]() {
+                const double* dxk = dx;
+                const double* K = st.K[0];
+                st.f(out, 0, 0) = dxk[3];
+                st.f(out, 0, 1) = qfma(K[3], dxk[3], qfma(K[2], dxk[2], qfma(K[1], dxk[1], qfma(K[0], dxk[0], st.kk[0][0]))));
+                st.f(out, 0, 2) = qfma(K[7], dxk[3], qfma(K[6], dxk[2], qfma(K[5], dxk[1], qfma(K[4], dxk[0], st.kk[0][1]))));
+            };
+            if constexpr (NC > 0) {
+                constexpr int L = lanes_per_instance(NC, 1);
+                static_assert(lane_mask_stage(NC, 1) == lane_mask_walk_fwd(NC, 1, 0), "lig < N is the walk's mask");
+                if (QSP_SOME_LANE(lanes_of<lane_mask_walk_fwd(NC, 1, 0)>())) {
 #pragma clang loop unroll_count(QSP_WALK_UNROLL)
-            for (int j = 0; j < L - 1; ++j) {
-                if (QSP_SOME_LANE(lanes_in(act))) step();
-                act = lane_mask_leave(act, first, j);
-            }
-        } else {
-#pragma clang loop unroll_count(1)
-            for (int j = 0; j < c.L - 1; ++j) {
-                if (QSP_SOME_LANE(c.lig >= j && c.lig < c.L - 1)) {
-                    double n[4];
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-                        n[i] = qfma(M[0][4 * i + 3], dx[3], qfma(M[0][4 * i + 2], dx[2], qfma(M[0][4 * i + 1], dx[1], qfma(M[0][4 * i], dx[0], cv[i]))));
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) dx[i] = wave_from_prev(dx[i], n[i]);
+                    for (int j = 0; j < L - 2; ++j) step();
+                    store();
                 }
+            } else if (QSP_SOME_LANE(c.lig <= c.L - 2)) {
+#pragma clang loop unroll_count(1)
+                for (int j = 0; j < c.L - 2; ++j) step();
+                store();
             }
-        }
-        const double* dxk = dx;
-        if (NC ? lanes_of<lane_mask_stage(NC, 1)>() : QSP_SOME_LANE(c.lig < c.N)) {
-            const double* K = st.K[0];
-            st.f(out, 0, 0) = dxk[3];
-            st.f(out, 0, 1) = qfma(K[3], dxk[3], qfma(K[2], dxk[2], qfma(K[1], dxk[1], qfma(K[0], dxk[0], st.kk[0][0]))));
-            st.f(out, 0, 2) = qfma(K[7], dxk[3], qfma(K[6], dxk[2], qfma(K[5], dxk[1], qfma(K[4], dxk[0], st.kk[0][1]))));
         }
         SEG_ADD(FACTOR ? 3 : 7, t_rs);
         return;

@@ -48,7 +48,8 @@ extern "C" {
                              8: qsp_default_sim_noise, qsp_set_sim_noise, qsp_clear_sim_noise, qsp_get_sim_noise,
                                 qsp_gen_sim_noise;
                              9: qsp_default_waypoint_opts, qsp_gen_waypoints (and, without a new number, the
-                                query qsp_get_fixed_horizon) */
+                                query qsp_get_fixed_horizon and the KKT evaluators qsp_eval_kkt,
+                                qsp_eval_kkt_device, qsp_qp_residuals with the getter qsp_get_lam) */
 
 #define QSP_OK 0
 #define QSP_ERR_ARG (-1)
@@ -226,6 +227,70 @@ int qsp_get_qp_stalled(qsp_solver* s, int32_t* stalled /* B */);
  * test the final iterate at max_iter, which moves both these residuals and the status 0/2 boundary
  * for an instance that converges on its last step.  No reference fixture fixes either behaviour. */
 int qsp_get_residuals(qsp_solver* s, double* res /* B x 4 */);
+/* acados' get('lam'), nlp_mode 1 only (else, and before any solve, QSP_ERR_STATE): the bound multipliers
+ * of the last solve's final NLP iterate, per stage (s lo, s hi, u_n lo, u_n hi, u_t lo, u_t hi), stages
+ * 0 .. N-1.  Never shifted: after qsp_controller_solve they pair with the unshifted iterate, not with the
+ * shifted warm start that qsp_get_x/u/pi return then.  After qsp_solve_device on a caller's stream,
+ * synchronise that stream first. */
+int qsp_get_lam(qsp_solver* s, double* lam /* B x N x 6 */);
+
+/* ------------------------------------------------- KKT residuals recomputed on the device
+ * The optimality of ANY point, from its numbers alone, in both nlp_modes and without a previous solve: the
+ * OCP's stage data are formed at (X, U) as the SQP forms them (one RK4 step with sensitivities per stage,
+ * defect x+(x_k, u_k) - x_{k+1}, gradient tau W ([x_k; u_k] - yref_k), terminal W_e (x_N - yref_e)) and
+ * the residuals are those of qsp_get_residuals: on a lane the merit SQP reports converged (status 0),
+ * qsp_eval_kkt of qsp_get_x/u/pi/lam returns the bits of qsp_get_residuals.  Weights, bounds, tau, Ts and
+ * stage0_s_bound are the handle's; shapes per lane as qsp_set_shape_ids.
+ *   PI   B x N x 4, pi_k the multiplier of x_{k+1} = x+(x_k, u_k) (qsp_get_pi's);
+ *   LAM  B x N x 6 as qsp_get_lam, or NULL for the IMPLIED multipliers: each bounded quantity of a stage
+ *        (s_k for k >= 1, u_n, u_t) takes lam_lo = max(r, 0), lam_hi = max(-r, 0) from its stationarity r
+ *        without bound multipliers (the stage-0 s pair is 0).  The stationarity of those components is
+ *        then zero by construction and the optimality gap shows in res_comp; at a KKT point with strict
+ *        complementarity the implied multipliers are the true ones.  This is the measure for the RTI
+ *        path, which keeps no bound multipliers.
+ *   x0   B x 4 or NULL.  Used as given, without the controller's s pre-wrap.  NULL: X's row 0 is taken
+ *        as the initial state.
+ *   yref, yref_e  NULL: the references the handle has staged (qsp_set_yref*, or the last controller
+ *        step's); QSP_ERR_STATE if none ever were.
+ *   res        B x 4, acados' order: res_stat = max(stat_u, stat_x, stat_term), res_eq = max(eq_dyn, eq_x0)
+ *              with eq_x0 = max |x0 - X_0| (0 with x0 == NULL), res_ineq, res_comp;
+ *   parts      B x QSP_KKT_NPARTS or NULL, columns QSP_KKT_*: the maxima res is formed from;
+ *   stage_res  B x (N+1) x 4 or NULL: the four residuals of each stage (eq_x0 counts at stage 0), of which
+ *              res is the maximum over the stages, bit for bit.
+ * A lane for which any value read is not finite (X, U, PI, LAM, its references, x0 where given; or whose
+ * RK4 step is not) returns NaN in every output, all rows of stage_res included; every other lane keeps
+ * the bits it has without that lane.  QSP_ERR_STATE without shapes; QSP_ERR_ARG for a null required
+ * pointer.  After qsp_controller_solve, qsp_get_x/u/pi are the shifted warm start: evaluate them against
+ * the next step's references, not as the step's answer. */
+#define QSP_KKT_NPARTS 7
+#define QSP_KKT_STAT_U 0      /* stationarity in u, stages 0 .. N-1 */
+#define QSP_KKT_STAT_X 1      /* stationarity in x, stages 1 .. N-1 */
+#define QSP_KKT_STAT_TERM 2   /* stationarity in x_N */
+#define QSP_KKT_EQ_DYN 3      /* dynamics defect */
+#define QSP_KKT_EQ_X0 4       /* |x0 - X_0| */
+#define QSP_KKT_INEQ 5        /* bound violation */
+#define QSP_KKT_COMP 6        /* complementarity |lam * slack| */
+int qsp_eval_kkt(qsp_solver* s, const double* x0 /* B x 4 or NULL */, const double* X, const double* U,
+                 const double* PI, const double* LAM /* B x N x 6 or NULL */, const double* yref,
+                 const double* yref_e /* NULL: the handle's staged ones */, double* res /* B x 4 */,
+                 double* parts /* B x 7 or NULL */, double* stage_res /* B x (N+1) x 4 or NULL */);
+/* The same on caller-owned device memory, asynchronous on hip_stream (NULL: the handle's), as
+ * qsp_rollout_cost_device: x0, LAM, yref, yref_e, parts, stage_res NULL as above; shape_id NULL = the
+ * handle's. */
+typedef struct {
+    const double* x0;        /* B x 4 or NULL */
+    const double* X;         /* B x (N+1) x 4 */
+    const double* U;         /* B x N x 2 */
+    const double* PI;        /* B x N x 4 */
+    const double* LAM;       /* B x N x 6 or NULL */
+    const double* yref;      /* B x N x 6 or NULL */
+    const double* yref_e;    /* B x 4 or NULL */
+    const int32_t* shape_id; /* B or NULL */
+    double* res;             /* B x 4 */
+    double* parts;           /* B x QSP_KKT_NPARTS or NULL */
+    double* stage_res;       /* B x (N+1) x 4 or NULL */
+} qsp_kkt_io;
+int qsp_eval_kkt_device(qsp_solver* s, const qsp_kkt_io* io, void* hip_stream);
 int qsp_get_time_tot(qsp_solver* s, double* ms);                                        /* 'time_tot' */
 /* dims of the handle (outputs of a MEX/FFI layer are sized from these, never from caller input) */
 int qsp_get_dims(const qsp_solver* s, int32_t* N, int32_t* B);
@@ -471,11 +536,26 @@ int qsp_eval_vbound(qsp_solver* s, int32_t n, const int32_t* shape_id, const dou
  * 1e-10: state-bound multipliers lam <~ 1e-2 at such data (du then within 1e-4, mostly truncation);
  * the OCP's own QPs (B = O(Ts), offsets <= 0.07) sit lower at the same multipliers (u-stationarity
  * of 1 024 bench lanes' QPs: median 1e-13 .. 3e-7, 99th percentile 2e-3 .. 8e-3).
- * Beyond it (lam ~ 1: du wrong by up to 1) recompute H_u du + g_u + B' pi - lam_lo + lam_hi from the
- * returned du, pi, lam before trusting status 0. */
+ * Beyond it (lam ~ 1: du wrong by up to 1) check the returned point with qsp_qp_residuals (below) before
+ * trusting status 0. */
 int qsp_qp_solve(qsp_solver* s, int32_t nb, const double* A, const double* B, const double* b, const double* H,
                  const double* g, const double* lo, const double* hi, const double* dx0, double* dx, double* du,
                  double* pi, double* lam, int32_t* iters, int32_t* qp_status);
+/* The KKT residuals of QP points, recomputed on the device from the numbers given: same array layouts and
+ * sign conventions as qsp_qp_solve (dx: nb x (N+1) x 4, du: nb x N x 2, pi: nb x N x 4, lam: nb x N x 6).
+ * None of qsp_qp_solve's restrictions applies: H may differ per stage and lane, bound widths per stage, A
+ * is read as a full 4 x 4; the data are read as given.  res: nb x 6, largest absolute values per lane of
+ *   0 stat_u   H_u du_k + g_u + B_k' pi_k - lam_lo + lam_hi, k < N
+ *   1 stat_x   H_x dx_k + g_x + A_k' pi_k - pi_{k-1} + e_s (lam_hi - lam_lo), 0 < k < N, and the terminal
+ *              H_N dx_N + g_N - pi_{N-1}
+ *   2 dyn      dx_{k+1} - A_k dx_k - B_k du_k - b_k, and dx_0 - dx0
+ *   3 infeas   bound violation;  4 comp  |lam * slack|;  5 dual  negative multipliers
+ * The stage-0 s row counts in infeas, comp and dual with the handle's stage0_s_bound = 1 and is left out of
+ * all three otherwise.  A lane with a non-finite value in any array returns NaN in its six outputs; the
+ * other lanes keep their bits. */
+int qsp_qp_residuals(qsp_solver* s, int32_t nb, const double* A, const double* B, const double* b, const double* H,
+                     const double* g, const double* lo, const double* hi, const double* dx0, const double* dx,
+                     const double* du, const double* pi, const double* lam, double* res /* nb x 6 */);
 
 /* ------------------------------------- rollout costs and the u0 cost landscape */
 /* The reference's optimality probe on the device (helper.m:356-431): control trajectories are rolled out

@@ -75,6 +75,15 @@ class LandscapeIO(C.Structure):
                  "idx_min")] + [("n_un", C.c_int32), ("n_ut", C.c_int32)]
 
 
+class KktIO(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in
+                ("x0", "X", "U", "PI", "LAM", "yref", "yref_e", "shape_id", "res", "parts", "stage_res")]
+
+
+KKT_PARTS = ("stat_u", "stat_x", "stat_term", "eq_dyn", "eq_x0", "ineq", "comp")   # QSP_KKT_* columns
+QP_RESIDUALS = ("stat_u", "stat_x", "dyn", "infeas", "comp", "dual")              # qsp_qp_residuals' columns
+
+
 class OpenLoopOpts(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("n_steps", C.c_int32), ("M", C.c_int32), ("u_steps", C.c_int32),
                 ("clip", C.c_int32), ("store_tile", C.c_int32), ("Ts", C.c_double), ("v_alpha", C.c_double),
@@ -174,6 +183,10 @@ _SIGS = {
     "qsp_eval_rk4": [_P, _I, _P, _D, _P, _P, _P, _P, _P],
     "qsp_eval_vbound": [_P, _I, _P, _P, _P],
     "qsp_qp_solve": [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "qsp_qp_residuals": [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "qsp_get_lam": [_P, _P],
+    "qsp_eval_kkt": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "qsp_eval_kkt_device": [_P, C.POINTER(KktIO), _P],
     "qsp_default_rollout_opts": [C.POINTER(RolloutOpts)],
     "qsp_rollout_cost": [_P, C.POINTER(RolloutOpts), _I, _P, _P, _P, _P, _P, _P, _P],
     "qsp_rollout_cost_device": [_P, C.POINTER(RolloutOpts), _I, C.POINTER(RolloutIO), _P],

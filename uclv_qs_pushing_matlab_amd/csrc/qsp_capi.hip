@@ -28,7 +28,7 @@ static int fail(int code, const std::string& msg) {
         if (e_ != hipSuccess) return fail(QSP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
     } while (0)
 
-constexpr int STAGE_POOL = 12;   // most host arrays of one call (qsp_cost_landscape, qsp_qp_solve: 10)
+constexpr int STAGE_POOL = 13;   // most host arrays of one call (qsp_qp_residuals: 13)
 
 // Every device array is a Dev<T> member (qsp_devbuf.hpp): it is freed with the handle, whichever call allocated it.
 struct __attribute__((visibility("hidden"))) qsp_solver {
@@ -70,6 +70,7 @@ struct __attribute__((visibility("hidden"))) qsp_solver {
     bool solved = false;            // wU holds a solve's iterate (qsp_cost_landscape with U_tail = NULL)
     int32_t T = 0;
     bool have_traj = false;
+    bool have_yref = false;         // yref / yref_e hold references (a setter's or a controller step's)
     bool traj_per_lane = false;     // reference table per lane (B x T x 6) instead of shared (T x 6)
     float last_ms = 0.0f;
     bool last_controller = false;
@@ -311,6 +312,7 @@ static int check_ids(qsp_solver* s, int32_t n, const int32_t* ids) {
 
 // y_ref staging for the controller step at index_time + offset
 static hipError_t launch_controller_step(qsp_solver* s, int offset) {
+    s->have_yref = true;
     return launch_stage_yref(s->traj.data(), s->T, s->traj_per_lane ? 1 : 0, s->index_time.data(), offset,
                              s->D, s->o.batch, s->o.N, s->yref.data(), s->yref_e.data(), s->stream);
 }
@@ -672,8 +674,10 @@ int qsp_set_x0(qsp_solver* s, const double* x0) { return set_array(s, "qsp_set_x
 
 int qsp_set_yref(qsp_solver* s, const double* yref, const double* yref_e) {
     if (!s || !yref || !yref_e) return fail(QSP_ERR_ARG, "qsp_set_yref: null argument");
-    const int r = h2d(s, s->yref, yref, s->dim.yref());
-    return r ? r : h2d(s, s->yref_e, yref_e, s->dim.yref_e());
+    int r = h2d(s, s->yref, yref, s->dim.yref());
+    if (!r) r = h2d(s, s->yref_e, yref_e, s->dim.yref_e());
+    if (!r) s->have_yref = true;
+    return r;
 }
 
 int qsp_set_init(qsp_solver* s, const double* X, const double* U, const double* PI) {
@@ -731,10 +735,15 @@ int qsp_set_yref_stage(qsp_solver* s, int32_t k, const double* y) {
     HIPCHK(hipMemcpy2DAsync(s->yref.data() + (size_t)k * 6, s->dim.N * row, y, row, row, s->dim.B,
                             hipMemcpyHostToDevice, s->stream));
     HIPCHK(hipStreamSynchronize(s->stream));
+    s->have_yref = true;
     return QSP_OK;
 }
 
-int qsp_set_yref_e(qsp_solver* s, const double* y_e) { return set_array(s, "qsp_set_yref_e", y_e, &qsp_solver::yref_e, &Dims::yref_e); }
+int qsp_set_yref_e(qsp_solver* s, const double* y_e) {
+    const int r = set_array(s, "qsp_set_yref_e", y_e, &qsp_solver::yref_e, &Dims::yref_e);
+    if (!r) s->have_yref = true;
+    return r;
+}
 
 int qsp_set_init_x(qsp_solver* s, const double* X) { return set_array(s, "qsp_set_init_x", X, &qsp_solver::X, &Dims::X); }
 int qsp_set_init_u(qsp_solver* s, const double* U) { return set_array(s, "qsp_set_init_u", U, &qsp_solver::U, &Dims::U); }
@@ -1407,6 +1416,112 @@ int qsp_qp_solve(qsp_solver* s, int32_t nb, const double* A, const double* B, co
                                            hi + (size_t)l * N * 3, dx0 + (size_t)l * 4, qst[l]);
     }
     return QSP_OK;
+}
+
+// ------------------------------------- KKT residuals recomputed from given numbers
+static const char* missing(bool host);
+static hipStream_t stream_of(qsp_solver* s, bool host, void* stream);
+
+// host entry and _device twin, as rollout_cost_run
+static int eval_kkt_run(qsp_solver* s, const char* who, bool host, const qsp_kkt_io* io, void* stream) {
+    const std::string w(who);
+    if (!s || !io || !io->X || !io->U || !io->PI || !io->res) return fail(QSP_ERR_ARG, w + missing(host));
+    if (s->n_shapes < 1) return fail(QSP_ERR_STATE, w + ": no shapes set");
+    if ((!io->yref || !io->yref_e) && !s->have_yref)
+        return fail(QSP_ERR_STATE, w + ": no references given and none staged on the handle");
+    HIPCHK(hipSetDevice(s->o.device));
+    qsp_kkt_io d = *io;
+    Staging st(s);
+    if (host) {
+        const Dims& dim = s->dim;
+        d.x0 = st.in(io->x0, dim.x0());
+        d.X = st.in(io->X, dim.X());
+        d.U = st.in(io->U, dim.U());
+        d.PI = st.in(io->PI, dim.PI());
+        d.LAM = st.in(io->LAM, dim.lam());
+        d.yref = st.in(io->yref, dim.yref());
+        d.yref_e = st.in(io->yref_e, dim.yref_e());
+        d.res = st.out(io->res, dim.res());
+        d.parts = st.out(io->parts, dim.kkt_parts());
+        d.stage_res = st.out(io->stage_res, dim.kkt_stage_res());
+        if (st.err) return st.err;
+    }
+    KktNlpArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.p = s->p;
+    a.B = s->o.batch;
+    a.shapes = s->shapes.data();
+    a.n_shapes = s->n_shapes;
+    a.shape_id = d.shape_id ? d.shape_id : s->shape_id.data();
+    a.x0 = d.x0;
+    a.X = d.X;
+    a.U = d.U;
+    a.PI = d.PI;
+    a.LAM = d.LAM;
+    a.yref = d.yref ? d.yref : s->yref.data();
+    a.yref_e = d.yref_e ? d.yref_e : s->yref_e.data();
+    a.res = d.res;
+    a.parts = d.parts;
+    a.stage_res = d.stage_res;
+    HIPCHK(launch_kkt_nlp(a, stream_of(s, host, stream)));
+    return host ? st.finish() : QSP_OK;
+}
+
+int qsp_eval_kkt(qsp_solver* s, const double* x0, const double* X, const double* U, const double* PI, const double* LAM,
+                 const double* yref, const double* yref_e, double* res, double* parts, double* stage_res) {
+    const qsp_kkt_io io = {x0, X, U, PI, LAM, yref, yref_e, nullptr, res, parts, stage_res};
+    return eval_kkt_run(s, "qsp_eval_kkt", true, &io, nullptr);
+}
+
+int qsp_eval_kkt_device(qsp_solver* s, const qsp_kkt_io* io, void* stream) {
+    return eval_kkt_run(s, "qsp_eval_kkt_device", false, io, stream);
+}
+
+int qsp_get_lam(qsp_solver* s, double* lam) {
+    if (!s || !lam) return fail(QSP_ERR_ARG, "qsp_get_lam: null argument");
+    if (s->o.nlp_mode != QSP_NLP_SQP_MERIT || !s->wnlp.data()) return fail(QSP_ERR_STATE, "qsp_get_lam: nlp_mode 1 (SQP) only");
+    if (!s->solved) return fail(QSP_ERR_STATE, "qsp_get_lam: no solve yet");
+    // the iterate's multipliers live in the SQP's workspace, field-major over (instance, stage 0..N)
+    const size_t B = s->dim.B, N = s->dim.N, tot = s->dim.stages();
+    std::vector<double> w(6 * tot);
+    HIPCHK(hipSetDevice(s->o.device));
+    HIPCHK(hipMemcpyAsync(w.data(), s->wnlp.data() + W_LAM * tot, w.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    for (size_t i = 0; i < B; ++i)
+        for (size_t k = 0; k < N; ++k)
+            for (size_t q = 0; q < 6; ++q) lam[(i * N + k) * 6 + q] = w[q * tot + i * (N + 1) + k];
+    return QSP_OK;
+}
+
+int qsp_qp_residuals(qsp_solver* s, int32_t nb, const double* A, const double* B, const double* b, const double* H,
+                     const double* g, const double* lo, const double* hi, const double* dx0, const double* dx,
+                     const double* du, const double* pi, const double* lam, double* res) {
+    if (!s || nb < 1 || !A || !B || !b || !H || !g || !lo || !hi || !dx0 || !dx || !du || !pi || !lam || !res)
+        return fail(QSP_ERR_ARG, "qsp_qp_residuals: bad argument");
+    HIPCHK(hipSetDevice(s->o.device));
+    const Dims qd{(size_t)nb, (size_t)s->o.N};   // the QPs' own batch
+    Staging st(s);
+    KktQpArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.N = s->o.N;
+    a.nb = nb;
+    a.s0_bound = s->p.s0_bound;
+    a.A = st.in(A, qd.qp_A());
+    a.B = st.in(B, qd.qp_B());
+    a.b = st.in(b, qd.PI());
+    a.H = st.in(H, qd.qp_Hg());
+    a.g = st.in(g, qd.qp_Hg());
+    a.lo = st.in(lo, qd.qp_bound());
+    a.hi = st.in(hi, qd.qp_bound());
+    a.dx0 = st.in(dx0, qd.x0());
+    a.dx = st.in(dx, qd.X());
+    a.du = st.in(du, qd.U());
+    a.pi = st.in(pi, qd.PI());
+    a.lam = st.in(lam, qd.lam());
+    a.res = st.out(res, qd.qp_res());
+    if (st.err) return st.err;
+    HIPCHK(launch_kkt_qp(a, s->stream));
+    return st.finish();
 }
 
 // ------------------------------------- rollout costs and the u0 cost landscape

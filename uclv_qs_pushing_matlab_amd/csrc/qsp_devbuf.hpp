@@ -24,7 +24,14 @@ struct Dims {
     size_t PI() const { return B * N * 4; }
     size_t yref() const { return B * N * 6; }
     size_t yref_e() const { return B * 4; }
-    size_t lam() const { return B * N * 6; }           // qp_lam
+    size_t lam() const { return B * N * 6; }           // qp_lam, qsp_get_lam, the KKT evaluators' LAM
+    size_t kkt_parts() const { return B * KKT_NPARTS; }
+    size_t kkt_stage_res() const { return B * (N + 1) * 4; }
+    size_t qp_res() const { return B * KKT_QP_NRES; }
+    size_t qp_A() const { return B * N * 16; }         // qsp_qp_residuals' QP data
+    size_t qp_B() const { return B * N * 8; }
+    size_t qp_Hg() const { return B * (6 * N + 4); }
+    size_t qp_bound() const { return B * N * 3; }
     size_t stages() const { return B * (N + 1); }      // stride of the SoA workspaces
     size_t lin() const { return L_COUNT * stages(); }
     size_t nlp() const { return W_COUNT * stages(); }

@@ -269,4 +269,42 @@ struct OpenLoopArgs {
 };
 hipError_t launch_open_loop(const OpenLoopArgs& a, hipStream_t stream);
 
+// KKT residuals recomputed from given numbers (qsp_kkt.hip, qsp_kkt.hpp): one thread per (lane, stage).
+struct KktNlpArgs {
+    SolveParams p;             // the handle's: N, Ts, tau, W, We, lh, uh, s0_bound are read
+    int32_t B;
+    const ShapeDev* shapes;
+    int32_t n_shapes;
+    const int32_t* shape_id;   // B (nullptr: shape 0); clamped into [0, n_shapes)
+    const double* x0;          // B x 4 or nullptr (X's row 0 is the initial state)
+    const double* X;           // B x (N+1) x 4
+    const double* U;           // B x N x 2
+    const double* PI;          // B x N x 4
+    const double* LAM;         // B x N x 6 or nullptr (implied multipliers)
+    const double* yref;        // B x N x 6
+    const double* yref_e;      // B x 4
+    double* res;               // B x 4      stat, eq, ineq, comp
+    double* parts;             // B x 7 or nullptr (KktPart)
+    double* stage_res;         // B x (N+1) x 4 or nullptr
+};
+hipError_t launch_kkt_nlp(const KktNlpArgs& a, hipStream_t stream);
+struct KktQpArgs {
+    int32_t N, nb;
+    int32_t s0_bound;          // 1: the stage-0 s row counts in infeas, comp and dual
+    const double* A;           // nb x N x 16
+    const double* B;           // nb x N x 8
+    const double* b;           // nb x N x 4
+    const double* H;           // nb x (6N+4)
+    const double* g;           // nb x (6N+4)
+    const double* lo;          // nb x N x 3
+    const double* hi;          // nb x N x 3
+    const double* dx0;         // nb x 4
+    const double* dx;          // nb x (N+1) x 4
+    const double* du;          // nb x N x 2
+    const double* pi;          // nb x N x 4
+    const double* lam;         // nb x N x 6
+    double* res;               // nb x 6     stat_u, stat_x, dyn, infeas, comp, dual (KktQpRes)
+};
+hipError_t launch_kkt_qp(const KktQpArgs& a, hipStream_t stream);
+
 }  // namespace qsp

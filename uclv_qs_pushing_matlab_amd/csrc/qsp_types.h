@@ -6,6 +6,11 @@
 
 namespace qsp {
 
+// columns of the KKT evaluators' rows (qsp_kkt.hpp): the NLP parts table (QSP_KKT_NPARTS, include/qsp_nmpc.h)
+// and qsp_qp_residuals' res
+constexpr int KKT_NPARTS = 7;
+constexpr int KKT_QP_NRES = 6;
+
 // One slider shape: clamped cubic B-spline (bspline_shape.m, PusherSliderModel.m:113-132)
 // plus the physical constants that enter f (PusherSliderModel.m:53,55; object_selection.m).
 struct ShapeDev {

@@ -72,6 +72,7 @@ class OcpSolver:
         self._uh = np.array([0.011, 0.03, 0.05])
         self._dirty = set(["x0", "yref", "init"])
         self._refs_staged = False   # the device references are a controller step's, newer than set('cost_y_ref*')
+        self._refs_given = False    # set('cost_y_ref*') was called: eval_kkt may flush them (else the zeros above are no reference)
         self.n_shapes = 0
         self.shape_ids = np.zeros(Bn, np.int32)   # host copy of the per-lane shape ids (helper.mode_trace)
         self._plant = None                        # host copy of the installed plant model (set_plant)
@@ -249,12 +250,14 @@ class OcpSolver:
                 self._yref[:, stage] = self._lanes(value, 6)
             self._dirty.add("yref")
             self._refs_staged = False
+            self._refs_given = True
         elif field == "cost_y_ref_e":
             if stage is not None and stage != N:
                 raise ValueError("cost_y_ref_e is only defined at stage N")
             self._yref_e[:] = self._lanes(value, 4)
             self._dirty.add("yref")
             self._refs_staged = False
+            self._refs_given = True
         elif field == "cost_W":
             W = np.asarray(value, np.float64)
             if W.ndim == 2:
@@ -338,6 +341,10 @@ class OcpSolver:
             out = np.zeros((B, 4))
             check(self._L.qsp_get_residuals(self._h, ptr(out)), "get('residuals')")
             return out
+        if field == "lam":         # acados get('lam'): bound multipliers of the final NLP iterate (nlp_mode 1), never shifted
+            out = np.zeros((B, N, 6))
+            check(self._L.qsp_get_lam(self._h, ptr(out)), "get('lam')")
+            return out if stage is None else out[:, stage]
         if field == "time_tot":
             ms = C.c_double()
             check(self._L.qsp_get_time_tot(self._h, C.byref(ms)), "get('time_tot')")
@@ -359,8 +366,43 @@ class OcpSolver:
         check(self._L.qsp_get_cost(self._h, ptr(out)), "qsp_get_cost")
         return out
 
+    # ------------------------------- KKT residuals recomputed on the device
+    def eval_kkt(self, x=None, u=None, pi=None, lam=None, x0=None, yref=None, yref_e=None, parts=False, stages=False):
+        """KKT residuals of an NLP iterate recomputed from its numbers (qsp_eval_kkt): res (B, 4) in acados'
+        order res_stat, res_eq, res_ineq, res_comp; with parts / stages a tuple (res[, parts (B, 7), columns
+        _lib.KKT_PARTS][, stage_res (B, N + 1, 4)]).  Works in both nlp_solver_types and needs no solve.
+        x, u, pi omitted: get('x'), get('u'), get('pi').  lam omitted: get('lam') with 'SQP', and the implied
+        multipliers with 'SQP_RTI', which keeps none (lam='implied' asks for them with 'SQP' too): each
+        bounded quantity takes lam_lo = max(r, 0), lam_hi = max(-r, 0) from its stationarity r, and the
+        optimality gap shows in res_comp.  x0 None: x's row 0 is the initial state; else used as given,
+        without the controller's s pre-wrap.  yref / yref_e None: the handle's references.
+        The defaults are meaningful after solve(), not after controller_solve(): its get('x'), get('u') and
+        get('pi') are the warm start shifted by one stage, while get('lam') and the staged references are
+        the unshifted step's."""
+        B, N = self.B, self.N
+        X = f64(self.get("x") if x is None else x, (B, N + 1, 4))
+        U = f64(self.get("u") if u is None else u, (B, N, 2))
+        PI = f64(self.get("pi") if pi is None else pi, (B, N, 4))
+        if lam is None:
+            lam = self.get("lam") if self.opts.nlp_mode == self.NLP_MODES["SQP"] else "implied"
+        LAM = None if isinstance(lam, str) and lam == "implied" else f64(lam, (B, N, 6))
+        x0 = None if x0 is None else f64(self._lanes(x0, 4))
+        yr, ye = self._rollout_refs(yref, yref_e, flush=self._refs_given)
+        res = np.zeros((B, 4))
+        pt = np.zeros((B, len(_lib.KKT_PARTS))) if parts else None
+        sr = np.zeros((B, N + 1, 4)) if stages else None
+        check(self._L.qsp_eval_kkt(self._h, ptr(x0), ptr(X), ptr(U), ptr(PI), ptr(LAM), ptr(yr), ptr(ye), ptr(res),
+                                   ptr(pt), ptr(sr)), "qsp_eval_kkt")
+        out = (res,) + ((pt,) if parts else ()) + ((sr,) if stages else ())
+        return out[0] if len(out) == 1 else out
+
+    def eval_kkt_device(self, io, stream=None):
+        """eval_kkt on caller-owned device memory (io: _lib.KktIO of device pointers), asynchronous."""
+        check(self._L.qsp_eval_kkt_device(self._h, C.byref(io), C.c_void_p(stream) if stream else None),
+              "qsp_eval_kkt_device")
+
     # ------------------------------- rollout costs / u0 cost landscape
-    INTEGRATORS = {"euler": 0, "rk4": 1}   # QSP_ROLLOUT_EULER / QSP_ROLLOUT_RK4
+    INTEGRATORS ={"euler": 0, "rk4": 1}   # QSP_ROLLOUT_EULER / QSP_ROLLOUT_RK4
 
     def _rollout_opts(self, integrator, cost_scale):
         if integrator not in self.INTEGRATORS:
@@ -371,10 +413,11 @@ class OcpSolver:
         o.cost_scale = 1 if cost_scale else 0
         return o
 
-    def _rollout_refs(self, yref, yref_e):
+    def _rollout_refs(self, yref, yref_e, flush=True):
         """References of a rollout call: given arrays, or (None) the handle's staged ones -- the last controller
-        step's, or what set('cost_y_ref*') holds when that is newer (flushed here, as solve() would)."""
-        if (yref is None or yref_e is None) and "yref" in self._dirty and not self._refs_staged:
+        step's, or what set('cost_y_ref*') holds when that is newer (flushed here, as solve() would; flush=False:
+        only what the device already holds)."""
+        if flush and (yref is None or yref_e is None) and "yref" in self._dirty and not self._refs_staged:
             check(self._L.qsp_set_yref(self._h, ptr(f64(self._yref)), ptr(f64(self._yref_e))), "qsp_set_yref")
             self._dirty.discard("yref")
         yr = None if yref is None else f64(np.broadcast_to(np.asarray(yref, np.float64), (self.B, self.N, 6)))
@@ -742,3 +785,17 @@ class OcpSolver:
         check(self._L.qsp_qp_solve(self._h, nb, *[ptr(a) for a in arrs], ptr(dx), ptr(du), ptr(pi), ptr(lam),
                                    ptr(iters), ptr(qst)), "qsp_qp_solve")
         return dict(dx=dx, du=du, pi=pi, lam=lam, iters=iters, qp_status=qst)
+
+    def qp_residuals(self, A, B, b, H, g, lo, hi, dx0, dx, du, pi, lam):
+        """KKT residuals of QP points recomputed on the device (qsp_qp_residuals): qp_solve's array layouts,
+        none of its restrictions on H, the bound widths or A.  Returns a dict of (nb,) arrays keyed
+        _lib.QP_RESIDUALS (stat_u, stat_x, dyn, infeas, comp, dual); the stage-0 s row counts in the last
+        three with stage0_s_bound only."""
+        N = self.N
+        nb = np.shape(b)[0]
+        shapes = ((nb, N, 16), (nb, N, 8), (nb, N, 4), (nb, 6 * N + 4), (nb, 6 * N + 4), (nb, N, 3), (nb, N, 3), (nb, 4),
+                  (nb, N + 1, 4), (nb, N, 2), (nb, N, 4), (nb, N, 6))
+        arrs = [f64(a, sh) for a, sh in zip((A, B, b, H, g, lo, hi, dx0, dx, du, pi, lam), shapes)]
+        res = np.zeros((nb, len(_lib.QP_RESIDUALS)))
+        check(self._L.qsp_qp_residuals(self._h, nb, *[ptr(a) for a in arrs], ptr(res)), "qsp_qp_residuals")
+        return {k: res[:, i].copy() for i, k in enumerate(_lib.QP_RESIDUALS)}

@@ -49,7 +49,9 @@ extern "C" {
                                 qsp_gen_sim_noise;
                              9: qsp_default_waypoint_opts, qsp_gen_waypoints (and, without a new number, the
                                 query qsp_get_fixed_horizon and the KKT evaluators qsp_eval_kkt,
-                                qsp_eval_kkt_device, qsp_qp_residuals with the getter qsp_get_lam) */
+                                qsp_eval_kkt_device, qsp_qp_residuals with the getter qsp_get_lam, and the
+                                sensitivities qsp_default_sens_opts, qsp_eval_sens, qsp_eval_sens_device,
+                                qsp_get_sens, qsp_qp_sens) */
 
 #define QSP_OK 0
 #define QSP_ERR_ARG (-1)
@@ -291,6 +293,88 @@ typedef struct {
     double* stage_res;       /* B x (N+1) x 4 or NULL */
 } qsp_kkt_io;
 int qsp_eval_kkt_device(qsp_solver* s, const qsp_kkt_io* io, void* hip_stream);
+
+/* ------------------------------------------------- solution sensitivities du_k/dx0 on the device
+ * How the optimal inputs move when the measured state moves: the first-order sensitivities dU_k = du_k/dx0
+ * (2 x 4 each, row-major) of ANY point (X, U), in both nlp_modes and without a previous solve.  The stage-0
+ * block K0 = dU_0 is the feedback gain: between two solves a faster loop applies u = u0 + K0 (x - x0).
+ * Definition -- the BARRIER-SMOOTHED GAUSS-NEWTON SENSITIVITY (csrc/qsp_sens.hpp):
+ *   stage data  A_k, B_k from one RK4 step with sensitivities at (x_k, u_k), as qsp_eval_kkt forms them;
+ *   Hessian     Hx = tau W[0..3], Hu = tau W[4..5] for k < N, W_e at N (the exact Gauss-Newton Hessian of the
+ *               least-squares cost);
+ *   bounds      each of the six bound sides of h = [s; u_n; u_t] at stage k adds lam / max(slack, t_floor) to
+ *               that component's diagonal entry, slack = v - lh or uh - v; the stage-0 s pair only with
+ *               s0_bound.  An inactive bound (lam = 0) adds nothing, an active one lam / t_floor, which pins the
+ *               component; as t_floor -> 0 under strict complementarity this tends to the exact active-set
+ *               sensitivity, and it is what the interior point's last factorisation holds;
+ *   backward    P_N = diag(W_e), then the solver's own Riccati step for k = N-1 .. 0: the stage gains K_k
+ *               (du_k = K_k dx_k) and P_0, the Hessian of the optimal value in dx0;
+ *   forward     only when dU is asked for: Phi_0 = I, dU_k = K_k Phi_k, Phi_{k+1} = (A_k + B_k K_k) Phi_k.
+ * It is the sensitivity of the Gauss-Newton QP at the point, not of the exact-Hessian NLP.  Parity against
+ * acados' solution sensitivities is unpinned, as everywhere: no reference fixture fixes them.
+ * Accuracy (measured against a dense KKT solve on data of order one, tests/test_sens_host.py): with input
+ * bounds pinned alone, by weights up to 1e10, the gains hold to a few eps relative.  A pinned s carries its
+ * weight d = lam / t_floor through the Riccati recursion, which cancels it twice (the limit qsp_qp_solve's
+ * header describes): K0 was off by 4e-6 relative at d = 4e7 and by 0.4 at d = 7e9 in mid-horizon.  The OCP's own
+ * data couple s more weakly (B = O(Ts)); where gains at an active s bound matter, raise t_floor.
+ * The implied multipliers are the true ones at a KKT point; away from one the stationarity residual of an
+ * interior component acts as a (spurious) barrier, so read such gains beside qsp_eval_kkt's residuals.
+ *   x0   B x 4 or NULL.  Given, it stands for X's row 0 as the point of stage 0 (used as given, without the
+ *        controller's s pre-wrap).
+ *   PI, LAM  LAM: B x N x 6 as qsp_get_lam.  LAM == NULL with PI: the implied multipliers of qsp_eval_kkt,
+ *        formed against the references the handle has staged (QSP_ERR_STATE if none ever were).  Both NULL:
+ *        zero multipliers, the unconstrained LQR gains.
+ *   K0   B x 2 x 4;  K  B x N x 2 x 4 or NULL (the stage gains);  dU  B x N x 2 x 4 or NULL;
+ *   P0   B x 10 or NULL, the upper triangle by rows: (0,0)(0,1)(0,2)(0,3)(1,1)(1,2)(1,3)(2,2)(2,3)(3,3);
+ *   flag B (int32) or NULL.
+ * A lane where any value read (every row of X, U and of the multipliers given; x0; the references with implied
+ * multipliers), any linearisation or any 1/det is not finite gets NaN in every output and 1 in flag; every
+ * other lane gets 0 and keeps the bits it has without that lane.  A NULL optional output is not written.
+ * QSP_ERR_STATE without shapes; QSP_ERR_ARG for a null required pointer (X, U, K0), an opts of another
+ * struct_size, t_floor <= 0 or not finite, s0_bound outside -1, 0, 1.  opts == NULL: the defaults.  The
+ * handle owns the workspace of these calls (allocated on first use): calls on one handle must not overlap. */
+typedef struct {
+    int32_t struct_size;     /* sizeof(qsp_sens_opts) */
+    int32_t s0_bound;        /* -1 (default): the handle's stage0_s_bound; 0 / 1: that value for this call */
+    double t_floor;          /* smallest slack a multiplier is divided by; default 1e-8 */
+} qsp_sens_opts;
+void qsp_default_sens_opts(qsp_sens_opts* o);
+int qsp_eval_sens(qsp_solver* s, const qsp_sens_opts* opts, const double* x0 /* B x 4 or NULL */, const double* X,
+                  const double* U, const double* PI /* or NULL */, const double* LAM /* or NULL */,
+                  double* K0 /* B x 2 x 4 */, double* K /* B x N x 2 x 4 or NULL */,
+                  double* dU /* B x N x 2 x 4 or NULL */, double* P0 /* B x 10 or NULL */, int32_t* flag /* B or NULL */);
+/* The same on caller-owned device memory, asynchronous on hip_stream (NULL: the handle's), no copies and no
+ * synchronisation; yref NULL = the handle's staged references, shape_id NULL = the handle's. */
+typedef struct {
+    const double* x0;        /* B x 4 or NULL */
+    const double* X;         /* B x (N+1) x 4 */
+    const double* U;         /* B x N x 2 */
+    const double* PI;        /* B x N x 4 or NULL */
+    const double* LAM;       /* B x N x 6 or NULL */
+    const double* yref;      /* B x N x 6 or NULL */
+    const int32_t* shape_id; /* B or NULL */
+    double* K0;              /* B x 2 x 4 */
+    double* K;               /* B x N x 2 x 4 or NULL */
+    double* dU;              /* B x N x 2 x 4 or NULL */
+    double* P0;              /* B x 10 or NULL */
+    int32_t* flag;           /* B or NULL */
+} qsp_sens_io;
+int qsp_eval_sens_device(qsp_solver* s, const qsp_sens_opts* opts, const qsp_sens_io* io, void* hip_stream);
+/* The same computation at the last solve's final, unshifted iterate (after qsp_solve the bits of
+ * qsp_get_x/u): with its bound multipliers (qsp_get_lam) in nlp_mode 1, with the implied ones from qsp_get_pi
+ * and the staged references in nlp_mode 0.  QSP_ERR_STATE before any solve.  After qsp_controller_solve the
+ * iterate and, in nlp_mode 1, its bound multipliers are still the step's own (never shifted), so nlp_mode 1
+ * answers there too; in nlp_mode 0 the epilogue keeps the dynamics multipliers only shifted by one stage
+ * (pi_0 is gone), the implied multipliers cannot be formed, and the call returns QSP_ERR_STATE.  After
+ * qsp_solve_device on a caller's stream, synchronise that stream first. */
+int qsp_get_sens(qsp_solver* s, const qsp_sens_opts* opts, double* K0, double* K, double* dU, double* P0, int32_t* flag);
+/* The linear algebra alone, on caller-given QP data of nb lanes and horizon N (any N >= 1, not the handle's):
+ * A nb x N x 16, B nb x N x 8 and the diagonal Hessian H nb x (6N+4) of qsp_qp_solve's layout, with the
+ * barrier terms already in H (H may differ per stage and lane).  A must have the structure qsp_qp_solve
+ * asks for (the identity except a02, a03, a12, a13, a23, a33), else QSP_ERR_ARG.  Outputs, flag and lane
+ * isolation as above. */
+int qsp_qp_sens(qsp_solver* s, int32_t nb, int32_t N, const double* A, const double* B, const double* H, double* K0,
+                double* K, double* dU, double* P0, int32_t* flag);
 int qsp_get_time_tot(qsp_solver* s, double* ms);                                        /* 'time_tot' */
 /* dims of the handle (outputs of a MEX/FFI layer are sized from these, never from caller input) */
 int qsp_get_dims(const qsp_solver* s, int32_t* N, int32_t* B);

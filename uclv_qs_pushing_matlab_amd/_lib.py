@@ -84,6 +84,18 @@ KKT_PARTS = ("stat_u", "stat_x", "stat_term", "eq_dyn", "eq_x0", "ineq", "comp")
 QP_RESIDUALS = ("stat_u", "stat_x", "dyn", "infeas", "comp", "dual")              # qsp_qp_residuals' columns
 
 
+class SensOpts(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("s0_bound", C.c_int32), ("t_floor", C.c_double)]
+
+
+class SensIO(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in
+                ("x0", "X", "U", "PI", "LAM", "yref", "shape_id", "K0", "K", "dU", "P0", "flag")]
+
+
+SENS_OUTPUTS = ("K0", "K", "dU", "P0", "flag")   # what qsp_eval_sens can return (K0 always computed)
+
+
 class OpenLoopOpts(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("n_steps", C.c_int32), ("M", C.c_int32), ("u_steps", C.c_int32),
                 ("clip", C.c_int32), ("store_tile", C.c_int32), ("Ts", C.c_double), ("v_alpha", C.c_double),
@@ -187,6 +199,11 @@ _SIGS = {
     "qsp_get_lam": [_P, _P],
     "qsp_eval_kkt": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "qsp_eval_kkt_device": [_P, C.POINTER(KktIO), _P],
+    "qsp_default_sens_opts": [C.POINTER(SensOpts)],
+    "qsp_eval_sens": [_P, C.POINTER(SensOpts), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "qsp_eval_sens_device": [_P, C.POINTER(SensOpts), C.POINTER(SensIO), _P],
+    "qsp_get_sens": [_P, C.POINTER(SensOpts), _P, _P, _P, _P, _P],
+    "qsp_qp_sens": [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P],
     "qsp_default_rollout_opts": [C.POINTER(RolloutOpts)],
     "qsp_rollout_cost": [_P, C.POINTER(RolloutOpts), _I, _P, _P, _P, _P, _P, _P, _P],
     "qsp_rollout_cost_device": [_P, C.POINTER(RolloutOpts), _I, C.POINTER(RolloutIO), _P],
@@ -205,7 +222,7 @@ _SIGS = {
     "qsp_last_error": [],
 }
 _VOID = {"qsp_default_options", "qsp_default_rollout_opts", "qsp_default_open_loop_opts", "qsp_default_sim_noise",
-         "qsp_default_waypoint_opts"}
+         "qsp_default_waypoint_opts", "qsp_default_sens_opts"}
 EXPORTED = tuple(_SIGS)
 
 

@@ -10,9 +10,10 @@ import sys
 PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libqsp_nmpc.so")
-SOURCES = ["qsp_solver.hip", "qsp_sim.hip", "qsp_capi.hip", "qsp_rollout.hip", "qsp_openloop.hip", "qsp_kkt.hip"]
+SOURCES = ["qsp_solver.hip", "qsp_sim.hip", "qsp_capi.hip", "qsp_rollout.hip", "qsp_openloop.hip", "qsp_kkt.hip",
+           "qsp_sens.hip"]
 HEADERS = ["qsp_math.hpp", "qsp_fp.hpp", "qsp_riccati.hpp", "qsp_ipm.hpp", "qsp_types.h", "qsp_kernels.h", "qsp_layout.h", "qsp_candidates.hpp",
-           "qsp_devbuf.hpp", "qsp_noise.hpp", "qsp_kkt.hpp","../../include/qsp_nmpc.h"]
+           "qsp_devbuf.hpp", "qsp_noise.hpp", "qsp_kkt.hpp", "qsp_sens.hpp", "../../include/qsp_nmpc.h"]
 ARCH = os.environ.get("QSP_OFFLOAD_ARCH", "gfx950")
 
 

@@ -155,3 +155,9 @@ class NMPCController:
         u = self.ocp_solver.controller_solve(np.broadcast_to(x0, (self.batch, 4)), index_time)
         self.cost_function_vect.append(self.ocp_solver.get_cost())      # :420
         return u
+
+    def feedback_gain(self, t_floor=1e-8):
+        """K0 (B, 2, 4) = du_0/dx0 at the last solve's iterate: between two solves a faster loop applies
+        u = u0 + K0 (x - x0).  Needs nlp_solver_type 'SQP' (OcpSolver.get_sens: 'SQP_RTI' keeps no unshifted
+        multipliers after a controller step)."""
+        return self.ocp_solver.get_sens(t_floor=t_floor)["K0"]

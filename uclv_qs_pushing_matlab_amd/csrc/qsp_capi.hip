@@ -67,6 +67,7 @@ struct __attribute__((visibility("hidden"))) qsp_solver {
     Dev<int32_t> wdone, wperm, wnit, whist, wadjv;
     Dev<uint8_t> pool[STAGE_POOL];  // device images of one call's host arrays (bytes), handed out by Staging
     Dev<double> ol_ring;            // qsp_open_loop's plant delay buffer (clipped u_t of the last D steps)
+    Dev<double> wsens, wsensK;      // the sensitivity entries' workspace (SensField; the gains of the forward pass), on first use
     bool solved = false;            // wU holds a solve's iterate (qsp_cost_landscape with U_tail = NULL)
     int32_t T = 0;
     bool have_traj = false;
@@ -1521,6 +1522,159 @@ int qsp_qp_residuals(qsp_solver* s, int32_t nb, const double* A, const double* B
     a.res = st.out(res, qd.qp_res());
     if (st.err) return st.err;
     HIPCHK(launch_kkt_qp(a, s->stream));
+    return st.finish();
+}
+
+// ------------------------------------- solution sensitivities du_k/dx0
+void qsp_default_sens_opts(qsp_sens_opts* o) {
+    std::memset(o, 0, sizeof(*o));
+    o->struct_size = (int32_t)sizeof(qsp_sens_opts);
+    o->s0_bound = -1;
+    o->t_floor = 1e-8;
+}
+
+// opts (NULL: the defaults) checked and resolved against the handle
+static int sens_opts(qsp_solver* s, const qsp_sens_opts* opts, const std::string& w, int32_t& s0_bound, double& t_floor) {
+    qsp_sens_opts o;
+    qsp_default_sens_opts(&o);
+    if (opts) {
+        if (opts->struct_size != (int32_t)sizeof(qsp_sens_opts))
+            return fail(QSP_ERR_ARG, w + ": qsp_sens_opts.struct_size != sizeof(qsp_sens_opts) (stale layout?)");
+        o = *opts;
+    }
+    if (!(std::isfinite(o.t_floor) && o.t_floor > 0.0)) return fail(QSP_ERR_ARG, w + ": t_floor must be finite and > 0");
+    if (o.s0_bound < -1 || o.s0_bound > 1) return fail(QSP_ERR_ARG, w + ": s0_bound must be -1, 0 or 1");
+    s0_bound = o.s0_bound < 0 ? s->p.s0_bound : o.s0_bound;
+    t_floor = o.t_floor;
+    return QSP_OK;
+}
+
+// the gains' workspace of a call of nb lanes and horizon N that asks for dU
+static hipError_t sens_gain_buffer(qsp_solver* s, const double* dU, size_t nb, size_t N, double** wK) {
+    *wK = nullptr;
+    if (!dU) return hipSuccess;
+    const hipError_t e = s->wsensK.ensure((size_t)SENS_NK * N * nb);
+    *wK = s->wsensK.data();
+    return e;
+}
+
+// host entry and _device twin, as eval_kkt_run
+static int eval_sens_run(qsp_solver* s, const char* who, bool host, const qsp_sens_opts* opts, const qsp_sens_io* io,
+                         void* stream) {
+    const std::string w(who);
+    if (!s || !io || !io->X || !io->U || !io->K0) return fail(QSP_ERR_ARG, w + missing(host));
+    SensNlpArgs a;
+    std::memset(&a, 0, sizeof a);
+    int r = sens_opts(s, opts, w, a.s0_bound, a.t_floor);
+    if (r) return r;
+    if (s->n_shapes < 1) return fail(QSP_ERR_STATE, w + ": no shapes set");
+    const bool implied = !io->LAM && io->PI;
+    if (implied && !io->yref && !s->have_yref)
+        return fail(QSP_ERR_STATE, w + ": implied multipliers need references, and none are staged on the handle");
+    HIPCHK(hipSetDevice(s->o.device));
+    qsp_sens_io d = *io;
+    Staging st(s);
+    const Dims& dim = s->dim;
+    const size_t gains = dim.U() * 4;   // B x N x 2 x 4
+    if (host) {
+        d.x0 = st.in(io->x0, dim.x0());
+        d.X = st.in(io->X, dim.X());
+        d.U = st.in(io->U, dim.U());
+        d.PI = st.in(io->PI, dim.PI());
+        d.LAM = st.in(io->LAM, dim.lam());
+        d.yref = st.in(io->yref, dim.yref());
+        d.K0 = st.out(io->K0, dim.lane() * 8);
+        d.K = st.out(io->K, gains);
+        d.dU = st.out(io->dU, gains);
+        d.P0 = st.out(io->P0, dim.lane() * 10);
+        d.flag = st.out(io->flag, dim.lane());
+        if (st.err) return st.err;
+    }
+    HIPCHK(s->wsens.ensure((size_t)SF_COUNT * dim.N * dim.B));
+    HIPCHK(sens_gain_buffer(s, d.dU, dim.B, dim.N, &a.wK));
+    a.p = s->p;
+    a.B = s->o.batch;
+    a.shapes = s->shapes.data();
+    a.n_shapes = s->n_shapes;
+    a.shape_id = d.shape_id ? d.shape_id : s->shape_id.data();
+    a.x0 = d.x0;
+    a.X = d.X;
+    a.U = d.U;
+    a.PI = d.PI;
+    a.LAM = d.LAM;
+    a.yref = implied ? (d.yref ? d.yref : s->yref.data()) : nullptr;
+    a.ws = s->wsens.data();
+    a.out = {d.K0, d.K, d.dU, d.P0, d.flag};
+    HIPCHK(launch_sens_nlp(a, stream_of(s, host, stream)));
+    return host ? st.finish() : QSP_OK;
+}
+
+int qsp_eval_sens(qsp_solver* s, const qsp_sens_opts* opts, const double* x0, const double* X, const double* U,
+                  const double* PI, const double* LAM, double* K0, double* K, double* dU, double* P0, int32_t* flag) {
+    const qsp_sens_io io = {x0, X, U, PI, LAM, nullptr, nullptr, K0, K, dU, P0, flag};
+    return eval_sens_run(s, "qsp_eval_sens", true, opts, &io, nullptr);
+}
+
+int qsp_eval_sens_device(qsp_solver* s, const qsp_sens_opts* opts, const qsp_sens_io* io, void* stream) {
+    return eval_sens_run(s, "qsp_eval_sens_device", false, opts, io, stream);
+}
+
+int qsp_get_sens(qsp_solver* s, const qsp_sens_opts* opts, double* K0, double* K, double* dU, double* P0, int32_t* flag) {
+    if (!s || !K0) return fail(QSP_ERR_ARG, "qsp_get_sens: null argument");
+    if (!s->solved) return fail(QSP_ERR_STATE, "qsp_get_sens: no solve yet");
+    const bool merit = s->o.nlp_mode == QSP_NLP_SQP_MERIT && s->wnlp.data();
+    if (s->last_controller && !merit)
+        return fail(QSP_ERR_STATE, "qsp_get_sens: after qsp_controller_solve in nlp_mode 0 the handle keeps only the "
+                                   "shifted dynamics multipliers");
+    // The unshifted final iterate, through the host entry (a getter, not a hot path): X and U from the SQP's
+    // workspace, which the epilogue reads and leaves (after qsp_solve the bits of qsp_get_x/u); the
+    // bound multipliers are the merit SQP's (qsp_get_lam: never shifted; with them PI is not read), or the
+    // implied ones from qsp_get_pi in nlp_mode 0.
+    const Dims& dim = s->dim;
+    std::vector<double> X(dim.X()), U(dim.U()), PI, LAM;
+    int r = d2h(s, X.data(), s->wX, dim.X());
+    if (!r) r = d2h(s, U.data(), s->wU, dim.U());
+    if (!r && merit) {
+        LAM.resize(dim.lam());
+        r = qsp_get_lam(s, LAM.data());
+    } else if (!r) {
+        PI.resize(dim.PI());
+        r = qsp_get_pi(s, PI.data());
+    }
+    if (r) return r;
+    const qsp_sens_io io = {nullptr, X.data(), U.data(), PI.empty() ? nullptr : PI.data(),
+                            LAM.empty() ? nullptr : LAM.data(), nullptr, nullptr, K0, K, dU, P0, flag};
+    return eval_sens_run(s, "qsp_get_sens", true, opts, &io, nullptr);
+}
+
+int qsp_qp_sens(qsp_solver* s, int32_t nb, int32_t N, const double* A, const double* B, const double* H, double* K0,
+                double* K, double* dU, double* P0, int32_t* flag) {
+    if (!s || nb < 1 || N < 1 || !A || !B || !H || !K0) return fail(QSP_ERR_ARG, "qsp_qp_sens: bad argument");
+    for (size_t q = 0; q < (size_t)nb * N; ++q) {
+        const double* Ak = A + q * 16;
+        const double st[10] = {Ak[0] - 1.0, Ak[1], Ak[4], Ak[5] - 1.0, Ak[8], Ak[9], Ak[10] - 1.0, Ak[12], Ak[13], Ak[14]};
+        for (double v : st)
+            if (v != 0.0) return fail(QSP_ERR_ARG, "qsp_qp_sens: A lacks the pusher-slider structure");
+    }
+    HIPCHK(hipSetDevice(s->o.device));
+    const Dims qd{(size_t)nb, (size_t)N};   // the QPs' own batch
+    const size_t gains = qd.U() * 4;
+    Staging st(s);
+    SensQpArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.N = N;
+    a.nb = nb;
+    a.A = st.in(A, qd.qp_A());
+    a.B = st.in(B, qd.qp_B());
+    a.H = st.in(H, qd.qp_Hg());
+    a.out.K0 = st.out(K0, qd.lane() * 8);
+    a.out.K = st.out(K, gains);
+    a.out.dU = st.out(dU, gains);
+    a.out.P0 = st.out(P0, qd.lane() * 10);
+    a.out.flag = st.out(flag, qd.lane());
+    if (st.err) return st.err;
+    HIPCHK(sens_gain_buffer(s, a.out.dU, qd.B, qd.N, &a.wK));
+    HIPCHK(launch_sens_qp(a, s->stream));
     return st.finish();
 }
 

@@ -307,4 +307,46 @@ struct KktQpArgs {
 };
 hipError_t launch_kkt_qp(const KktQpArgs& a, hipStream_t stream);
 
+// Solution sensitivities du_k/dx_0 (qsp_sens.hip, qsp_sens.hpp).  The workspace of the NLP entry is stage- and
+// field-major with the lane fastest: field f of stage k < N of lane i at (k * SF_COUNT + f) * B + i, so that
+// the walk (one thread per lane) loads consecutive addresses across a wave.  wK, the gains kept for the
+// forward pass, has the same order with 8 fields.
+enum SensField : int { SF_A = 0, SF_B = 6, SF_HX = 14, SF_HU = 18, SF_COUNT = 20 };
+constexpr int SENS_NK = 8;
+struct SensOut {
+    double* K0;                // B x 2 x 4
+    double* K;                 // B x N x 2 x 4 or nullptr
+    double* dU;                // B x N x 2 x 4 or nullptr (nullptr: no forward pass)
+    double* P0;                // B x 10 or nullptr (sidx order)
+    int32_t* flag;             // B or nullptr (1: the lane is non-finite, all its outputs NaN)
+};
+struct SensNlpArgs {
+    SolveParams p;             // the handle's: N, Ts, tau, W, We, lh, uh are read
+    int32_t B;
+    int32_t s0_bound;          // 1: the s pair of stage 0 counts in the barrier
+    double t_floor;            // > 0
+    const ShapeDev* shapes;
+    int32_t n_shapes;
+    const int32_t* shape_id;   // B (nullptr: shape 0); clamped into [0, n_shapes)
+    const double* x0;          // B x 4 or nullptr: stands for X's row 0
+    const double* X;           // B x (N+1) x 4
+    const double* U;           // B x N x 2
+    const double* PI;          // B x N x 4 or nullptr
+    const double* LAM;         // B x N x 6 or nullptr (PI: implied multipliers; neither: zero)
+    const double* yref;        // B x N x 6, read for the implied multipliers only
+    double* ws;                // SF_COUNT x N x B
+    double* wK;                // SENS_NK x N x B, used with out.dU only
+    SensOut out;
+};
+hipError_t launch_sens_nlp(const SensNlpArgs& a, hipStream_t stream);   // sens_lin_kernel, then sens_walk_kernel
+struct SensQpArgs {
+    int32_t N, nb;
+    const double* A;           // nb x N x 16, the pusher-slider structure (checked by the entry)
+    const double* B;           // nb x N x 8
+    const double* H;           // nb x (6N+4), barrier in it
+    double* wK;                // SENS_NK x N x nb, used with out.dU only
+    SensOut out;
+};
+hipError_t launch_sens_qp(const SensQpArgs& a, hipStream_t stream);     // sens_walk_kernel on caller data
+
 }  // namespace qsp

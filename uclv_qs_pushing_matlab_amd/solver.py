@@ -345,6 +345,8 @@ class OcpSolver:
             out = np.zeros((B, N, 6))
             check(self._L.qsp_get_lam(self._h, ptr(out)), "get('lam')")
             return out if stage is None else out[:, stage]
+        if field == "sens_K0":     # the feedback gain du_0/dx0 at the last solve()'s iterate (get_sens)
+            return self.get_sens()["K0"]
         if field == "time_tot":
             ms = C.c_double()
             check(self._L.qsp_get_time_tot(self._h, C.byref(ms)), "get('time_tot')")
@@ -400,6 +402,80 @@ class OcpSolver:
         """eval_kkt on caller-owned device memory (io: _lib.KktIO of device pointers), asynchronous."""
         check(self._L.qsp_eval_kkt_device(self._h, C.byref(io), C.c_void_p(stream) if stream else None),
               "qsp_eval_kkt_device")
+
+    # ------------------------------- solution sensitivities du_k/dx0
+    @staticmethod
+    def _sens_want(want):
+        """The outputs asked for, checked before any library call: names of _lib.SENS_OUTPUTS."""
+        want = (want,) if isinstance(want, str) else tuple(want)
+        bad = [w for w in want if w not in _lib.SENS_OUTPUTS]
+        if bad:
+            raise ValueError(f"want: unknown output(s) {bad}; choose from {_lib.SENS_OUTPUTS}")
+        return want
+
+    def _sens_opts(self, t_floor, s0_bound):
+        o = _lib.SensOpts()
+        self._L.qsp_default_sens_opts(C.byref(o))
+        o.t_floor = float(t_floor)
+        o.s0_bound = -1 if s0_bound is None else int(bool(s0_bound))
+        return o
+
+    @staticmethod
+    def _sens_outputs(want, nb, N):
+        shapes = {"K0": (nb, 2, 4), "K": (nb, N, 2, 4), "dU": (nb, N, 2, 4), "P0": (nb, 10)}
+        out = {k: np.zeros(sh) for k, sh in shapes.items() if k in want or k == "K0"}
+        if "flag" in want:
+            out["flag"] = np.zeros(nb, np.int32)
+        return out
+
+    def eval_sens(self, X, U, PI=None, LAM=None, x0=None, t_floor=1e-8, want=("K0",), s0_bound=None):
+        """Barrier-smoothed Gauss-Newton sensitivities du_k/dx0 at a point (qsp_eval_sens; definition in
+        include/qsp_nmpc.h): a dict with the arrays named in want -- K0 (B, 2, 4) the feedback gain, K (B, N, 2, 4)
+        the stage gains, dU (B, N, 2, 4) = du_k/dx0, P0 (B, 10) the value Hessian's upper triangle, flag (B,) 1 on
+        a non-finite lane (whose outputs are NaN).  LAM (B, N, 6) as get('lam'); LAM None with PI: the implied
+        multipliers of eval_kkt against the handle's references; both None: the unconstrained LQR gains.
+        x0 given stands for X's row 0.  s0_bound None: the handle's stage0_s_bound."""
+        want = self._sens_want(want)
+        B, N = self.B, self.N
+        X, U = f64(X, (B, N + 1, 4)), f64(U, (B, N, 2))
+        PI = None if PI is None else f64(PI, (B, N, 4))
+        LAM = None if LAM is None else f64(LAM, (B, N, 6))
+        x0 = None if x0 is None else f64(self._lanes(x0, 4))
+        if LAM is None and PI is not None:
+            self._rollout_refs(None, None, flush=self._refs_given)
+        out = self._sens_outputs(want, B, N)
+        o = self._sens_opts(t_floor, s0_bound)
+        check(self._L.qsp_eval_sens(self._h, C.byref(o), ptr(x0), ptr(X), ptr(U), ptr(PI), ptr(LAM),
+                                    *[ptr(out.get(k)) for k in _lib.SENS_OUTPUTS]), "qsp_eval_sens")
+        return {k: out[k] for k in want}
+
+    def eval_sens_device(self, io, t_floor=1e-8, s0_bound=None, stream=None):
+        """eval_sens on caller-owned device memory (io: _lib.SensIO of device pointers), asynchronous."""
+        o = self._sens_opts(t_floor, s0_bound)
+        check(self._L.qsp_eval_sens_device(self._h, C.byref(o), C.byref(io), C.c_void_p(stream) if stream else None),
+              "qsp_eval_sens_device")
+
+    def get_sens(self, t_floor=1e-8, want=("K0",), s0_bound=None):
+        """eval_sens at the last solve's final, unshifted iterate (qsp_get_sens): its bound multipliers with 'SQP',
+        the implied ones with 'SQP_RTI'.  After controller_solve() with 'SQP' only: the RTI path keeps its dynamics
+        multipliers only shifted by one stage there, and the call raises QspError (-3)."""
+        want = self._sens_want(want)
+        out = self._sens_outputs(want, self.B, self.N)
+        o = self._sens_opts(t_floor, s0_bound)
+        check(self._L.qsp_get_sens(self._h, C.byref(o), *[ptr(out.get(k)) for k in _lib.SENS_OUTPUTS]), "qsp_get_sens")
+        return {k: out[k] for k in want}
+
+    def qp_sens(self, A, B, H, want=("K0",)):
+        """The sensitivity walk alone on caller-given QP data (qsp_qp_sens): A (nb, N, 16) of qp_solve's structure,
+        B (nb, N, 8), H (nb, 6N + 4) diagonal with the barrier terms in it; any horizon N.  A dict as eval_sens."""
+        want = self._sens_want(want)
+        A = f64(A)
+        nb, N = A.shape[0], A.shape[1]
+        A, B, H = f64(A, (nb, N, 16)), f64(B, (nb, N, 8)), f64(H, (nb, 6 * N + 4))
+        out = self._sens_outputs(want, nb, N)
+        check(self._L.qsp_qp_sens(self._h, nb, N, ptr(A), ptr(B), ptr(H), *[ptr(out.get(k)) for k in _lib.SENS_OUTPUTS]),
+              "qsp_qp_sens")
+        return {k: out[k] for k in want}
 
     # ------------------------------- rollout costs / u0 cost landscape
     INTEGRATORS ={"euler": 0, "rk4": 1}   # QSP_ROLLOUT_EULER / QSP_ROLLOUT_RK4

@@ -76,6 +76,16 @@ def qp_residuals(q, dx, du, pi, lam, stage0_s_bound):
     return res, scale
 
 
+def lam_of_stationarity(r):
+    """The implied-multiplier rule (implied_lam, csrc/qsp_point.hpp), the one statement of it in the tests: r
+    (nb, N, 3) the stationarity of (s, u_n, u_t) at stages k < N without bound multipliers -> lam (nb, N, 3, 2) with
+    lam_lo = r where r > 0, lam_hi = -r where r < 0, else 0, and the stage-0 s pair 0.  Exact: the bits of lam are
+    those of r, so a caller that forms r as the kernel does (tests/sens_ref.py::implied_lam) gets the kernel's."""
+    lam = np.stack([np.where(r > 0.0, r, 0.0), np.where(r < 0.0, -r, 0.0)], 3)
+    lam[:, 0, 0] = 0.0
+    return lam
+
+
 def nlp_residuals(X, U, PI, LAM, yref, yref_e, xn, A, B, tau, W, We, lh, uh, stage0_s_bound, x0=None):
     """The NLP iterate's residuals from its stage data xn, A, B = one RK4 step with sensitivities at
     (X[:, :N], U) (nb x N x 4, x 4 x 4, x 4 x 2).  LAM None: the implied multipliers.  Returns a dict:
@@ -97,8 +107,7 @@ def nlp_residuals(X, U, PI, LAM, yref, yref_e, xn, A, B, tau, W, We, lh, uh, sta
     if LAM is None:
         r = np.concatenate([rx0[..., 3:4], ru0], 2)               # (s, u_n, u_t)
         sr = np.concatenate([sx0[..., 3:4], su0], 2)
-        lam = np.stack([np.maximum(r, 0.0), np.maximum(-r, 0.0)], 3)
-        lam[:, 0, 0] = 0.0
+        lam = lam_of_stationarity(r)
         lam_err = BOUND * np.repeat(sr[..., None], 2, 3)
         lam_err[:, 0, 0] = 0.0
     else:

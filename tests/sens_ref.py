@@ -16,6 +16,8 @@ the barrier diagonal of an NLP point as qsp_eval_sens forms it (nlp_H), and the 
 """
 import numpy as np
 
+import kkt_ref
+
 EPS = np.finfo(float).eps
 SIDX = [(0, 0), (0, 1), (0, 2), (0, 3), (1, 1), (1, 2), (1, 3), (2, 2), (2, 3), (3, 3)]   # sidx, qsp_riccati.hpp
 
@@ -84,20 +86,6 @@ def row_scale(ref, name):
 
 
 OUTPUTS = ("K0", "K", "dU", "P0")
-
-
-def build_host_program(out, sanitize):
-    """tests/stubs/sens_main.cpp (csrc/qsp_sens.hpp for the host) compiled to `out`, contraction off as the
-    library.  sanitize: with the address and undefined-behaviour sanitizers, as tests/test_kkt_host.py builds its
-    program (the CPU test); without them for the GPU test, which only needs the program's bits."""
-    import os
-    import subprocess
-    from conftest import ROOT
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan"]
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-ffp-contract=off",
-                           "-I", os.path.join(ROOT, "uclv_qs_pushing_matlab_amd", "csrc")] + (san if sanitize else []) +
-                          ["-g", "-w", os.path.join(ROOT, "tests", "stubs", "sens_main.cpp"), "-o", str(out)])
-    return str(out)
 
 
 def run_host_program(exe, path, A, B, H):
@@ -198,23 +186,22 @@ def fma(a, b, c):
 
 
 def implied_lam(X, U, PI, yref, A, B, W, tau):
-    """The implied multipliers (B, N, 6) operation for operation as sens_implied_lam (csrc/qsp_sens.hpp), so that
-    they are the bits the kernel forms: A (nb, N, 4, 4), B (nb, N, 4, 2) as qsp_eval_rk4 returns them."""
+    """The implied multipliers (B, N, 6) operation for operation as implied_lam (csrc/qsp_point.hpp) on the
+    gradient sens_nlp_stage hands it, so that they are the bits the kernel forms: A (nb, N, 4, 4), B (nb, N, 4, 2)
+    as qsp_eval_rk4 returns them.  The rule itself is kkt_ref.lam_of_stationarity."""
     nb, N = U.shape[:2]
-    lam = np.zeros((nb, N, 6))
+    r = np.zeros((nb, N, 3))                      # the stationarity of (s, u_n, u_t) without bound multipliers
     chain = lambda c, p: fma(c[3], p[3], fma(c[2], p[2], fma(c[1], p[1], c[0] * p[0])))
     for l in range(nb):
         for k in range(N):
             pk = PI[l, k]
             for i in range(2):
                 gu = tau * W[4 + i] * (U[l, k, i] - yref[l, k, 4 + i])
-                r = gu + chain(B[l, k, :, i], pk)
-                lam[l, k, 2 * (1 + i)], lam[l, k, 2 * (1 + i) + 1] = (r if r > 0.0 else 0.0), (-r if r < 0.0 else 0.0)
+                r[l, k, 1 + i] = gu + chain(B[l, k, :, i], pk)
             if k >= 1:
                 gs = tau * W[3] * (X[l, k, 3] - yref[l, k, 3])
-                r = gs - PI[l, k - 1, 3] + chain(A[l, k, :, 3], pk)
-                lam[l, k, 0], lam[l, k, 1] = (r if r > 0.0 else 0.0), (-r if r < 0.0 else 0.0)
-    return lam
+                r[l, k, 0] = gs - PI[l, k - 1, 3] + chain(A[l, k, :, 3], pk)
+    return kkt_ref.lam_of_stationarity(r).reshape(nb, N, 6)
 
 
 def nlp_H(X, U, LAM, W, We, tau, lh, uh, s0_bound, t_floor):

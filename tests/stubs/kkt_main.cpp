@@ -26,27 +26,25 @@ int main(int argc, char** argv) {
     const size_t N = (size_t)hdr[0], nb = (size_t)hdr[1];
     const int s0 = hdr[2];
     std::vector<double> A, B, b, H, g, lo, hi, dx0, dx, du, pi, lam;
-    const bool ok = read_doubles(f, A, nb * N * 16) && read_doubles(f, B, nb * N * 8) && read_doubles(f, b, nb * N * 4) &&
-                    read_doubles(f, H, nb * (6 * N + 4)) && read_doubles(f, g, nb * (6 * N + 4)) &&
-                    read_doubles(f, lo, nb * N * 3) && read_doubles(f, hi, nb * N * 3) && read_doubles(f, dx0, nb * 4) &&
+    using Q = qsp::QpLaneData;
+    const bool ok = read_doubles(f, A, nb * N * Q::NA) && read_doubles(f, B, nb * N * Q::NB) && read_doubles(f, b, nb * N * Q::Nb) &&
+                    read_doubles(f, H, nb * Q::hg(N)) && read_doubles(f, g, nb * Q::hg(N)) &&
+                    read_doubles(f, lo, nb * N * Q::NBOUND) && read_doubles(f, hi, nb * N * Q::NBOUND) && read_doubles(f, dx0, nb * 4) &&
                     read_doubles(f, dx, nb * (N + 1) * 4) && read_doubles(f, du, nb * N * 2) &&
                     read_doubles(f, pi, nb * N * 4) && read_doubles(f, lam, nb * N * 6);
     std::fclose(f);
     if (!ok) return 5;
     std::printf("kkt ok\n");
+    const qsp::PointIn pt = {nullptr, 0, nullptr, dx0.data(), dx.data(), du.data(), pi.data(), lam.data(), nullptr, nullptr};
     for (size_t i = 0; i < nb; ++i) {
         double lane[qsp::KKT_QP_NRES] = {0, 0, 0, 0, 0, 0};
         bool fin = true;
-        for (size_t k = 0; k <= N; ++k) {
-            const size_t ku = k < N ? k : N - 1;   // rows read for k < N only
-            const size_t sk = i * N + ku, hk = i * (6 * N + 4) + 6 * k;
-            const double* x = dx.data() + i * (N + 1) * 4;
-            const double* p = pi.data() + i * N * 4;
+        const qsp::QpLaneData q(A.data(), B.data(), b.data(), H.data(), g.data(), lo.data(), hi.data(), (int)N, i);
+        for (int kk = 0; kk <= (int)N; ++kk) {   // the kernel's own views (qsp_point.hpp) do the indexing
             double res[qsp::KKT_QP_NRES];
-            const bool sf = qsp::kkt_qp_stage((int)N, s0, (int)k, A.data() + sk * 16, B.data() + sk * 8, b.data() + sk * 4,
-                                              H.data() + hk, g.data() + hk, lo.data() + sk * 3, hi.data() + sk * 3,
-                                              dx0.data() + i * 4, x + 4 * k, du.data() + sk * 2, x + 4 * (ku + 1), p + 4 * ku,
-                                              p + 4 * (k >= 1 ? k - 1 : 0), lam.data() + sk * 6, res);
+            const qsp::PointRows r(pt, (int)N, i, kk);
+            const bool sf = qsp::kkt_qp_stage((int)N, s0, kk, q.Ak(kk), q.Bk(kk), q.bk(kk), q.Hk(kk), q.gk(kk), q.lok(kk), q.hik(kk),
+                                              r.x0, r.x, r.u, r.x1, r.pi, r.pip, r.lam, res);
             qsp::kkt_fold(qsp::KKT_QP_NRES, res, sf, lane, fin);
         }
         for (int q = 0; q < qsp::KKT_QP_NRES; ++q) std::printf("%a%c", fin ? lane[q] : __builtin_nan(""), q == 5 ? '\n' : ' ');

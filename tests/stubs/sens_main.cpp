@@ -29,27 +29,26 @@ int main(int argc, char** argv) {
     if (std::fread(hdr, sizeof(int32_t), 4, f) != 4 || hdr[0] < 1 || hdr[1] < 1) return 4;
     const size_t N = (size_t)hdr[0], nb = (size_t)hdr[1];
     std::vector<double> A, B, H;
-    const bool ok = read_doubles(f, A, nb * N * 16) && read_doubles(f, B, nb * N * 8) && read_doubles(f, H, nb * (6 * N + 4));
+    using Q = qsp::QpLaneData;
+    const bool ok = read_doubles(f, A, nb * N * Q::NA) && read_doubles(f, B, nb * N * Q::NB) && read_doubles(f, H, nb * Q::hg(N));
     std::fclose(f);
     if (!ok) return 5;
     std::printf("sens ok\n");
     std::vector<double> K(N * 8), dU(N * 8);
     for (size_t i = 0; i < nb; ++i) {
-        const double* Hl = H.data() + i * (6 * N + 4);
+        const Q q(A.data(), B.data(), nullptr, H.data(), nullptr, nullptr, nullptr, (int)N, i);   // the kernel's view
         double P[10], a[6], Kk[8];
-        bool fin = qsp::sens_terminal(Hl + 6 * N, P);
-        for (size_t k = N; k-- > 0;) {
-            const double* Ak = A.data() + (i * N + k) * 16;
-            a[0] = Ak[2]; a[1] = Ak[3]; a[2] = Ak[6]; a[3] = Ak[7]; a[4] = Ak[11]; a[5] = Ak[15];
-            fin = qsp::sens_back_step(a, B.data() + (i * N + k) * 8, Hl + 6 * k, Hl + 6 * k + 4, P, Kk) && fin;
-            for (int q = 0; q < 8; ++q) K[k * 8 + q] = Kk[q];
+        bool fin = qsp::sens_terminal(q.Hk((int)N), P);
+        for (int k = (int)N; k-- > 0;) {
+            Q::free_entries(q.Ak(k), a);
+            fin = qsp::sens_back_step(a, q.Bk(k), q.Hk(k), q.Hk(k) + 4, P, Kk) && fin;
+            for (int j = 0; j < 8; ++j) K[k * 8 + j] = Kk[j];
         }
         double Phi[16];
         qsp::sens_identity(Phi);
-        for (size_t k = 0; k < N; ++k) {
-            const double* Ak = A.data() + (i * N + k) * 16;
-            a[0] = Ak[2]; a[1] = Ak[3]; a[2] = Ak[6]; a[3] = Ak[7]; a[4] = Ak[11]; a[5] = Ak[15];
-            fin = qsp::sens_fwd_step(a, B.data() + (i * N + k) * 8, K.data() + k * 8, Phi, dU.data() + k * 8) && fin;
+        for (int k = 0; k < (int)N; ++k) {
+            Q::free_entries(q.Ak(k), a);
+            fin = qsp::sens_fwd_step(a, q.Bk(k), K.data() + k * 8, Phi, dU.data() + k * 8) && fin;
         }
         std::printf("%d\n", fin ? 0 : 1);
         print_row(K.data(), 8, fin);

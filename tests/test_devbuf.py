@@ -5,19 +5,14 @@ hipMemsetAsync with counting versions over malloc, and is built with the address
 sanitizers: ensure() keeps or replaces with one free, every destructor path ends with nothing live, a copy or
 fill above the capacity is an error that touches nothing, and Dims equals the shapes of qsp_kernels.h's comments
 at (B, N) = (5, 10) and (3, 32).  Nothing is loaded into Python."""
-import os
 import subprocess
 
-from conftest import ROOT
+import host_program
 
 
 def test_devbuf_program(tmp_path):
     exe = tmp_path / "devbuf_main"
-    subprocess.check_call(["g++", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
-                           "-I", os.path.join(ROOT, "uclv_qs_pushing_matlab_amd", "csrc"),
-                           "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                           "-static-libasan", "-static-libubsan", "-g", "-w",   # the runtimes in the program itself
-                           os.path.join(ROOT, "tests", "stubs", "devbuf_main.cpp"), "-o", str(exe)])
+    host_program.build("devbuf_main", exe, flags=host_program.HIP_HOST)
     r = subprocess.run([str(exe)], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     assert r.stdout.startswith("devbuf ok:"), r.stdout

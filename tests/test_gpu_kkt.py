@@ -15,7 +15,8 @@ import pytest
 
 import kkt_ref
 import manufactured_qp as mq
-from conftest import config2_x0, straight_traj
+import point_cases
+from point_cases import same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -23,50 +24,18 @@ NAMES = ("santal", "balea", "montana", "pulirapid")
 ERR_ARG, ERR_STATE = r"\(-1\)", r"\(-3\)"
 
 
-def bits(a):
-    return np.ascontiguousarray(a, np.float64).view(np.uint64)
-
-
-def same_bits(a, b):
-    return np.array_equal(bits(a), bits(b))
-
-
 def within(got, ref, scale, extra=0.0):
     return np.all(np.abs(got - ref) <= kkt_ref.BOUND * scale + extra)
 
 
-def make_solver(N, B, **kw):
-    from uclv_qs_pushing_matlab_amd.objects import make_shape
-    from uclv_qs_pushing_matlab_amd.solver import OcpSolver
-    s = OcpSolver(N=N, batch=B, **kw)
-    sid = np.arange(B) % 4
-    s.set_shapes([make_shape(n) for n in NAMES], shape_id=sid)
-    return s, sid
-
-
-def nlp_inputs(s, sid, seed):
-    """A point that is no solution: U uniform inside the input bounds, X an Euler rollout from x0 plus 1e-3
-    noise (defects, and the s bound on both sides), PI in +-1e3, LAM in [0, 1], the straight reference."""
-    B, N = s.B, s.N
-    rng = np.random.default_rng(seed)
-    x0 = config2_x0(B, seed)
-    U = rng.uniform(s._lh[1:], s._uh[1:], (B, N, 2))
-    X = np.zeros((B, N + 1, 4))
-    X[:, 0] = x0
-    for k in range(N):
-        X[:, k + 1] = X[:, k] + s.Ts * s.eval_dynamics(X[:, k], U[:, k], shape_id=sid)[0]
-    X += 1e-3 * rng.uniform(-1, 1, X.shape)
-    PI = rng.uniform(-1e3, 1e3, (B, N, 4))
-    LAM = rng.uniform(0.0, 1.0, (B, N, 6))
-    yref = np.repeat(straight_traj()[None, :N], B, 0)
-    yref_e = yref[:, N - 1, :4].copy()
-    return dict(x0=x0, x=X, u=U, pi=PI, lam=LAM, yref=yref, yref_e=yref_e)
+make_solver = lambda N, B, **kw: point_cases.make_solver(N, B, NAMES, np.arange(B) % 4, **kw)
+nlp_inputs = lambda s, sid, seed: point_cases.nlp_point(s, sid, seed, feasible=False)
 
 
 def nlp_reference(s, sid, d, lam, x0):
     B, N = s.B, s.N
-    xn, A, Bm = s.eval_rk4(d["x"][:, :N].reshape(-1, 4), d["u"].reshape(-1, 2), shape_id=np.repeat(sid, N))
-    return kkt_ref.nlp_residuals(d["x"], d["u"], d["pi"], lam, d["yref"], d["yref_e"], xn.reshape(B, N, 4),
+    xn, A, Bm = s.eval_rk4(d["X"][:, :N].reshape(-1, 4), d["U"].reshape(-1, 2), shape_id=np.repeat(sid, N))
+    return kkt_ref.nlp_residuals(d["X"], d["U"], d["PI"], lam, d["yref"], d["yref_e"], xn.reshape(B, N, 4),
                                  A.reshape(B, N, 4, 4), Bm.reshape(B, N, 4, 2), s.Ts, s._W, s._We, s._lh, s._uh,
                                  bool(s.opts.stage0_s_bound), x0=x0)
 
@@ -77,7 +46,7 @@ def eval_device(s, d, lam, x0, sid=None):
     from uclv_qs_pushing_matlab_amd._lib import KKT_PARTS, KktIO
     dev = torch.device("cuda", 0)
     t = lambda a: None if a is None else torch.as_tensor(np.ascontiguousarray(a), device=dev)
-    ins = {k: t(v) for k, v in (("x0", x0), ("X", d["x"]), ("U", d["u"]), ("PI", d["pi"]), ("LAM", lam),
+    ins = {k: t(v) for k, v in (("x0", x0), ("X", d["X"]), ("U", d["U"]), ("PI", d["PI"]), ("LAM", lam),
                                 ("yref", d["yref"]), ("yref_e", d["yref_e"]),
                                 ("shape_id", None if sid is None else np.asarray(sid, np.int32)))}
     outs = dict(res=torch.zeros((s.B, 4), dtype=torch.float64, device=dev),
@@ -149,9 +118,9 @@ def test_eval_kkt_against_numpy(N, B):
     try:
         d = nlp_inputs(s, sid, 3 + N)
         worst = {}
-        for mode, lam in (("given", d["lam"]), ("implied", None)):
+        for mode, lam in (("given", d["LAM"]), ("implied", None)):
             r = nlp_reference(s, sid, d, lam, d["x0"])
-            res, parts, sres = s.eval_kkt(d["x"], d["u"], d["pi"], "implied" if lam is None else lam, x0=d["x0"],
+            res, parts, sres = s.eval_kkt(d["X"], d["U"], d["PI"], "implied" if lam is None else lam, x0=d["x0"],
                                           yref=d["yref"], yref_e=d["yref_e"], parts=True, stages=True)
             ex = r["comp_extra"]
             tol_s, tol_p, tol_r = np.zeros_like(sres), np.zeros_like(parts), np.zeros_like(res)
@@ -170,9 +139,9 @@ def test_eval_kkt_against_numpy(N, B):
             assert same_bits(parts[:, :3].max(1), mx[:, 0]) and same_bits(parts[:, 3:5].max(1), mx[:, 1])
             assert same_bits(parts[:, 5:], mx[:, 2:])
             # x0 = X_0 adds nothing
-            a = s.eval_kkt(d["x"], d["u"], d["pi"], "implied" if lam is None else lam, x0=d["x"][:, 0],
+            a = s.eval_kkt(d["X"], d["U"], d["PI"], "implied" if lam is None else lam, x0=d["X"][:, 0],
                            yref=d["yref"], yref_e=d["yref_e"])
-            b = s.eval_kkt(d["x"], d["u"], d["pi"], "implied" if lam is None else lam, yref=d["yref"], yref_e=d["yref_e"])
+            b = s.eval_kkt(d["X"], d["U"], d["PI"], "implied" if lam is None else lam, yref=d["yref"], yref_e=d["yref_e"])
             assert same_bits(a, b)
             assert np.all(res[:, 1] >= b[:, 1])
             # the device entry on caller-owned buffers
@@ -188,14 +157,7 @@ def test_reproduces_the_merit_sqp_test():
     N, nb, K = 20, 64, 30
     s, sid = make_solver(N, nb, sqp_iters=K, nlp_solver_type="SQP")
     try:
-        x0 = config2_x0(nb, 21)
-        yref = np.repeat(straight_traj()[None, :N], nb, 0)
-        s.set("constr_x0", x0)
-        s.set("cost_y_ref", yref)
-        s.set("cost_y_ref_e", yref[:, N - 1, :4].copy())
-        s.set("init_x", np.repeat(x0[:, None], N + 1, 1))
-        s.set("init_u", np.zeros((nb, N, 2)))
-        s.solve()
+        point_cases.cold_solve(s, 21)
         conv = np.nonzero(s.get("status") == 0)[0]
         assert len(conv) >= 10, len(conv)
         want = s.get("residuals")
@@ -212,7 +174,7 @@ def test_reproduces_the_merit_sqp_test():
 def clean():
     s, sid = make_solver(20, 70)
     d = nlp_inputs(s, sid, 9)
-    out = s.eval_kkt(d["x"], d["u"], d["pi"], d["lam"], x0=d["x0"], yref=d["yref"], yref_e=d["yref_e"], parts=True, stages=True)
+    out = s.eval_kkt(d["X"], d["U"], d["PI"], d["LAM"], x0=d["x0"], yref=d["yref"], yref_e=d["yref_e"], parts=True, stages=True)
     yield s, d, out
     s.close()
 
@@ -225,10 +187,11 @@ BAD = (0, 33, 69)
 def test_bad_lanes(clean, where, value):
     s, d, want = clean
     e = {k: v.copy() for k, v in d.items()}
+    where = dict(x="X", u="U", pi="PI", lam="LAM").get(where, where)     # the point's keys (point_cases.nlp_point)
     # the first word of lane 0, one in the middle of lane 33, the last word of lane 69
     for lane, pos in zip(BAD, (0, e[where][0].size // 2, e[where][0].size - 1)):
         e[where][lane].reshape(-1)[pos] = value
-    got = s.eval_kkt(e["x"], e["u"], e["pi"], e["lam"], x0=e["x0"], yref=e["yref"], yref_e=e["yref_e"], parts=True, stages=True)
+    got = s.eval_kkt(e["X"], e["U"], e["PI"], e["LAM"], x0=e["x0"], yref=e["yref"], yref_e=e["yref_e"], parts=True, stages=True)
     good = np.setdiff1d(np.arange(s.B), BAD)
     for g, w in zip(got, want):
         assert np.all(np.isnan(g[list(BAD)])), (where, g[list(BAD)])
@@ -299,18 +262,8 @@ def test_errors_and_lam():
     with pytest.raises(_lib.QspError, match=ERR_STATE):
         s.get("lam")
     # ... and after solve() its answers have an optimality measure: finite, res_eq the recomputed defect
-    x0 = config2_x0(B, 21)
-    yref = np.repeat(straight_traj()[None, :N], B, 0)
     sid = np.arange(B) % 4
-
-    def stage(s):
-        s.set("constr_x0", x0)
-        s.set("cost_y_ref", yref)
-        s.set("cost_y_ref_e", yref[:, N - 1, :4].copy())
-        s.set("init_x", np.repeat(x0[:, None], N + 1, 1))
-        s.set("init_u", np.zeros((B, N, 2)))
-    stage(s)
-    s.solve()
+    point_cases.cold_solve(s, 21)
     ok = s.get("status") == 0
     assert ok.sum() >= B // 2
     res = s.eval_kkt()
@@ -329,8 +282,7 @@ def test_errors_and_lam():
     s.set_shapes([make_shape(n) for n in NAMES], shape_id=sid)
     with pytest.raises(_lib.QspError, match=ERR_STATE):
         s.get("lam")
-    stage(s)
-    s.solve()
+    point_cases.cold_solve(s, 21)
     lam = s.get("lam")
     assert lam.shape == (B, N, 6) and np.all(lam >= 0.0) and lam.max() > 0.0
     assert s.get("lam", stage=3).shape == (B, 6)

@@ -13,9 +13,12 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import host_program
 import manufactured_qp as mq
+import point_cases
 import sens_ref
 from conftest import config2_x0, straight_traj
+from point_cases import same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -24,48 +27,14 @@ ERR_ARG, ERR_STATE = r"\(-1\)", r"\(-3\)"
 ALL = ("K0", "K", "dU", "P0", "flag")
 
 
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64) if a.dtype == np.float64 else a
-
-
-def same_bits(a, b):
-    return np.array_equal(bits(a), bits(b))
-
-
 def assert_same(got, want, lanes=slice(None), what=""):
     for k in want:
         if k in got:
             assert same_bits(got[k][lanes], want[k][lanes]), (what, k, np.abs(got[k][lanes] - want[k][lanes]).max())
 
 
-def make_solver(N, B, **kw):
-    from uclv_qs_pushing_matlab_amd.objects import make_shape
-    from uclv_qs_pushing_matlab_amd.solver import OcpSolver
-    s = OcpSolver(N=N, batch=B, **kw)
-    sid = (np.arange(B) * 7 // 3) % 2          # two shapes, mixed per lane
-    s.set_shapes([make_shape(n) for n in NAMES], shape_id=sid)
-    return s, sid
-
-
-def nlp_point(s, sid, seed):
-    """A random feasible point: U uniform inside the input bounds, X an Euler rollout from the config-2 x0 law with
-    s clipped into its bounds; PI in +-1, LAM zero on about two thirds of the sides and in [0, 1] on the rest,
-    and a few components moved onto or within 1e-12 of a bound (slack below t_floor); the straight reference."""
-    B, N = s.B, s.N
-    rng = np.random.default_rng(seed)
-    U = rng.uniform(s._lh[1:], s._uh[1:], (B, N, 2))
-    U[:, :, 1][rng.uniform(0, 1, (B, N)) < 0.05] = s._uh[2]           # on u_t's upper bound
-    U[:, :, 0][rng.uniform(0, 1, (B, N)) < 0.05] = s._lh[1] + 1e-12   # within 1e-12 of u_n's lower bound
-    X = np.zeros((B, N + 1, 4))
-    X[:, 0] = config2_x0(B, seed)
-    for k in range(N):
-        X[:, k + 1] = X[:, k] + s.Ts * s.eval_dynamics(X[:, k], U[:, k], shape_id=sid)[0]
-        X[:, k + 1, 3] = np.clip(X[:, k + 1, 3], s._lh[0], s._uh[0])
-    PI = rng.uniform(-1.0, 1.0, (B, N, 4))
-    LAM = np.where(rng.uniform(0, 1, (B, N, 6)) < 0.35, rng.uniform(0.0, 1.0, (B, N, 6)), 0.0)
-    yref = np.repeat(straight_traj()[None, :N], B, 0)
-    return dict(X=X, U=U, PI=PI, LAM=LAM, yref=yref, yref_e=yref[:, N - 1, :4].copy())
+make_solver = lambda N, B, **kw: point_cases.make_solver(N, B, NAMES, (np.arange(B) * 7 // 3) % 2, **kw)   # mixed per lane
+nlp_point = lambda s, sid, seed: point_cases.nlp_point(s, sid, seed, feasible=True)
 
 
 def rk4_data(s, sid, d):
@@ -77,7 +46,7 @@ def rk4_data(s, sid, d):
 # ------------------------------------------------------------------ test 1
 @pytest.fixture(scope="module")
 def host_exe(tmp_path_factory):
-    return sens_ref.build_host_program(tmp_path_factory.mktemp("sens") / "sens_main", sanitize=False)
+    return host_program.build("sens_main", tmp_path_factory.mktemp("sens") / "sens_main", sanitize=False)
 
 
 @pytest.mark.parametrize("N", [3, 20])
@@ -265,14 +234,7 @@ def test_get_sens_is_eval_sens_of_the_iterate(mode):
     try:
         with pytest.raises(_lib.QspError, match=ERR_STATE):
             s.get_sens()
-        x0 = config2_x0(B, 21)
-        yref = np.repeat(straight_traj()[None, :N], B, 0)
-        s.set("constr_x0", x0)
-        s.set("cost_y_ref", yref)
-        s.set("cost_y_ref_e", yref[:, N - 1, :4].copy())
-        s.set("init_x", np.repeat(x0[:, None], N + 1, 1))
-        s.set("init_u", np.zeros((B, N, 2)))
-        s.solve()
+        point_cases.cold_solve(s, 21)
         got = s.get_sens(want=ALL)
         lam = s.get("lam") if mode == "SQP" else None
         want = s.eval_sens(s.get("x"), s.get("u"), PI=s.get("pi"), LAM=lam, want=ALL)

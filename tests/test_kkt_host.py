@@ -4,28 +4,21 @@ solutions (tests/manufactured_qp.py).  Built with the address and undefined-beha
 tests/test_sim_noise_host.py builds its program.  Nothing is loaded into Python.
 
 Every comparison uses the derived bound of tests/kkt_ref.py, |got - ref| <= 64 eps * term scale."""
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
+import host_program
 import kkt_ref
 import manufactured_qp as mq
-from conftest import ROOT
 
 ORDER = ("A", "B", "b", "H", "g", "lo", "hi", "dx0")
 
 
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
-    out = tmp_path_factory.mktemp("kkt") / "kkt_main"
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-ffp-contract=off",
-                           "-I", os.path.join(ROOT, "uclv_qs_pushing_matlab_amd", "csrc"),
-                           "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                           "-static-libasan", "-static-libubsan", "-g", "-w",
-                           os.path.join(ROOT, "tests", "stubs", "kkt_main.cpp"), "-o", str(out)])
-    return str(out)
+    return host_program.build("kkt_main", tmp_path_factory.mktemp("kkt") / "kkt_main")
 
 
 def run(exe, path, q, point, s0):

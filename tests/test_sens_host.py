@@ -31,6 +31,7 @@ inputs pattern holds it to rounding.
 import numpy as np
 import pytest
 
+import host_program
 import manufactured_qp as mq
 import sens_ref
 
@@ -41,7 +42,7 @@ NB, SEED = 7, 1
 
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
-    return sens_ref.build_host_program(tmp_path_factory.mktemp("sens") / "sens_main", sanitize=True)
+    return host_program.build("sens_main", tmp_path_factory.mktemp("sens") / "sens_main")
 
 
 @pytest.mark.parametrize("N", [3, 20])

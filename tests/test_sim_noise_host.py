@@ -3,22 +3,17 @@ header's functions are __host__ __device__): its Philox4x32-10 gives the publish
 equals the numpy restatement within the bound the GPU test uses, 1e-13 sigma scale -- the argument rounding of
 cos(2 pi u) is <= 7e-16, the libm errors a few ulp, times |r| <= 6.76: about 1e-14.  Built with the address and
 undefined-behaviour sanitizers, as tests/test_devbuf.py builds its program.  Nothing is loaded into Python."""
-import os
 import subprocess
 
 import numpy as np
 
-from conftest import ROOT
+import host_program
 from sim_noise_ref import sim_noise
 
 
 def test_header_on_the_host(tmp_path):
     exe = tmp_path / "noise_main"
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
-                           "-I", os.path.join(ROOT, "uclv_qs_pushing_matlab_amd", "csrc"),
-                           "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                           "-static-libasan", "-static-libubsan", "-g", "-w",
-                           os.path.join(ROOT, "tests", "stubs", "noise_main.cpp"), "-o", str(exe)])
+    host_program.build("noise_main", exe, flags=host_program.FP + host_program.HIP_HOST)
     seed, stream, step0, lane0, T, B = 0x9E3779B97F4A7C15, 3, 2 ** 32 - 2, 2 ** 31 + 5, 5, 7
     r = subprocess.run([str(exe)] + [str(v) for v in (seed, stream, step0, lane0, T, B)], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr

@@ -304,6 +304,30 @@ struct Staging {
     }
 };
 
+// The inputs of an NLP point from an evaluator's io block (qsp_kkt_io, qsp_sens_io: x0, X, U, PI, LAM, yref,
+// shape_id) into the kernels' PointIn: host arrays go through the staging pool (st.err says how that went),
+// device arrays are used as they are; shape_id and the references fall back to the handle's.  refs = false:
+// the call reads no references.
+template <class IO>
+static PointIn point_in(qsp_solver* s, Staging& st, bool host, const IO& io, const double* yref_e, bool refs) {
+    const Dims& dim = s->dim;
+    const auto in = [&](const double* v, size_t n) -> const double* { return host ? st.in(v, n) : v; };
+    PointIn pt;
+    pt.shapes = s->shapes.data();
+    pt.n_shapes = s->n_shapes;
+    pt.shape_id = io.shape_id ? io.shape_id : s->shape_id.data();
+    pt.x0 = in(io.x0, dim.x0());
+    pt.X = in(io.X, dim.X());
+    pt.U = in(io.U, dim.U());
+    pt.PI = in(io.PI, dim.PI());
+    pt.LAM = in(io.LAM, dim.lam());
+    pt.yref = refs ? in(io.yref, dim.yref()) : nullptr;
+    pt.yref_e = refs ? in(yref_e, dim.yref_e()) : nullptr;
+    if (refs && !pt.yref) pt.yref = s->yref.data();
+    if (refs && !pt.yref_e) pt.yref_e = s->yref_e.data();
+    return pt;
+}
+
 static int check_ids(qsp_solver* s, int32_t n, const int32_t* ids) {
     if (s->n_shapes < 1) return fail(QSP_ERR_STATE, "no shapes set");
     for (int i = 0; i < n; ++i)
@@ -1350,46 +1374,38 @@ int qsp_qp_solve(qsp_solver* s, int32_t nb, const double* A, const double* B, co
     const int N = s->o.N;
     SolveParams p = s->p;
     qp_level_params(p, H, lo, hi);   // bounds in step space lo = lh - v, hi = uh - v with lh = 0, uh = width, v = -lo
-    for (int l = 0; l < nb; ++l) {
-        for (int k = 0; k < N; ++k) {
-            for (int i = 0; i < 6; ++i)
-                if (H[(size_t)l * (6 * N + 4) + 6 * k + i] != p.W[i])
-                    return fail(QSP_ERR_ARG, "qsp_qp_solve: stage Hessian must be equal on every stage");
-            for (int j = 0; j < 3; ++j) {
-                const double w = hi[((size_t)l * N + k) * 3 + j] - lo[((size_t)l * N + k) * 3 + j];
-                if (std::fabs(w - p.uh[j]) > 1e-12 * (1.0 + std::fabs(w)))
-                    return fail(QSP_ERR_ARG, "qsp_qp_solve: bound widths must be equal on every stage");
-            }
-            const double* Ak = A + ((size_t)l * N + k) * 16;
-            const double st[10] = {Ak[0] - 1.0, Ak[1], Ak[4], Ak[5] - 1.0, Ak[8], Ak[9], Ak[10] - 1.0, Ak[12], Ak[13], Ak[14]};
-            for (double v : st)
-                if (v != 0.0) return fail(QSP_ERR_ARG, "qsp_qp_solve: A lacks the pusher-slider structure");
-        }
-        for (int i = 0; i < 4; ++i)
-            if (H[(size_t)l * (6 * N + 4) + 6 * N + i] != p.We[i])
-                return fail(QSP_ERR_ARG, "qsp_qp_solve: terminal Hessian must be equal on every lane");
-    }
-    // pack the workspace on the host: stage data SoA, v = -lo through X/U, x0 - X_0 = dx0
     const Dims qd{(size_t)nb, (size_t)N};   // the QPs' own batch
     const size_t tot = qd.stages();
     std::vector<double> lin(qd.lin(), 0.0), X(qd.X()), U(qd.U()), x0(qd.x0());
-    for (int l = 0; l < nb; ++l) {
+    for (int l = 0; l < nb; ++l) {   // each lane checked, then packed
+        const QpLaneData q(A, B, b, H, g, lo, hi, N, (size_t)l);
+        for (int k = 0; k < N; ++k) {
+            for (int i = 0; i < 6; ++i)
+                if (q.Hk(k)[i] != p.W[i]) return fail(QSP_ERR_ARG, "qsp_qp_solve: stage Hessian must be equal on every stage");
+            for (int j = 0; j < 3; ++j) {
+                const double w = q.hik(k)[j] - q.lok(k)[j];
+                if (std::fabs(w - p.uh[j]) > 1e-12 * (1.0 + std::fabs(w)))
+                    return fail(QSP_ERR_ARG, "qsp_qp_solve: bound widths must be equal on every stage");
+            }
+            if (!QpLaneData::has_structure(q.Ak(k))) return fail(QSP_ERR_ARG, "qsp_qp_solve: A lacks the pusher-slider structure");
+        }
+        for (int i = 0; i < 4; ++i)
+            if (q.Hk(N)[i] != p.We[i]) return fail(QSP_ERR_ARG, "qsp_qp_solve: terminal Hessian must be equal on every lane");
+        // pack the workspace on the host: stage data SoA, v = -lo through X/U, x0 - X_0 = dx0
         for (int k = 0; k <= N; ++k) {
             const size_t gi = (size_t)l * (N + 1) + k;
             if (k < N) {
-                const double* Ak = A + ((size_t)l * N + k) * 16;
-                const double av[6] = {Ak[2], Ak[3], Ak[6], Ak[7], Ak[11], Ak[15]};
+                double av[6];
+                QpLaneData::free_entries(q.Ak(k), av);
                 for (int f = 0; f < 6; ++f) lin[(L_A + f) * tot + gi] = av[f];
-                for (int f = 0; f < 8; ++f) lin[(L_B + f) * tot + gi] = B[((size_t)l * N + k) * 8 + f];
-                for (int f = 0; f < 4; ++f) lin[(L_BB + f) * tot + gi] = b[((size_t)l * N + k) * 4 + f];
-                for (int f = 0; f < 6; ++f) lin[(L_G + f) * tot + gi] = g[(size_t)l * (6 * N + 4) + 6 * k + f];
-            } else {
-                for (int f = 0; f < 4; ++f) lin[(L_G + f) * tot + gi] = g[(size_t)l * (6 * N + 4) + 6 * N + f];
+                for (int f = 0; f < 8; ++f) lin[(L_B + f) * tot + gi] = q.Bk(k)[f];
+                for (int f = 0; f < 4; ++f) lin[(L_BB + f) * tot + gi] = q.bk(k)[f];
             }
+            for (int f = 0; f < (k < N ? 6 : 4); ++f) lin[(L_G + f) * tot + gi] = q.gk(k)[f];
         }
         // dx0 = wx0 - X_0 with X_0 = (0, 0, 0, -lo_s(0))  ->  wx0 = dx0 + X_0
-        qp_level_iterate(N, lo + (size_t)l * N * 3, dx0 + (size_t)l * 4, X.data() + (size_t)l * (N + 1) * 4,
-                         U.data() + (size_t)l * N * 2, x0.data() + (size_t)l * 4);
+        qp_level_iterate(N, q.lo, dx0 + (size_t)l * 4, X.data() + (size_t)l * (N + 1) * 4, U.data() + (size_t)l * N * 2,
+                         x0.data() + (size_t)l * 4);
     }
     HIPCHK(hipSetDevice(s->o.device));
     Staging st(s);
@@ -1413,17 +1429,22 @@ int qsp_qp_solve(qsp_solver* s, int32_t nb, const double* A, const double* B, co
     if (st.finish()) return st.err;
     if (qp_status) {
         for (int l = 0; l < nb; ++l)
-            qp_status[l] = qp_level_status(p, dx + (size_t)l * (N + 1) * 4, du + (size_t)l * N * 2, lo + (size_t)l * N * 3,
-                                           hi + (size_t)l * N * 3, dx0 + (size_t)l * 4, qst[l]);
+            qp_status[l] = qp_level_status(p, dx + (size_t)l * (N + 1) * 4, du + (size_t)l * N * 2,
+                                           lo + (size_t)l * N * QpLaneData::NBOUND, hi + (size_t)l * N * QpLaneData::NBOUND,
+                                           dx0 + (size_t)l * 4, qst[l]);
     }
     return QSP_OK;
 }
 
-// ------------------------------------- KKT residuals recomputed from given numbers
-static const char* missing(bool host);
-static hipStream_t stream_of(qsp_solver* s, bool host, void* stream);
+// Each host entry and its _device twin run one function: the checks, io onto the kernel's argument block,
+// the launch.  host: io holds host arrays, which go through the staging pool and are copied back before
+// the return, on the handle's stream; else device arrays, used as they are, asynchronous on `stream`.
+static const char* missing(bool host) { return host ? ": null argument" : ": missing device pointer"; }
+static hipStream_t stream_of(qsp_solver* s, bool host, void* stream) {
+    return (host || !stream) ? s->stream : (hipStream_t)stream;
+}
 
-// host entry and _device twin, as rollout_cost_run
+// ------------------------------------- KKT residuals recomputed from given numbers
 static int eval_kkt_run(qsp_solver* s, const char* who, bool host, const qsp_kkt_io* io, void* stream) {
     const std::string w(who);
     if (!s || !io || !io->X || !io->U || !io->PI || !io->res) return fail(QSP_ERR_ARG, w + missing(host));
@@ -1431,39 +1452,17 @@ static int eval_kkt_run(qsp_solver* s, const char* who, bool host, const qsp_kkt
     if ((!io->yref || !io->yref_e) && !s->have_yref)
         return fail(QSP_ERR_STATE, w + ": no references given and none staged on the handle");
     HIPCHK(hipSetDevice(s->o.device));
-    qsp_kkt_io d = *io;
     Staging st(s);
-    if (host) {
-        const Dims& dim = s->dim;
-        d.x0 = st.in(io->x0, dim.x0());
-        d.X = st.in(io->X, dim.X());
-        d.U = st.in(io->U, dim.U());
-        d.PI = st.in(io->PI, dim.PI());
-        d.LAM = st.in(io->LAM, dim.lam());
-        d.yref = st.in(io->yref, dim.yref());
-        d.yref_e = st.in(io->yref_e, dim.yref_e());
-        d.res = st.out(io->res, dim.res());
-        d.parts = st.out(io->parts, dim.kkt_parts());
-        d.stage_res = st.out(io->stage_res, dim.kkt_stage_res());
-        if (st.err) return st.err;
-    }
+    const Dims& dim = s->dim;
     KktNlpArgs a;
     std::memset(&a, 0, sizeof a);
     a.p = s->p;
     a.B = s->o.batch;
-    a.shapes = s->shapes.data();
-    a.n_shapes = s->n_shapes;
-    a.shape_id = d.shape_id ? d.shape_id : s->shape_id.data();
-    a.x0 = d.x0;
-    a.X = d.X;
-    a.U = d.U;
-    a.PI = d.PI;
-    a.LAM = d.LAM;
-    a.yref = d.yref ? d.yref : s->yref.data();
-    a.yref_e = d.yref_e ? d.yref_e : s->yref_e.data();
-    a.res = d.res;
-    a.parts = d.parts;
-    a.stage_res = d.stage_res;
+    a.pt = point_in(s, st, host, *io, io->yref_e, true);
+    a.res = host ? st.out(io->res, dim.res()) : io->res;
+    a.parts = host ? st.out(io->parts, dim.kkt_parts()) : io->parts;
+    a.stage_res = host ? st.out(io->stage_res, dim.kkt_stage_res()) : io->stage_res;
+    if (st.err) return st.err;
     HIPCHK(launch_kkt_nlp(a, stream_of(s, host, stream)));
     return host ? st.finish() : QSP_OK;
 }
@@ -1514,11 +1513,11 @@ int qsp_qp_residuals(qsp_solver* s, int32_t nb, const double* A, const double* B
     a.g = st.in(g, qd.qp_Hg());
     a.lo = st.in(lo, qd.qp_bound());
     a.hi = st.in(hi, qd.qp_bound());
-    a.dx0 = st.in(dx0, qd.x0());
-    a.dx = st.in(dx, qd.X());
-    a.du = st.in(du, qd.U());
-    a.pi = st.in(pi, qd.PI());
-    a.lam = st.in(lam, qd.lam());
+    a.pt.x0 = st.in(dx0, qd.x0());
+    a.pt.X = st.in(dx, qd.X());
+    a.pt.U = st.in(du, qd.U());
+    a.pt.PI = st.in(pi, qd.PI());
+    a.pt.LAM = st.in(lam, qd.lam());
     a.res = st.out(res, qd.qp_res());
     if (st.err) return st.err;
     HIPCHK(launch_kkt_qp(a, s->stream));
@@ -1549,13 +1548,20 @@ static int sens_opts(qsp_solver* s, const qsp_sens_opts* opts, const std::string
     return QSP_OK;
 }
 
-// the gains' workspace of a call of nb lanes and horizon N that asks for dU
-static hipError_t sens_gain_buffer(qsp_solver* s, const double* dU, size_t nb, size_t N, double** wK) {
+// the gains' workspace of a call of dims d that asks for dU
+static hipError_t sens_gain_buffer(qsp_solver* s, const double* dU, const Dims& d, double** wK) {
     *wK = nullptr;
     if (!dU) return hipSuccess;
-    const hipError_t e = s->wsensK.ensure((size_t)SENS_NK * N * nb);
+    const hipError_t e = s->wsensK.ensure(d.sens_wK());
     *wK = s->wsensK.data();
     return e;
+}
+
+// the outputs of a call of dims d: host arrays through the staging pool, device arrays as they are
+static SensOut sens_out(Staging& st, bool host, const Dims& d, double* K0, double* K, double* dU, double* P0, int32_t* flag) {
+    if (!host) return {K0, K, dU, P0, flag};
+    return {st.out(K0, d.sens_K0()), st.out(K, d.sens_gains()), st.out(dU, d.sens_gains()), st.out(P0, d.sens_P0()),
+            st.out(flag, d.lane())};
 }
 
 // host entry and _device twin, as eval_kkt_run
@@ -1572,39 +1578,16 @@ static int eval_sens_run(qsp_solver* s, const char* who, bool host, const qsp_se
     if (implied && !io->yref && !s->have_yref)
         return fail(QSP_ERR_STATE, w + ": implied multipliers need references, and none are staged on the handle");
     HIPCHK(hipSetDevice(s->o.device));
-    qsp_sens_io d = *io;
     Staging st(s);
     const Dims& dim = s->dim;
-    const size_t gains = dim.U() * 4;   // B x N x 2 x 4
-    if (host) {
-        d.x0 = st.in(io->x0, dim.x0());
-        d.X = st.in(io->X, dim.X());
-        d.U = st.in(io->U, dim.U());
-        d.PI = st.in(io->PI, dim.PI());
-        d.LAM = st.in(io->LAM, dim.lam());
-        d.yref = st.in(io->yref, dim.yref());
-        d.K0 = st.out(io->K0, dim.lane() * 8);
-        d.K = st.out(io->K, gains);
-        d.dU = st.out(io->dU, gains);
-        d.P0 = st.out(io->P0, dim.lane() * 10);
-        d.flag = st.out(io->flag, dim.lane());
-        if (st.err) return st.err;
-    }
-    HIPCHK(s->wsens.ensure((size_t)SF_COUNT * dim.N * dim.B));
-    HIPCHK(sens_gain_buffer(s, d.dU, dim.B, dim.N, &a.wK));
+    a.pt = point_in(s, st, host, *io, nullptr, implied);
+    a.out = sens_out(st, host, dim, io->K0, io->K, io->dU, io->P0, io->flag);
+    if (st.err) return st.err;
+    HIPCHK(s->wsens.ensure(dim.sens_ws()));
+    HIPCHK(sens_gain_buffer(s, a.out.dU, dim, &a.wK));
     a.p = s->p;
     a.B = s->o.batch;
-    a.shapes = s->shapes.data();
-    a.n_shapes = s->n_shapes;
-    a.shape_id = d.shape_id ? d.shape_id : s->shape_id.data();
-    a.x0 = d.x0;
-    a.X = d.X;
-    a.U = d.U;
-    a.PI = d.PI;
-    a.LAM = d.LAM;
-    a.yref = implied ? (d.yref ? d.yref : s->yref.data()) : nullptr;
     a.ws = s->wsens.data();
-    a.out = {d.K0, d.K, d.dU, d.P0, d.flag};
     HIPCHK(launch_sens_nlp(a, stream_of(s, host, stream)));
     return host ? st.finish() : QSP_OK;
 }
@@ -1650,15 +1633,11 @@ int qsp_get_sens(qsp_solver* s, const qsp_sens_opts* opts, double* K0, double* K
 int qsp_qp_sens(qsp_solver* s, int32_t nb, int32_t N, const double* A, const double* B, const double* H, double* K0,
                 double* K, double* dU, double* P0, int32_t* flag) {
     if (!s || nb < 1 || N < 1 || !A || !B || !H || !K0) return fail(QSP_ERR_ARG, "qsp_qp_sens: bad argument");
-    for (size_t q = 0; q < (size_t)nb * N; ++q) {
-        const double* Ak = A + q * 16;
-        const double st[10] = {Ak[0] - 1.0, Ak[1], Ak[4], Ak[5] - 1.0, Ak[8], Ak[9], Ak[10] - 1.0, Ak[12], Ak[13], Ak[14]};
-        for (double v : st)
-            if (v != 0.0) return fail(QSP_ERR_ARG, "qsp_qp_sens: A lacks the pusher-slider structure");
-    }
+    for (size_t q = 0; q < (size_t)nb * N; ++q)
+        if (!QpLaneData::has_structure(A + q * QpLaneData::NA))
+            return fail(QSP_ERR_ARG, "qsp_qp_sens: A lacks the pusher-slider structure");
     HIPCHK(hipSetDevice(s->o.device));
     const Dims qd{(size_t)nb, (size_t)N};   // the QPs' own batch
-    const size_t gains = qd.U() * 4;
     Staging st(s);
     SensQpArgs a;
     std::memset(&a, 0, sizeof a);
@@ -1667,13 +1646,9 @@ int qsp_qp_sens(qsp_solver* s, int32_t nb, int32_t N, const double* A, const dou
     a.A = st.in(A, qd.qp_A());
     a.B = st.in(B, qd.qp_B());
     a.H = st.in(H, qd.qp_Hg());
-    a.out.K0 = st.out(K0, qd.lane() * 8);
-    a.out.K = st.out(K, gains);
-    a.out.dU = st.out(dU, gains);
-    a.out.P0 = st.out(P0, qd.lane() * 10);
-    a.out.flag = st.out(flag, qd.lane());
+    a.out = sens_out(st, true, qd, K0, K, dU, P0, flag);
     if (st.err) return st.err;
-    HIPCHK(sens_gain_buffer(s, a.out.dU, qd.B, qd.N, &a.wK));
+    HIPCHK(sens_gain_buffer(s, a.out.dU, qd, &a.wK));
     HIPCHK(launch_sens_qp(a, s->stream));
     return st.finish();
 }
@@ -1715,14 +1690,7 @@ static int rollout_args(qsp_solver* s, const qsp_rollout_opts* o, const char* wh
     return QSP_OK;
 }
 
-// Each host entry and its _device twin run one function: the checks, io onto the kernel's argument block,
-// the launch.  host: io holds host arrays, which go through the staging pool and are copied back before
-// the return, on the handle's stream; else device arrays, used as they are, asynchronous on `stream`.
-static const char* missing(bool host) { return host ? ": null argument" : ": missing device pointer"; }
-static hipStream_t stream_of(qsp_solver* s, bool host, void* stream) {
-    return (host || !stream) ? s->stream : (hipStream_t)stream;
-}
-
+// host entry and _device twin, as eval_kkt_run
 static int rollout_cost_run(qsp_solver* s, const qsp_rollout_opts* opts, const char* who, bool host, int32_t M,
                             const qsp_rollout_io* io, void* stream) {
     RolloutArgs a;

@@ -28,10 +28,15 @@ struct Dims {
     size_t kkt_parts() const { return B * KKT_NPARTS; }
     size_t kkt_stage_res() const { return B * (N + 1) * 4; }
     size_t qp_res() const { return B * KKT_QP_NRES; }
-    size_t qp_A() const { return B * N * 16; }         // qsp_qp_residuals' QP data
-    size_t qp_B() const { return B * N * 8; }
-    size_t qp_Hg() const { return B * (6 * N + 4); }
-    size_t qp_bound() const { return B * N * 3; }
+    size_t qp_A() const { return B * N * QpLaneData::NA; }   // caller-given QP data (qsp_point.hpp)
+    size_t qp_B() const { return B * N * QpLaneData::NB; }
+    size_t qp_Hg() const { return B * QpLaneData::hg(N); }
+    size_t qp_bound() const { return B * N * QpLaneData::NBOUND; }
+    size_t sens_K0() const { return B * 8; }           // the sensitivities' outputs: K0 2 x 4 per lane,
+    size_t sens_gains() const { return B * N * 8; }    // K and dU 2 x 4 per stage,
+    size_t sens_P0() const { return B * 10; }          // P0's upper triangle;
+    size_t sens_ws() const { return SF_COUNT * N * B; }   // and workspaces (SensField, SENS_NK)
+    size_t sens_wK() const { return SENS_NK * N * B; }
     size_t stages() const { return B * (N + 1); }      // stride of the SoA workspaces
     size_t lin() const { return L_COUNT * stages(); }
     size_t nlp() const { return W_COUNT * stages(); }

@@ -19,18 +19,21 @@
 // C++ compiler (no ROCm include path) compiles them into the CPU twin, oracle/qsp_twin.cpp (test
 // infrastructure may read a product header; the product never reads the twin).  Their qualifiers:
 //   QSP_FN         a device function;           QSP_HD_FN  one the host code of the library calls too;
-//   QSP_MEMBER_FN  a device member function -- on the host all three are plain inline functions.
+//   QSP_MEMBER_FN  a device member function;   QSP_HD_MEMBER_FN  one the host code calls too -- on the host all
+//                  four are plain inline functions.
 #pragma once
 #ifdef __HIPCC__
 #include <hip/hip_runtime.h>
 #define QSP_FN __device__ __forceinline__
 #define QSP_HD_FN __host__ __device__ __forceinline__
 #define QSP_MEMBER_FN __device__ __forceinline__
+#define QSP_HD_MEMBER_FN __host__ __device__ __forceinline__
 #else
 #include <math.h>
 #define QSP_FN static inline
 #define QSP_HD_FN static inline
 #define QSP_MEMBER_FN inline
+#define QSP_HD_MEMBER_FN inline
 #endif
 
 namespace qsp {

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "qsp_layout.h"
+#include "qsp_point.hpp"
 #include "qsp_types.h"
 
 #define QSP_FLAG_CONTROLLER 1u  // NMPC_controller.solve prologue: s pre-wrap, cold/warm start, clip, Euler rollout
@@ -269,20 +270,12 @@ struct OpenLoopArgs {
 };
 hipError_t launch_open_loop(const OpenLoopArgs& a, hipStream_t stream);
 
-// KKT residuals recomputed from given numbers (qsp_kkt.hip, qsp_kkt.hpp): one thread per (lane, stage).
+// KKT residuals recomputed from given numbers (qsp_kkt.hip, qsp_kkt.hpp): one thread per (lane, stage).  The
+// inputs of an NLP point are a PointIn (qsp_point.hpp), as the sensitivities' below.
 struct KktNlpArgs {
     SolveParams p;             // the handle's: N, Ts, tau, W, We, lh, uh, s0_bound are read
     int32_t B;
-    const ShapeDev* shapes;
-    int32_t n_shapes;
-    const int32_t* shape_id;   // B (nullptr: shape 0); clamped into [0, n_shapes)
-    const double* x0;          // B x 4 or nullptr (X's row 0 is the initial state)
-    const double* X;           // B x (N+1) x 4
-    const double* U;           // B x N x 2
-    const double* PI;          // B x N x 4
-    const double* LAM;         // B x N x 6 or nullptr (implied multipliers)
-    const double* yref;        // B x N x 6
-    const double* yref_e;      // B x 4
+    PointIn pt;                // x0 nullptr: X's row 0 is the initial state; LAM nullptr: implied multipliers
     double* res;               // B x 4      stat, eq, ineq, comp
     double* parts;             // B x 7 or nullptr (KktPart)
     double* stage_res;         // B x (N+1) x 4 or nullptr
@@ -298,11 +291,7 @@ struct KktQpArgs {
     const double* g;           // nb x (6N+4)
     const double* lo;          // nb x N x 3
     const double* hi;          // nb x N x 3
-    const double* dx0;         // nb x 4
-    const double* dx;          // nb x (N+1) x 4
-    const double* du;          // nb x N x 2
-    const double* pi;          // nb x N x 4
-    const double* lam;         // nb x N x 6
+    PointIn pt;                // the QP point dx0, dx, du, pi, lam as x0, X, U, PI, LAM (all given); the rest unset
     double* res;               // nb x 6     stat_u, stat_x, dyn, infeas, comp, dual (KktQpRes)
 };
 hipError_t launch_kkt_qp(const KktQpArgs& a, hipStream_t stream);
@@ -325,15 +314,8 @@ struct SensNlpArgs {
     int32_t B;
     int32_t s0_bound;          // 1: the s pair of stage 0 counts in the barrier
     double t_floor;            // > 0
-    const ShapeDev* shapes;
-    int32_t n_shapes;
-    const int32_t* shape_id;   // B (nullptr: shape 0); clamped into [0, n_shapes)
-    const double* x0;          // B x 4 or nullptr: stands for X's row 0
-    const double* X;           // B x (N+1) x 4
-    const double* U;           // B x N x 2
-    const double* PI;          // B x N x 4 or nullptr
-    const double* LAM;         // B x N x 6 or nullptr (PI: implied multipliers; neither: zero)
-    const double* yref;        // B x N x 6, read for the implied multipliers only
+    PointIn pt;                // x0 given: stands for X's row 0; LAM nullptr: the implied multipliers from PI and
+                               // yref, or zero where PI is nullptr too; yref_e is not read
     double* ws;                // SF_COUNT x N x B
     double* wK;                // SENS_NK x N x B, used with out.dU only
     SensOut out;

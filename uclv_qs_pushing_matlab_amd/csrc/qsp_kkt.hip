@@ -55,15 +55,8 @@ __global__ void __launch_bounds__(KKT_BLOCK) kkt_nlp_kernel(KktNlpArgs A, int lp
 #pragma unroll
     for (int q = 0; q <= KKT_NPARTS; ++q) row[q] = 0.0;
     if (live) {
-        const size_t i = (size_t)lane;
-        const int ku = k < N ? k : N - 1;   // rows read for k < N only: the pointers stay inside their arrays
-        const double* X = A.X + i * (size_t)L * 4;
-        const double* PI = A.PI + i * (size_t)N * 4;
-        const bool fin = kkt_nlp_stage(shape_clamped(A.shapes, A.n_shapes, A.shape_id, (int)lane), p, k, X + 4 * k,
-                                       A.U + (i * N + ku) * 2, X + 4 * (ku + 1),
-                                       k < N ? A.yref + (i * N + k) * 6 : A.yref_e + i * 4, PI + 4 * ku,
-                                       PI + 4 * (k >= 1 ? k - 1 : 0), A.LAM ? A.LAM + (i * N + ku) * 6 : nullptr,
-                                       A.x0 ? A.x0 + i * 4 : nullptr, row);
+        const bool fin = kkt_nlp_stage(shape_clamped(A.pt.shapes, A.pt.n_shapes, A.pt.shape_id, (int)lane), p, k,
+                                       PointRows(A.pt, N, (size_t)lane, k), row);
         row[KKT_NPARTS] = fin ? 0.0 : 1.0;
     }
     const int base = threadIdx.x - k;
@@ -102,14 +95,10 @@ __global__ void __launch_bounds__(KKT_BLOCK) kkt_qp_kernel(KktQpArgs A, int lpb)
 #pragma unroll
     for (int q = 0; q <= KKT_QP_NRES; ++q) row[q] = 0.0;
     if (live) {
-        const size_t i = (size_t)lane;
-        const int ku = k < N ? k : N - 1;
-        const size_t sk = i * N + ku, hk = i * (6 * (size_t)N + 4) + 6 * (size_t)k;
-        const double* dx = A.dx + i * (size_t)L * 4;
-        const double* pi = A.pi + i * (size_t)N * 4;
-        const bool fin = kkt_qp_stage(N, A.s0_bound, k, A.A + sk * 16, A.B + sk * 8, A.b + sk * 4, A.H + hk, A.g + hk,
-                                      A.lo + sk * 3, A.hi + sk * 3, A.dx0 + i * 4, dx + 4 * k, A.du + sk * 2,
-                                      dx + 4 * (ku + 1), pi + 4 * ku, pi + 4 * (k >= 1 ? k - 1 : 0), A.lam + sk * 6, row);
+        const QpLaneData d(A.A, A.B, A.b, A.H, A.g, A.lo, A.hi, N, (size_t)lane);
+        const PointRows r(A.pt, N, (size_t)lane, k);
+        const bool fin = kkt_qp_stage(N, A.s0_bound, k, d.Ak(k), d.Bk(k), d.bk(k), d.Hk(k), d.gk(k), d.lok(k), d.hik(k), r.x0, r.x,
+                                      r.u, r.x1, r.pi, r.pip, r.lam, row);
         row[KKT_QP_NRES] = fin ? 0.0 : 1.0;
     }
     const int base = threadIdx.x - k;

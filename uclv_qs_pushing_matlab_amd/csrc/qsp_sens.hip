@@ -32,15 +32,9 @@ __global__ void __launch_bounds__(SENS_LIN_BLOCK) sens_lin_kernel(SensNlpArgs A)
     if (gi >= B * (size_t)N) return;
     const int k = (int)(gi / B);
     const size_t i = gi - (size_t)k * B;
-    const double* X = A.X + i * (size_t)(N + 1) * 4;
-    const size_t sk = i * (size_t)N + k;
-    const double* PI = A.PI ? A.PI + i * (size_t)N * 4 : nullptr;
     double a[6], Bm[8], Hx[4], Hu[2];
-    const bool fin = sens_nlp_stage(shape_clamped(A.shapes, A.n_shapes, A.shape_id, (int)i), p, A.s0_bound, A.t_floor, k,
-                                    (k == 0 && A.x0) ? A.x0 + i * 4 : X + 4 * k, A.U + sk * 2,
-                                    A.yref ? A.yref + sk * 6 : nullptr, PI ? PI + 4 * k : nullptr,
-                                    PI ? PI + 4 * (k >= 1 ? k - 1 : 0) : nullptr, A.LAM ? A.LAM + sk * 6 : nullptr,
-                                    k == N - 1 ? X + 4 * N : nullptr, a, Bm, Hx, Hu);
+    const bool fin = sens_nlp_stage(shape_clamped(A.pt.shapes, A.pt.n_shapes, A.pt.shape_id, (int)i), p, A.s0_bound, A.t_floor,
+                                    k, PointRows(A.pt, N, i, k), a, Bm, Hx, Hu);
     if (!fin) Hx[0] = __builtin_nan("");
     double* w = A.ws + (size_t)k * SF_COUNT * B + i;
 #pragma unroll
@@ -79,24 +73,22 @@ struct SensSrcWs {   // sens_lin_kernel's workspace
     }
 };
 struct SensSrcQp {   // the caller's QP arrays
-    const double *A, *Bq, *H;   // the lane's
-    int N;
+    QpLaneData d;
     __device__ __forceinline__ void terminal(double He[4]) const {
 #pragma unroll
-        for (int q = 0; q < 4; ++q) He[q] = H[6 * (size_t)N + q];
+        for (int q = 0; q < 4; ++q) He[q] = d.Hk(d.N)[q];
     }
     __device__ __forceinline__ void dyn(int k, double a[6], double Bm[8]) const {
-        const double* Ak = A + (size_t)k * 16;
-        a[0] = Ak[2]; a[1] = Ak[3]; a[2] = Ak[6]; a[3] = Ak[7]; a[4] = Ak[11]; a[5] = Ak[15];
+        QpLaneData::free_entries(d.Ak(k), a);
 #pragma unroll
-        for (int q = 0; q < 8; ++q) Bm[q] = Bq[(size_t)k * 8 + q];
+        for (int q = 0; q < 8; ++q) Bm[q] = d.Bk(k)[q];
     }
     __device__ __forceinline__ void stage(int k, double a[6], double Bm[8], double Hx[4], double Hu[2]) const {
         dyn(k, a, Bm);
 #pragma unroll
-        for (int q = 0; q < 4; ++q) Hx[q] = H[6 * (size_t)k + q];
+        for (int q = 0; q < 4; ++q) Hx[q] = d.Hk(k)[q];
 #pragma unroll
-        for (int q = 0; q < 2; ++q) Hu[q] = H[6 * (size_t)k + 4 + q];
+        for (int q = 0; q < 2; ++q) Hu[q] = d.Hk(k)[4 + q];
     }
 };
 
@@ -163,12 +155,7 @@ __global__ void __launch_bounds__(SENS_WALK_BLOCK) sens_walk_kernel(SensNlpArgs 
 __global__ void __launch_bounds__(SENS_WALK_BLOCK) sens_walk_qp_kernel(SensQpArgs A) {
     const size_t i = (size_t)blockIdx.x * SENS_WALK_BLOCK + threadIdx.x;
     if (i >= (size_t)A.nb) return;
-    const size_t N = (size_t)A.N;
-    SensSrcQp src;
-    src.A = A.A + i * N * 16;
-    src.Bq = A.B + i * N * 8;
-    src.H = A.H + i * (6 * N + 4);
-    src.N = A.N;
+    const SensSrcQp src = {QpLaneData(A.A, A.B, nullptr, A.H, nullptr, nullptr, nullptr, A.N, i)};
     sens_walk(src, A.N, (size_t)A.nb, i, A.wK, A.out);
 }
 
@@ -176,7 +163,7 @@ static bool sens_out_ok(const SensOut& o, const double* wK) { return o.K0 && (!o
 
 hipError_t launch_sens_nlp(const SensNlpArgs& a, hipStream_t stream) {
     if (a.B < 1 || a.p.N < 1 || !a.ws || !sens_out_ok(a.out, a.wK) || !(a.t_floor > 0.0)) return hipErrorInvalidValue;
-    if (!a.LAM && a.PI && !a.yref) return hipErrorInvalidValue;
+    if (!a.pt.LAM && a.pt.PI && !a.pt.yref) return hipErrorInvalidValue;
     const size_t n = (size_t)a.B * (size_t)a.p.N;
     const dim3 lgrid((unsigned)((n + SENS_LIN_BLOCK - 1) / SENS_LIN_BLOCK)), lblock(SENS_LIN_BLOCK);
     hipLaunchKernelGGL(sens_lin_kernel, lgrid, lblock, 0, stream, a);

@@ -5,7 +5,7 @@
 // (tests/stubs/sens_main.cpp), as qsp_kkt.hpp.
 //
 // Definition: the BARRIER-SMOOTHED GAUSS-NEWTON SENSITIVITY of lane i at a point (X, U) with bound multipliers LAM.
-//   stage data   A_k, B_k from one RK4 step with sensitivities at (x_k, u_k), exactly as kkt_nlp_stage forms them;
+//   stage data   A_k, B_k from one RK4 step with sensitivities at (x_k, u_k): point_stage (qsp_point.hpp), as kkt_nlp_stage;
 //   Hessian      Hx = tau W[0..3], Hu = tau W[4..5] for k < N and We at N: the cost is linear least squares,
 //                so this is the exact Gauss-Newton Hessian;
 //   bounds       each of the six bound sides of h = [s; u_n; u_t] at stage k adds lam / max(slack, t_floor) to
@@ -23,23 +23,17 @@
 // derivatives of the dynamics enter), and parity against acados' own solution sensitivities is unpinned, as
 // everywhere: no reference fixture fixes them.
 //
-// The implied multipliers (LAM not given, PI given) are those of kkt_nlp_stage, written out once more
-// (sens_implied_lam): lam_lo = max(r, 0), lam_hi = max(-r, 0) from the component's stationarity r without
-// bound multipliers; the stage-0 s pair is 0.  tests/test_gpu_sens.py holds the two statements together.
+// The implied multipliers (LAM not given, PI given) are kkt_nlp_stage's: implied_lam (qsp_point.hpp).  The SQP
+// kernels keep a stage load of their own (qsp_solver.hip; the comment above qp_outcome there says why);
+// tests/test_gpu_sens.py::test_eval_sens_is_qp_sens_of_its_own_stage_data holds this header's to qsp_eval_rk4.
 //
 // Non-finite values: every function that reads or produces numbers returns a flag -- all of them finite --
 // and the caller turns a lane with one unset flag into NaN in every output.
 #pragma once
-#include "qsp_ipm.hpp"
+#include "qsp_point.hpp"
 #include "qsp_riccati.hpp"
 
 namespace qsp {
-
-QSP_FN bool sens_finite(const double* v, int n) {
-    bool f = true;
-    for (int q = 0; q < n; ++q) f = f && __builtin_isfinite(v[q]);
-    return f;
-}
 
 // The barrier diagonal of stage k: d[j] for v = (s, u_n, u_t), both sides of each summed (lower first).
 QSP_FN void sens_barrier(const double lh[3], const double uh[3], int k, int s0_bound, double t_floor, const double v[3],
@@ -52,59 +46,25 @@ QSP_FN void sens_barrier(const double lh[3], const double uh[3], int k, int s0_b
     }
 }
 
-// The implied multipliers of stage k < N (kkt_nlp_stage's, see above): y = yref_k, pk = pi_k, pp = pi_{k-1}
-// (read for k >= 1).
-QSP_FN void sens_implied_lam(const SolveParams& p, int k, const double x[4], const double u[2], const double y[6],
-                             const double a[6], const double Bm[8], const double pk[4], const double pp[4], double lam[6]) {
-    for (int q = 0; q < 6; ++q) lam[q] = 0.0;
-    for (int i = 0; i < 2; ++i) {
-        const double gu = p.tau * p.W[4 + i] * (u[i] - y[4 + i]);
-        const double r = gu + qfma(Bm[6 + i], pk[3], qfma(Bm[4 + i], pk[2], qfma(Bm[2 + i], pk[1], Bm[i] * pk[0])));
-        lam[2 * (1 + i)] = r > 0.0 ? r : 0.0;
-        lam[2 * (1 + i) + 1] = r < 0.0 ? -r : 0.0;
-    }
-    if (k >= 1) {
-        const double gs = p.tau * p.W[3] * (x[3] - y[3]);
-        const double r = gs - pp[3] + qfma(a[5], pk[3], qfma(a[4], pk[2], qfma(a[3], pk[1], a[1] * pk[0])));
-        lam[0] = r > 0.0 ? r : 0.0;
-        lam[1] = r < 0.0 ? -r : 0.0;
-    }
-}
-
 // Stage k < N of an NLP point: a (the six free entries of A_k), Bm, and the diagonal Hx, Hu with the barrier
-// in it.  xk: x_k; uk: u_k; LAMk: the stage's multipliers, or nullptr: the implied ones from PIk, PIp
-// (= pi_{k-1}, read for k >= 1) and yr = yref_k, or zero where PIk is nullptr too.  xN: x_N at k = N - 1, else
-// nullptr -- nothing is computed from it (the terminal Hessian is We), it only counts in the flag, so that
-// every row of X does.  Returns the finite flag.
-QSP_FN bool sens_nlp_stage(const ShapeDev& sh, const SolveParams& p, int s0_bound, double t_floor, int k, const double* xk,
-                           const double* uk, const double* yr, const double* PIk, const double* PIp, const double* LAMk,
-                           const double* xN, double a[6], double Bm[8], double Hx[4], double Hu[2]) {
-    double x[4], u[2], lam[6] = {0, 0, 0, 0, 0, 0};
-    for (int q = 0; q < 4; ++q) x[q] = xk[q];
-    for (int q = 0; q < 2; ++q) u[q] = uk[q];
-    bool fin = sens_finite(x, 4) && sens_finite(u, 2);
-    if (xN) {
-        double z[4];
-        for (int q = 0; q < 4; ++q) z[q] = xN[q];
-        fin = fin && sens_finite(z, 4);
-    }
-    Lin Ln;
-    rk4<true>(sh, p.Ts, x, u, Ln);
-    fin = fin && sens_finite(Ln.xn, 4) && sens_finite(Ln.a, 6) && sens_finite(Ln.B, 8);
-    for (int q = 0; q < 6; ++q) a[q] = Ln.a[q];
-    for (int q = 0; q < 8; ++q) Bm[q] = Ln.B[q];
-    if (LAMk) {
-        for (int q = 0; q < 6; ++q) lam[q] = LAMk[q];
-        fin = fin && sens_finite(lam, 6);
-    } else if (PIk) {
+// in it.  r: the point's rows at (lane, k), x0 standing for X's row 0 where given; r.lam: the stage's
+// multipliers, or nullptr: the implied ones from r.pi, r.pip (read for k >= 1) and r.yr, or zero where r.pi is
+// nullptr too.  At k = N - 1 nothing is computed from x_N (the terminal Hessian is We), it only counts in the
+// flag, so that every row of X does.  Returns the finite flag.
+QSP_FN bool sens_nlp_stage(const ShapeDev& sh, const SolveParams& p, int s0_bound, double t_floor, int k, const PointRows& r,
+                           double a[6], double Bm[8], double Hx[4], double Hu[2]) {
+    double x[4], u[2], xn[4], lam[6] = {0, 0, 0, 0, 0, 0};
+    bool fin = point_stage(sh, p.Ts, r.x_or_x0(k), r.u, x, u, a, Bm, xn);
+    double z[4];
+    if (k == p.N - 1) fin &= load(z, r.x1, 4);
+    if (r.lam) {
+        fin &= load(lam, r.lam, 6);
+    } else if (r.pi) {
         double y[6], pk[4], pp[4] = {0, 0, 0, 0};
-        for (int q = 0; q < 6; ++q) y[q] = yr[q];
-        for (int q = 0; q < 4; ++q) pk[q] = PIk[q];
-        if (k >= 1) {
-            for (int q = 0; q < 4; ++q) pp[q] = PIp[q];
-        }
-        fin = fin && sens_finite(y, 6) && sens_finite(pk, 4) && sens_finite(pp, 4);
-        sens_implied_lam(p, k, x, u, y, a, Bm, pk, pp, lam);
+        fin &= load(y, r.yr, 6) & load(pk, r.pi, 4);
+        if (k >= 1) fin &= load(pp, r.pip, 4);
+        const double gu[2] = {p.tau * p.W[4] * (u[0] - y[4]), p.tau * p.W[5] * (u[1] - y[5])};
+        implied_lam(k, p.tau * p.W[3] * (x[3] - y[3]), gu, a, Bm, pk, pp, lam);
     }
     const double v[3] = {x[3], u[0], u[1]};
     double d[3];
@@ -113,14 +73,14 @@ QSP_FN bool sens_nlp_stage(const ShapeDev& sh, const SolveParams& p, int s0_boun
     Hx[3] = p.tau * p.W[3] + d[0];
     Hu[0] = p.tau * p.W[4] + d[1];
     Hu[1] = p.tau * p.W[5] + d[2];
-    return fin && sens_finite(Hx, 4) && sens_finite(Hu, 2);
+    return fin && all_finite(Hx, 4) && all_finite(Hu, 2);
 }
 
 // P_N = diag(He)
 QSP_FN bool sens_terminal(const double He[4], double P[10]) {
     for (int q = 0; q < 10; ++q) P[q] = 0.0;
     P[0] = He[0]; P[4] = He[1]; P[7] = He[2]; P[9] = He[3];
-    return sens_finite(He, 4);
+    return all_finite(He, 4);
 }
 
 // One backward step: P = P_{k+1} -> P_k and the stage gain K (row-major 2 x 4).  The flag covers the stage
@@ -130,8 +90,8 @@ QSP_FN bool sens_back_step(const double a[6], const double Bm[8], const double H
     const double z[4] = {0.0, 0.0, 0.0, 0.0};
     double pv[4] = {0.0, 0.0, 0.0, 0.0}, Rn[3], kk[2];
     ric_factor_step(a, Bm, z, Hx, Hu, z, z, P, pv, K, Rn, kk, true);
-    return sens_finite(a, 6) && sens_finite(Bm, 8) && sens_finite(Hx, 4) && sens_finite(Hu, 2) && sens_finite(Rn, 3) &&
-           sens_finite(K, 8) && sens_finite(P, 10);
+    return all_finite(a, 6) && all_finite(Bm, 8) && all_finite(Hx, 4) && all_finite(Hu, 2) && all_finite(Rn, 3) &&
+           all_finite(K, 8) && all_finite(P, 10);
 }
 
 // One forward step: dU = K Phi (row-major 2 x 4), then Phi <- A Phi + B dU.  Phi is kept by columns:
@@ -147,7 +107,7 @@ QSP_FN bool sens_fwd_step(const double a[6], const double Bm[8], const double K[
         dU[4 + j] = du[1];
         dyn_step(a, Bm, z, du, c);
     }
-    return sens_finite(dU, 8) && sens_finite(Phi, 16);
+    return all_finite(dU, 8) && all_finite(Phi, 16);
 }
 
 QSP_FN void sens_identity(double Phi[16]) {
